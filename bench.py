@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: MIMO U-Net training throughput (images/s) at 256x256, S=2, fbc=30.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config cfg3|cfg2|cfg4]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config cfg3|cfg2|cfg4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs when --dump-outputs is given,
+and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  Everything else it can
+measure or check (the strict-arithmetic pass, the host-enqueue and HIP-event kernel passes with the roofline, the other
+scaling regime at N > 1, the cross-rank parameter check, the CPU baseline) runs only with --full; --no-strict,
+--profile-steps, --one-regime and --no-cpu-baseline trim a --full run.
 
 N > 1 without a torch.distributed environment: this process starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, before anything here touches the GPU) and
@@ -22,13 +28,19 @@ global, 4 per GPU at 8) — `value` at N > 1 is that regime; "weak" = the per-GP
 (32: the reference README's SEN12TP batch size with Lightning-DDP semantics, batch_size = per device).  At N > 1 the
 line carries both (`config.strong_images_per_s`, `config.weak_images_per_s`), each from its own timed pass.
 
-`value_strict` / `ms_per_step_strict`: the same timed pass of a second model under MIMO_WGRAD_NP=3 (three bf16-pair MFMAs per
-product in the weight gradient instead of the default's two fp16 MFMAs with the activation as one fp16 value): the fp32-class
-figure next to the headline (`--no-strict` skips it).
+`value_strict` / `ms_per_step_strict` (--full): the same timed pass of a second model under MIMO_WGRAD_NP=3 (three bf16-pair
+MFMAs per product in the weight gradient instead of the default's two fp16 MFMAs with the activation as one fp16 value): the
+fp32-class figure next to the headline (`--no-strict` skips it); null in a plain run.
 
-The timed region runs WITHOUT instrumentation.  A second, shorter pass with HIP events recorded on the launch
+The timed region runs WITHOUT instrumentation.  With --full, a second, shorter pass with HIP events recorded on the launch
 stream around every kernel class and every resolution tier gives the roofline numbers; at N=1 the CPU oracle
 is timed on this box's host cores for the same workload shape.  ONE JSON line on rank 0.
+
+--dump-outputs DIR: right after the timed steps (before anything --full adds), what the last timed step handed its caller
+(rank 0's at N > 1) as DIR/<name>.npy in float32: the training step's `loss`, `preds`, `aleatoric_std_map`, `err_map` and
+`label`, and `params`, the flat parameters after that step's Adam update.  An array above its element cap (DUMP_CAPS) is
+written as a fixed sample of its flattened elements (numpy default_rng(0), sorted indices), so that the files stay below
+64 MB in all.  Inputs, initial parameters and permutations are seeded: the same arguments give the same inputs every run.
 """
 import argparse
 import json
@@ -61,6 +73,9 @@ FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 at 
 # ceiling for ALGORITHMIC flops is the dense bf16/fp16 MFMA peak (~2500 TFLOP/s) divided by 3
 SPLIT16_PEAK_TFLOPS = 2500.0 / 3.0
 HBM_PEAK_GBS = 8000.0
+# --dump-outputs: elements written per array, at most (4 + 4 + 1 + 1 + 2) * 2^20 float32 = 48 MiB in all
+DUMP_CAPS = {"loss": 1, "preds": 1 << 22, "aleatoric_std_map": 1 << 22, "err_map": 1 << 20, "label": 1 << 20,
+             "params": 1 << 21}
 
 
 def learnable_label(image, noise=0.05, generator=None):
@@ -176,6 +191,19 @@ def cpu_baseline(c, batch=8, warmup=2, steps=5, threads=None, labels="uniform"):
                       f"torch {torch.__version__} CPU, {dt * 1e3:.0f} ms/step"}
 
 
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: each tensor as DIR/<name>.npy in float32, whole up to DUMP_CAPS[name] elements, else that many
+    elements of it flattened, at indices drawn once by numpy's default_rng(0) and sorted (the same for every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        cap = DUMP_CAPS[name]
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def visible_gpu_count(sysfs="/sys/class/kfd/kfd/topology/nodes"):
     """GPUs this process tree will see, WITHOUT any HIP / torch.cuda call (the parent of an N-rank run must not
     initialise the GPU before it starts its children): KFD topology nodes with SIMDs, cut down by
@@ -227,17 +255,25 @@ def main():
     ap.add_argument("--scaling", default=os.environ.get("MIMO_BENCH_SCALING", "strong"), choices=["weak", "strong"])
     ap.add_argument("--labels", default="uniform", choices=["uniform", "learnable"],
                     help="uniform (default): SURVEY 8d's label ~ U[0,1); learnable: label = learnable_label(image)")
-    ap.add_argument("--one-regime", action="store_true", help="N > 1: skip the second timed pass in the other scaling regime")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline timed pass (strict arithmetic, host "
+                         "enqueue, HIP-event kernel pass / roofline, other scaling regime, cross-rank check, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all)")
+    ap.add_argument("--one-regime", action="store_true",
+                    help="--full, N > 1: skip the second timed pass in the other scaling regime")
     ap.add_argument("--no-strict", action="store_true",
-                    help="skip the second timed pass under MIMO_WGRAD_NP=3 (value_strict: the three-MFMA weight gradient)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="steps of the instrumented second pass (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the second timed pass under MIMO_WGRAD_NP=3 (value_strict: the three-MFMA weight gradient)")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: steps of the instrumented second pass (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     # the data path: every step's batch starts in HOST memory and reaches HBM through
     # mimo_unet_amd.data.DevicePrefetcher (pinned double buffer, copy stream, event hand-off) — a diagnostic regime:
     # `value` of the default run is quoted with the inputs resident in HBM, as the contract says
     ap.add_argument("--host-batches", default=None, choices=["pinned", "pageable"],
                     help="feed each step from host tensors (a DataLoader's output: pinned with pin_memory=True) through DevicePrefetcher")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
 
@@ -348,10 +384,13 @@ def main():
 
     adam_events = []
 
-    def step(i, time_adam=False, r=None):
+    def step(i, time_adam=False, r=None, keep=None):
+        """one training step; `keep` (a dict) receives the step's outputs (the last timed step's, for --dump-outputs)"""
         r = r or run
         r.opt.zero_grad()
         out = r.model.training_step(batch if feed is None else next(feed), i)
+        if keep is not None:
+            keep.update(out)
         (r.scaler.scale(out["loss"]) if r.scaler is not None else out["loss"]).backward()
         if r.reducer is not None:
             r.reducer.finish()  # bucketed sums over RCCL were started from inside backward; FlatAdam scales by 1/world
@@ -370,7 +409,7 @@ def main():
 
     host_loop_s = []
 
-    def timed_pass(r=None):
+    def timed_pass(r=None, keep=None):
         """--warmup untimed steps, then EXACTLY --steps steps between barrier + synchronize; max over ranks"""
         for i in range(args.warmup):
             step(i, r=r)
@@ -379,7 +418,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            loss = step(i, r=r)
+            loss = step(i, r=r, keep=keep if i == args.steps - 1 else None)
         host_loop_s.append(time.perf_counter() - t0)  # the host has enqueued every step (it may run ahead of the GPU)
         torch.cuda.synchronize()
         if dist is not None:
@@ -392,12 +431,18 @@ def main():
         return dt, float(loss.detach())
 
     # ---- timed region (the regime of --scaling): no instrumentation ----
-    elapsed, final_loss = timed_pass()
+    last = {} if args.dump_outputs else None
+    elapsed, final_loss = timed_pass(keep=last)
     collectives = list(run.reducer.last_issued) if run.reducer is not None else []
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {k: last[k] for k in ("loss", "preds", "aleatoric_std_map", "err_map", "label")}
+                     | {"params": model.model.flat_parameters()})
+        del last
+    # ---- --full only from here to the line: everything beyond the headline timed pass ----
     # host time to ENQUEUE one step on an idle GPU (outside the timed region): the launch path's share of a step
     # (a diagnostic like the second pass below: --profile-steps 0 skips both, so that traces hold exactly warmup + steps)
     host_ms = []
-    for i in range(3 if args.profile_steps > 0 else 0):
+    for i in range(3 if args.full and args.profile_steps > 0 else 0):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step(i)
@@ -406,7 +451,7 @@ def main():
     host_enqueue_ms = min(host_ms) if host_ms else None
     plan = next(p for p in model.model._plans.values() if not p.inference_only)
     # ---- second pass: HIP events on the launch stream around every kernel class / resolution tier ----
-    prof, tiers, kind_tiers, psteps = {}, [], {}, max(0, args.profile_steps)
+    prof, tiers, kind_tiers, psteps = {}, [], {}, max(0, args.profile_steps) if args.full else 0
     if psteps:
         plan.profile(True)
         for i in range(psteps):
@@ -418,7 +463,7 @@ def main():
     # (MIMO_WGRAD_NP=3, rounds 1-4; ~1e-5 per product like the forward and the data gradient) instead of the default's two
     # fp16 MFMAs with the activation as one fp16 value — a second model and plan in this process, same protocol ----
     strict = None
-    if precision == "split16" and os.environ.get("MIMO_WGRAD_NP") is None and not args.no_strict:
+    if args.full and precision == "split16" and os.environ.get("MIMO_WGRAD_NP") is None and not args.no_strict:
         os.environ["MIMO_WGRAD_NP"] = "3"  # read when the plan is created (the run's first step)
         try:
             r3 = Run()
@@ -432,13 +477,13 @@ def main():
     # Lightning DDP semantics = the batch per device = weak), so that one line carries both, labelled ----
     other = "strong" if args.scaling == "weak" else "weak"
     other_elapsed = None
-    if world > 1 and not args.one_regime and not (other == "strong" and c["batch"] % world):
+    if args.full and world > 1 and not args.one_regime and not (other == "strong" and c["batch"] % world):
         batch = make_batch(other)
         if args.host_batches:
             prefetcher, feed = host_feed(batch)
         other_elapsed, _ = timed_pass()
     identical = None
-    if dist is not None:
+    if args.full and dist is not None:
         # data-parallel invariant: the same initial parameters + the same summed gradients => bit-identical parameters
         flat = model.model.flat_parameters()
         ref = flat.clone()
@@ -592,7 +637,7 @@ def main():
             "bandwidth_kernels": {"peak": HBM_PEAK_GBS, "unit": "GB/s",
                                   "ms_per_step": round(sum(k["ms_per_step"] for k in bw_kernels.values()), 2),
                                   "kernels": bw_kernels}}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(c, labels=args.labels)
     print(json.dumps(line), flush=True)
     if dist is not None:

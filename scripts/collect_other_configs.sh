@@ -14,12 +14,12 @@ for P in bf16-mixed 16-mixed; do  # cfg5 in the 16-bit storage modes (16-mixed =
   runp $P python scripts/measure_inference_speed.py
   runp $P python scripts/measure_inference_speed.py --batch 8
 done
-run python bench.py --config cfg2 --steps 10 --warmup 3 --no-cpu-baseline
-run python bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline
+run python bench.py --full --config cfg2 --steps 10 --warmup 3 --no-cpu-baseline
+run python bench.py --full --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline
 for P in bf16 bf16-mixed 16-mixed; do
-  runp $P python bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline
-  runp $P python bench.py --steps 20 --warmup 5 --no-cpu-baseline
+  runp $P python bench.py --full --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline
+  runp $P python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
 done
-runp fp32 python bench.py --steps 10 --warmup 3 --no-cpu-baseline
-run python bench.py --batch 4 --steps 30 --warmup 8 --no-cpu-baseline --profile-steps 0
+runp fp32 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
+run python bench.py --full --batch 4 --steps 30 --warmup 8 --no-cpu-baseline --profile-steps 0
 cat $O | cut -c1-200

@@ -41,5 +41,5 @@ unset MIMO_WGRAD_STREAM
 if [ -n "${PMC_INSTALL_DIR:-}" ] && [ -f "$OUT/pmc_traffic.json" ]; then
   mkdir -p "$R/$PMC_INSTALL_DIR" && cp "$OUT/pmc_traffic.json" "$R/$PMC_INSTALL_DIR/pmc_traffic.json"
 fi
-cd "$R" && python3 bench.py $BENCH_ARGS --steps ${FINAL_STEPS:-20} --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+cd "$R" && python3 bench.py --full $BENCH_ARGS --steps ${FINAL_STEPS:-20} --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"

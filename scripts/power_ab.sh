@@ -14,7 +14,7 @@ cd "$R"
 for I in 0 1; do
   for W in 0 1; do
     MIMO_CONV_WIDE=$W python3 scripts/power_sample.py "$OUT/bench_wide${W}_$I.power.txt" -- \
-      python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/bench_wide${W}_$I.json" 2> "$OUT/bench_wide${W}_$I.err"
+      python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/bench_wide${W}_$I.json" 2> "$OUT/bench_wide${W}_$I.err"
     head -4 "$OUT/bench_wide${W}_$I.power.txt"
     python3 - "$OUT/bench_wide${W}_$I.json" <<'PY'
 import json, sys

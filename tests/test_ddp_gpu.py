@@ -162,7 +162,7 @@ def test_bench_spawns_its_own_ranks_gloo_sharing_the_gpu():
     the driver uses); here over gloo with both ranks on GPU 0 so that it runs on a single-GPU box.  Strong scaling:
     the global batch of 4 is sharded 2 + 2; rank-0 parameters are broadcast at start and all ranks end bit-identical."""
     line = _run_bench({"MIMO_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                      "--scaling", "strong", "--profile-steps", "0", "--no-cpu-baseline")
+                      "--scaling", "strong", "--full", "--profile-steps", "0", "--no-cpu-baseline")
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["steps"] == 2
     cfg = line["config"]
     assert cfg["global_batch"] == 4 and cfg["per_gpu_batch"] == 2
@@ -180,7 +180,7 @@ def test_bench_eight_ranks_gloo_sharing_the_gpu():
     4 per rank (ddp.shard_batch), the backward of every rank issues the same five bucketed collectives, and all eight ranks
     end with bit-identical parameters.  Not a performance configuration."""
     line = _run_bench({"MIMO_BENCH_BACKEND": "gloo", "OMP_NUM_THREADS": "2"}, "--gpus", "8", "--steps", "2", "--warmup", "1",
-                      "--batch", "32", "--scaling", "strong", "--profile-steps", "0", "--no-cpu-baseline", "--no-strict",
+                      "--batch", "32", "--scaling", "strong", "--full", "--profile-steps", "0", "--no-cpu-baseline", "--no-strict",
                       "--one-regime")
     cfg = line["config"]
     assert line["n_gpus"] == 8 and cfg["world_size"] == 8 and cfg["backend"] == "gloo" and cfg["rccl_ranks"] is None
@@ -197,7 +197,7 @@ def test_bench_two_ranks_reduce_scatter_all_gather(algo):
     """The reduce-scatter + all-gather form of the exchange (ddp.FlatGradientAllReducer(algorithm=...), MIMO_DDP_ALGO) through
     the real step: two ranks over gloo on GPU 0, parameters bit-identical across the ranks at the end."""
     line = _run_bench({"MIMO_BENCH_BACKEND": "gloo", "MIMO_DDP_ALGO": algo}, "--gpus", "2", "--steps", "2", "--warmup", "1",
-                      "--batch", "4", "--profile-steps", "0", "--no-cpu-baseline", "--no-strict", "--one-regime")
+                      "--batch", "4", "--full", "--profile-steps", "0", "--no-cpu-baseline", "--no-strict", "--one-regime")
     cfg = line["config"]
     assert cfg["ddp_algorithm"] == algo and cfg["collectives_per_step"] == N_COLLECTIVES_CFG3, cfg["collective_mbytes"]
     assert cfg["params_bit_identical_across_ranks"] is True
@@ -205,7 +205,7 @@ def test_bench_two_ranks_reduce_scatter_all_gather(algo):
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL over xGMI)")
 def test_bench_two_ranks_rccl():
-    line = _run_bench({}, "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "4", "--profile-steps", "0",
+    line = _run_bench({}, "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "4", "--full", "--profile-steps", "0",
                       "--no-cpu-baseline")
     # default regime = strong: the batch of 4 is the global batch, 2 per GPU; the weak regime rides along
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["global_batch"] == 4

@@ -264,21 +264,30 @@ def test_evidential_loss_class_matches_golden():
     assert float(crit(ev, y, reduce_mean=True)) == float(crit(ev, y).mean())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/mimo"), reason="needs the reference checkout (build container only)")
-def test_alias_package_resolves_unmirrored_submodules_from_the_reference():
+def test_alias_package_resolves_unmirrored_submodules_from_the_reference(tmp_path):
     """scripts/train/train_ndvi.py:10-13 imports mimo.models.* (mirrored here) and mimo.tasks / mimo.datasets (not):
-    with the repo first and the reference second on PYTHONPATH both resolve, each from its own tree."""
+    with the repo first and the reference second on PYTHONPATH both resolve, each from its own tree.  The reference
+    checkout is stood in for by a tree of the same layout (an empty mimo/__init__.py, its own mimo.models / mimo.losses,
+    which must lose to ours, and the unmirrored mimo.regularization / mimo.visualization, which must be found there)."""
     import subprocess
     import sys
+    ref = tmp_path / "reference"
+    for rel in ("mimo/__init__.py", "mimo/models/__init__.py"):
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text("")
+    for rel in ("mimo/models/mimo_unet.py", "mimo/models/ensemble.py", "mimo/losses.py", "mimo/regularization.py",
+                "mimo/visualization.py"):
+        (ref / rel).write_text("TREE = 'reference'\n")
     code = ("import mimo.models.mimo_unet as a, mimo.models.ensemble as e, mimo.losses as l\n"
             "import mimo.regularization as r, mimo.visualization as v\n"
             "print(a.__file__); print(e.__file__); print(l.__file__); print(r.__file__); print(v.__file__)\n")
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + "/root/reference", PYTHONDONTWRITEBYTECODE="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, cwd="/tmp", capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + str(ref), PYTHONDONTWRITEBYTECODE="1")
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=str(tmp_path), capture_output=True, text=True,
+                         timeout=300)
     assert out.returncode == 0, out.stderr
     files = out.stdout.split()
     assert all(f.startswith(ROOT + os.sep) for f in files[:3]), files
-    assert all(f.startswith("/root/reference/") for f in files[3:]), files
+    assert all(f.startswith(str(ref) + os.sep) for f in files[3:]), files
 
 
 class _FakeFlatNet(torch.nn.Module):
@@ -471,6 +480,25 @@ def test_bench_algorithmic_byte_model_matches_survey_table():
     flops = 3 * sum(2 * ci * co * k * k * h * w for _, ci, co, h, w, k in bench.conv_layers(bench.CONFIGS["cfg3"]))
     assert round(flops / 1e9, 1) == 194.8
     assert round(bench.algorithmic_bytes_per_image(bench.CONFIGS["cfg2"])[1] / 1e6, 1) == 605.0
+
+
+def test_bench_dump_outputs_caps_and_samples_deterministically(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array, whole up to its cap, else the same seeded sample of its elements every run;
+    the caps keep the files below 64 MB in all."""
+    import bench
+    assert 4 * sum(bench.DUMP_CAPS.values()) < 64e6
+    monkeypatch.setitem(bench.DUMP_CAPS, "preds", 10)
+    preds = torch.arange(24, dtype=torch.float64).view(2, 3, 4)
+    loss = torch.tensor(1.5, dtype=torch.float16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"preds": preds, "loss": loss})
+    a, b = np.load(tmp_path / "a" / "preds.npy"), np.load(tmp_path / "b" / "preds.npy")
+    assert a.dtype == np.float32 and a.shape == (10,) and np.array_equal(a, b)
+    assert len(set(a.tolist())) == 10 and set(a.tolist()) <= set(range(24)) and np.all(np.diff(a) > 0)
+    lo = np.load(tmp_path / "a" / "loss.npy")
+    assert lo.dtype == np.float32 and lo.shape == () and float(lo) == 1.5
+    bench.dump_outputs(str(tmp_path / "c"), {"preds": preds[0, :2]})  # 8 elements: whole, shape kept
+    assert np.array_equal(np.load(tmp_path / "c" / "preds.npy"), preds[0, :2].numpy().astype(np.float32))
 
 
 def test_flat_adam_follows_the_grad_scaler_protocol_for_fused_optimizers(monkeypatch):
