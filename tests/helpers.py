@@ -147,3 +147,236 @@ def report(*parts):
         test = os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0]
         with open(path, "a") as fh:
             fh.write(f"{test}: {msg}\n")
+
+
+# ---- 3 x 3 convolutions: the benchmark's layer table, an fp64 reference, the comparison rules of the operator tests ----
+
+# resolution level (256 >> level) of each DoubleConv, by state_dict prefix (model.py:119-297: four 2x2 poolings down, four
+# 2x up-samplings back)
+_DOUBLE_CONV_LEVEL = {"encoder.in_convs": 0, "encoder.down1s": 1, "core.down2": 2, "core.down3": 3, "core.down4": 4,
+                      "core.up1": 3, "core.up2": 2, "core.up3": 1, "decoder.up4s": 0}
+BENCH_GPU_COUNTS = (1, 2, 4, 8)  # strong scaling: the config's batch is the global batch, sharded over 1 / 2 / 4 / 8 GPUs
+
+
+def pad8(c):
+    return (c + 7) // 8 * 8
+
+
+def conv_cin_pad(c):
+    """padded input channels of a convolution as the plan stores them: 4-channel pixels for the image (<= 4 channels),
+    8-channel units otherwise"""
+    return (c + 3) // 4 * 4 if c <= 4 else pad8(c)
+
+
+def config_conv_layers(c, n):
+    """(N, H, W, Cin, Cout) of every 3 x 3 convolution of bench.CONFIGS entry `c` at `n` images per GPU, distinct"""
+    cfg = O.NetConfig(in_channels=c["Ci"], out_channels=c["Co"], num_subnetworks=c["S"], filter_base_count=c["f"])
+    out = []
+    for prefix, cin, cmid, cout in O.double_conv_specs(cfg):
+        level = next(v for k, v in _DOUBLE_CONV_LEVEL.items() if prefix.startswith(k + "."))
+        h, w = c["H"] >> level, c["W"] >> level
+        for t in ((n, h, w, cin, cmid), (n, h, w, cmid, cout)):
+            if t not in out:
+                out.append(t)
+    return out
+
+
+def benchmark_shards(c):
+    """per-GPU batches bench.py runs config `c` at: its batch, and its strong-scaling shards at 2, 4 and 8 GPUs"""
+    return [c["batch"] // g for g in BENCH_GPU_COUNTS]
+
+
+def benchmark_conv_layers():
+    """The distinct (N, H, W, Cin, Cout) of every 3 x 3 convolution the benchmark runs: every config of bench.CONFIGS
+    at every per-GPU batch of benchmark_shards, in a fixed order (config, batch, forward order of the layers)."""
+    import bench
+    out = []
+    for c in bench.CONFIGS.values():
+        for n in benchmark_shards(c):
+            out += [t for t in config_conv_layers(c, n) if t not in out]
+    return out
+
+
+def conv3x3_reference_f64(x, w, b, dz, chunk_elems=1 << 26):
+    """Reference of one 3 x 3 reflect-padded convolution (components.py:23,26) in float64, on the inputs' device.
+
+    x [N, H, W, >= Cin] and dz [N, H, W, >= Cout] are NHWC (channels past w's are ignored), w [Cout, Cin, 3, 3], b [Cout].
+    Returns float64 z [N, H, W, Cout], dx [N, H, W, Cin], dw, db and the per-channel sums of z and z^2 ("sum", "sumsq").
+    The convolution is nine shifted matmuls, one per tap; autograd gives the backward, including the fold of the reflect
+    border.  Images are processed in chunks of about `chunk_elems` input / output elements (the sums are accumulated in
+    float64 across chunks)."""
+    import torch.nn.functional as F
+    Co, Ci = w.shape[:2]
+    N, H, W = x.shape[:3]
+    per_image = H * W * max(Ci, Co)
+    step = max(1, chunk_elems // per_image)
+    wt = w.detach().double().requires_grad_(True)
+    bt = b.detach().double().requires_grad_(True)
+    zs, dxs = [], []
+    for n0 in range(0, N, step):
+        xc = x[n0:n0 + step, ..., :Ci].double().requires_grad_(True)
+        xp = F.pad(xc.permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect").permute(0, 2, 3, 1)
+        z = bt
+        for ky in range(3):
+            for kx in range(3):
+                z = z + xp[:, ky:ky + H, kx:kx + W, :] @ wt[:, :, ky, kx].t()
+        z.backward(dz[n0:n0 + step, ..., :Co].double())
+        zs.append(z.detach())
+        dxs.append(xc.grad)
+    z = torch.cat(zs)
+    return {"z": z, "dx": torch.cat(dxs), "dw": wt.grad, "db": bt.grad, "sum": z.sum(dim=(0, 1, 2)),
+            "sumsq": (z * z).sum(dim=(0, 1, 2))}
+
+
+def worst_at(a, b):
+    """index (as a tuple) of the largest |a - b|"""
+    d = (torch.as_tensor(a, dtype=torch.float64) - torch.as_tensor(b, dtype=torch.float64)).abs()
+    return tuple(int(i) for i in np.unravel_index(int(d.argmax()), tuple(d.shape)))
+
+
+def err_where(a, b):
+    """rel_err(a, b) and worst_at(a, b) from one difference"""
+    b = torch.as_tensor(b, dtype=torch.float64)
+    d = (torch.as_tensor(a, dtype=torch.float64) - b).abs()
+    i = int(d.argmax())
+    return float(d.flatten()[i]) / max(float(b.abs().max()), 1e-30), tuple(int(k) for k in np.unravel_index(i, tuple(d.shape)))
+
+
+def conv_tolerances(precision):
+    """Per-quantity bounds (max |ours - ref| / max |ref|) of the 3 x 3 convolution operators against a reference of the
+    same operation on the same (unrounded) operands; the derivations are in test_ops_gpu.py::test_conv3x3_forward_dgrad_wgrad.
+    fp32: accumulation order only.  split16: fp16 / bf16 hi-lo pairs; the two-MFMA weight gradient (one fp16 activation)
+    5e-4.  bf16: operands rounded to bf16.  The bias gradient is an fp32 column sum in every mode; the statistics are sums
+    of the outputs."""
+    tol = {"fp32": 2e-5, "split16": 1e-4, "bf16": 2e-2}[precision]
+    stat = 2e-2 if precision == "bf16" else 2e-5
+    return {"fwd": tol, "dgrad": tol, "wgrad": 5e-4 if wgrad_two_mfma(precision) else tol, "bgrad": 2e-5, "sum": stat,
+            "sumsq": stat}
+
+
+# quantity -> (key of conv3x3_reference_f64's result, key of the kernel outputs), as check_conv_results compares them
+_CONV_QUANTITIES = {"fwd": ("z", "z"), "dgrad": ("dx", "dx"), "wgrad": ("dw", "dw"), "bgrad": ("db", "db"),
+                    "sum": ("sum", "stats0"), "sumsq": ("sumsq", "stats1")}
+
+
+def conv_outputs(z, stats, dx, dw, db, Ci, Co):
+    """the kernel results of one forward / data gradient / weight gradient as check_conv_results takes them (any of them
+    may be None when that operator was not run)"""
+    out = {}
+    if z is not None:
+        out.update(z_full=z, z=z[..., :Co], stats0=stats[0], stats1=stats[1])
+    if dx is not None:
+        out.update(dx_full=dx, dx=dx[..., :Ci])
+    if dw is not None:
+        out.update(dw=dw, db=db)
+    return out
+
+
+def check_conv_results(got, ref, precision, label, tols=None):
+    """Compare the outputs of mimo_op_conv3x3_forward / _dgrad / _wgrad (conv_outputs; the output buffers were filled with
+    NaN before the calls) with a reference of the same operation (the keys of conv3x3_reference_f64).  Asserts that every
+    output was fully overwritten, that the padding channels of z are exactly zero, and the per-quantity bounds
+    (conv_tolerances(precision), or `tols`).  The errors and the index of each quantity's worst element — (image, row,
+    column, channel) of z / dx, (cout, cin, ky, kx) of dW, the channel of db and of the sums — go through report() after
+    `label` (a tuple); they are also returned."""
+    tols = tols or conv_tolerances(precision)
+    if "z_full" in got:
+        Co = got["z"].shape[-1]
+        assert bool(torch.isfinite(got["z_full"]).all()), "z not fully written (NaN left in the output)"
+        assert bool((got["z_full"][..., Co:] == 0).all()), "padding channels of z must be exactly zero"
+    if "dx_full" in got:
+        assert bool(torch.isfinite(got["dx_full"]).all()), "dx not fully written (NaN left in the output)"
+    if "dw" in got:
+        assert bool(torch.isfinite(got["dw"]).all() and torch.isfinite(got["db"]).all()), "dW / db not fully written"
+    errs, where = {}, {}
+    for q, (rk, gk) in _CONV_QUANTITIES.items():
+        if gk not in got:
+            continue
+        a, r = got[gk], ref[rk].to(got[gk].device)
+        if q == "sum" and got["z"].shape[1] * got["z"].shape[2] <= 4:
+            errs[q], where[q] = 0.0, ()  # (2 x 2 images: every output sums the same four inputs, sum z cancels)
+            continue
+        errs[q], where[q] = err_where(a, r)
+    report(*label, {q: f"{e:.2e}" for q, e in errs.items()}, "worst at", where)
+    bad = {q: e for q, e in errs.items() if not e < tols[q]}
+    assert not bad, (bad, {q: where[q] for q in bad})
+    return errs, where
+
+
+STORAGE_TYPES = {"bf16-mixed": (torch.bfloat16, 2.0 ** -7), "16-mixed": (torch.float16, 2.0 ** -10)}  # type, largest relative spacing
+
+
+def fp32_acc_bound(k, small):
+    """Bound (of a tensor's scale) for the fp32 accumulation error of sums of `k` exact products, never below `small`.
+    A running fp32 sum adds a rounding error of up to 2^-25 of its partial sum per step: over a chain of k steps a random
+    walk of about 2^-24 * sqrt(k / 3) of the partial sums' scale.  Blocked and split accumulations only shorten the chains,
+    so 2^-24 * sqrt(k), with k the full reduction length (9 x Cin forward, 9 x Cout data gradient, N x H x W weight
+    gradient), bounds them; observed on the benchmark's layers (test_conv3x3_at_benchmark_batches_vs_fp64): 0.25 ... 0.37
+    of it on the bf16 forward and data gradient (2.0e-6 at k = 8640, 1.95e-6 at 17280), at most 0.3 of it on the weight
+    gradients (2.2e-6 at k = 65536, <= 1.5e-6 at k = 2^20 where the kernels split the pixels into slabs)."""
+    return max(small, 2.0 ** -24 * k ** 0.5)
+
+
+def check_bf16_rounded(got, ref, label, acc_k=None, fp32_ref=None):
+    """MIMO_PREC_BF16 kernels compute exactly the convolution of the bf16-rounded operands with fp32 accumulation: z, dx and
+    dW against a reference of the same operation on round_bf16(x), round_bf16(w), round_bf16(dz) within 2e-6 of each
+    tensor's scale (derived on reduction lengths <= 4096); with `acc_k` ({quantity: reduction length}) within
+    fp32_acc_bound(k, 2e-6).  With `fp32_ref` (the reference on the unrounded operands), a forward or weight gradient that
+    ran on the plain-FMA fp32 kernels instead (the image layer, conv_thin.hip, taken by the plan in this mode too) passes
+    at the fp32 bound 2e-5 against it.  Reports (after `label`) and returns {quantity: error}, {quantity: worst index}."""
+    errs, where, bad = {}, {}, {}
+    for q, rk in (("fwd", "z"), ("dgrad", "dx"), ("wgrad", "dw")):
+        r = ref[rk].to(got[rk].device)
+        errs[q], where[q] = err_where(got[rk], r)
+        if errs[q] < (fp32_acc_bound(acc_k[q], 2e-6) if acc_k else 2e-6):
+            continue
+        e32 = err_where(got[rk], fp32_ref[rk].to(got[rk].device)) if fp32_ref is not None and q != "dgrad" else None
+        if e32 is not None and e32[0] < 2e-5:  # (reported as "<quantity>_fp32": the error against the unrounded operands)
+            del errs[q], where[q]
+            errs[q + "_fp32"], where[q + "_fp32"] = e32
+        else:
+            bad[q] = errs[q]
+    report(*label, {q: f"{e:.2e}" for q, e in errs.items()}, "worst at", where)
+    assert not bad, (bad, {q: where[q] for q in bad})
+    return errs, where
+
+
+def check_storage_rounded(got, ref, mode, label, acc_k=None):
+    """The 16-bit STORAGE kernels (bf16-mixed / 16-mixed): products of the rounded operands exact, fp32 accumulation, the
+    output rounded ONCE to the storage type.  `ref` is the same operation on the rounded operands, unrounded (keys of
+    conv3x3_reference_f64, NHWC).  z and dx must be representable in the storage type; z within one unit in the last place
+    of the rounded reference element-wise (and >= 98 % identical); dx interior pixels within one unit element-wise, the two
+    border rows / columns (sums of up to four rounded padded-domain values, which may cancel) within two units of the
+    tensor's scale; dW (fp32 output) within 5e-6 of its scale; the BatchNorm sums (from the unrounded accumulators) within
+    1e-5.  The element-wise forward criterion measures a unit at max(|z|, 1e-3): near zero, the fp32 accumulation error
+    of the K = 9 x Cin products can exceed one unit of the value itself (cancellation).  With `acc_k` ({"fwd": K}) the
+    floor is max(1e-3, fp32_acc_bound(K, 0) * max|z| / ulp) — the element-wise error stays within the fp32 accumulation
+    bound of the tensor's scale there (observed in 16-mixed on the benchmark's layers: up to 1.95 units at the 1e-3 floor
+    for K = 2160 ... 8640, all within one unit of the K floor; bf16-mixed, whose unit is 8 x wider, stays within one unit
+    at 1e-3).  Reports (after `label`) and returns the errors (z and dx in units in the last place) and the worst
+    indices."""
+    dt, ulp = STORAGE_TYPES[mode]
+    dev = got["z"].device
+    r = lambda t: t.to(dt).double()
+    z, dx = got["z"].double(), got["dx"].double()
+    zr, dxr = ref["z"].to(dev), ref["dx"].to(dev)
+    assert torch.equal(r(z), z) and torch.equal(r(dx), dx), "outputs not representable in the storage type"
+    floor = max(1e-3, fp32_acc_bound(acc_k["fwd"], 0.0) * float(zr.abs().max()) / ulp) if acc_k else 1e-3
+    ez_all = (z - r(zr)).abs() / zr.abs().clamp_min(floor)
+    gref, gmax = r(dxr), float(dxr.abs().max())
+    rel = (dx - gref).abs() / dxr.abs().clamp_min(1e-3 * gmax)
+    H, W = z.shape[1:3]
+    e_int = float(rel[:, 2:-2, 2:-2, :].max()) if H > 4 and W > 4 else 0.0
+    errs = {"fwd_ulp": float(ez_all.max()) / ulp, "dgrad_ulp": max(e_int, float((dx - gref).abs().max()) / gmax / 2) / ulp,
+            "fwd_identical": float((z == r(zr)).double().mean())}
+    where = {"fwd_ulp": worst_at(ez_all, torch.zeros_like(ez_all)), "dgrad_ulp": worst_at(dx, gref)}
+    for q, gk, rk in (("wgrad", "dw", "dw"), ("sum", "stats0", "sum"), ("sumsq", "stats1", "sumsq")):
+        errs[q], where[q] = err_where(got[gk], ref[rk].to(dev))
+    ok = {"fwd_ulp": errs["fwd_ulp"] <= 1.01, "fwd_identical": errs["fwd_identical"] > 0.98,
+          "dgrad_ulp": errs["dgrad_ulp"] <= 1.01, "wgrad": errs["wgrad"] < 5e-6, "sum": errs["sum"] < 1e-5,
+          "sumsq": errs["sumsq"] < 1e-5}
+    report(*label, f"z {errs['fwd_ulp']:.2f} ulp ({100 * errs['fwd_identical']:.2f} % identical), dx {errs['dgrad_ulp']:.2f} ulp, "
+           f"dW {errs['wgrad']:.1e}, sums {errs['sum']:.1e} / {errs['sumsq']:.1e}", "worst at", where)
+    bad = {q: errs[q] for q, v in ok.items() if not v}
+    assert not bad, (bad, {q: where.get(q) for q in bad})
+    return errs, where

@@ -7,11 +7,10 @@ import torch
 import torch.nn.functional as F
 
 from oracle import mimo_oracle as O
-from tests.helpers import rel_err, report
+from tests.helpers import (STORAGE_TYPES, benchmark_conv_layers, check_bf16_rounded, check_conv_results, check_storage_rounded,
+                           config_conv_layers, conv3x3_reference_f64, conv_cin_pad, conv_outputs, pad8, rel_err, report)
 
 pytestmark = pytest.mark.gpu
-
-TOL = 2e-5  # fp32 implicit-GEMM vs fp32 direct conv: accumulation order only
 
 
 def _lib():
@@ -19,8 +18,8 @@ def _lib():
     return _lib
 
 
-def pad8(c):
-    return (c + 7) // 8 * 8
+def nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
 
 
 def to_nhwc(x, cp):
@@ -32,6 +31,32 @@ def to_nhwc(x, cp):
 
 def from_nhwc(t, c):
     return t[..., :c].permute(0, 3, 1, 2).contiguous().cpu()
+
+
+def run_conv(lib, xd, wd, bd, dzd, Ci, Co, prec, fwd=True, dgrad=True, wgrad=True):
+    """mimo_op_conv3x3_forward / _dgrad / _wgrad on device NHWC x [N, H, W, cip] and dz [N, H, W, cop] (padding channels
+    zero), w [Co, Ci, 3, 3], b [Co]; every output buffer starts NaN-filled.  Returns conv_outputs(...)."""
+    L = _lib()
+    N, H, W, cip = xd.shape
+    cop, st = dzd.shape[-1], L.current_stream()
+    nan = float("nan")
+    z = stats = dx = dw = db = None
+    if fwd:
+        z = torch.full((N, H, W, cop), nan, device="cuda")
+        stats = torch.full((2, Co), nan, dtype=torch.float64, device="cuda")
+        L.check(lib.mimo_op_conv3x3_forward(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), z.data_ptr(), stats.data_ptr(), N, H, W,
+                                            Ci, cip, Co, cop, prec, st), "conv fwd")
+    if dgrad:
+        dx = torch.full((N, H, W, cip), nan, device="cuda")
+        L.check(lib.mimo_op_conv3x3_dgrad(dzd.data_ptr(), wd.data_ptr(), dx.data_ptr(), N, H, W, Ci, cip, Co, cop, prec, st),
+                "conv dgrad")
+    if wgrad:
+        dw = torch.full((Co, Ci, 3, 3), nan, device="cuda")
+        db = torch.full((Co,), nan, device="cuda")
+        L.check(lib.mimo_op_conv3x3_wgrad(xd.data_ptr(), dzd.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, Ci, cip, Co, cop,
+                                          prec, st), "conv wgrad")
+    torch.cuda.synchronize()
+    return conv_outputs(z, stats, dx, dw, db, Ci, Co)
 
 
 CONV_CASES = [
@@ -66,7 +91,6 @@ def test_conv3x3_forward_dgrad_wgrad(case, precision):
     bf16: operands rounded to bf16 (2^-9 each), fp32 accumulation -> 2e-2 of the tensor's scale."""
     L = _lib()
     prec = L.PRECISIONS[precision]
-    tol = {"fp32": TOL, "split16": 1e-4, "bf16": 2e-2}[precision]
     lib = L.load()
     N, H, W, Ci, Co = case
     g = torch.Generator().manual_seed(sum(case))
@@ -79,40 +103,13 @@ def test_conv3x3_forward_dgrad_wgrad(case, precision):
     br = b.clone().requires_grad_(True)
     z_ref = O.conv3x3_reflect(xr, wr, br)
     z_ref.backward(dz)
-    cip, cop = (Ci + 3) // 4 * 4 if Ci <= 4 else pad8(Ci), pad8(Co)
-    st = L.current_stream()
-    xd, wd_, bd = to_nhwc(x, cip), w.cuda().contiguous(), b.cuda()
-    zd = torch.full((N, H, W, cop), float("nan"), device="cuda")
-    stats = torch.zeros(2, Co, dtype=torch.float64, device="cuda")
-    L.check(lib.mimo_op_conv3x3_forward(xd.data_ptr(), wd_.data_ptr(), bd.data_ptr(), zd.data_ptr(), stats.data_ptr(),
-                                        N, H, W, Ci, cip, Co, cop, prec, st), "conv fwd")
-    torch.cuda.synchronize()
-    z = from_nhwc(zd, Co)
-    errs = {"fwd": rel_err(z, z_ref.detach())}
-    assert torch.all(zd[..., Co:] == 0), "padding channels of z must be exactly zero"
     zr64 = z_ref.detach().double()
-    errs["sum"] = rel_err(stats[0].cpu(), zr64.sum(dim=(0, 2, 3))) if H * W > 4 else 0.0
-    errs["sumsq"] = rel_err(stats[1].cpu(), (zr64 * zr64).sum(dim=(0, 2, 3)))
-    # data gradient (transposed conv + fold of the reflect border)
-    dzd = to_nhwc(dz, cop)
-    dxd = torch.full((N, H, W, cip), float("nan"), device="cuda")
-    L.check(lib.mimo_op_conv3x3_dgrad(dzd.data_ptr(), wd_.data_ptr(), dxd.data_ptr(), N, H, W, Ci, cip, Co, cop, prec, st),
-            "conv dgrad")
-    errs["dgrad"] = rel_err(from_nhwc(dxd, Ci), xr.grad)
-    # weight / bias gradient
-    dwd = torch.full((Co, Ci, 3, 3), float("nan"), device="cuda")
-    dbd = torch.full((Co,), float("nan"), device="cuda")
-    L.check(lib.mimo_op_conv3x3_wgrad(xd.data_ptr(), dzd.data_ptr(), dwd.data_ptr(), dbd.data_ptr(), N, H, W, Ci, cip,
-                                      Co, cop, prec, st), "conv wgrad")
-    errs["wgrad"] = rel_err(dwd.cpu(), wr.grad)
-    errs["bgrad"] = rel_err(dbd.cpu(), br.grad)
-    report("conv", precision, case, {k: f"{v:.2e}" for k, v in errs.items()})
-    stat_tol = TOL if precision != "bf16" else 2e-2  # the statistics are sums of the (bf16-product) outputs
-    import os
-    wg_tol = 5e-4 if precision == "split16" and os.environ.get("MIMO_WGRAD_NP") != "3" else tol
-    bad = {k: v for k, v in errs.items()
-           if not v < (TOL if k == "bgrad" else stat_tol if k in ("sum", "sumsq") else wg_tol if k == "wgrad" else tol)}
-    assert not bad, bad
+    ref = {"z": nhwc(z_ref.detach()), "dx": nhwc(xr.grad), "dw": wr.grad, "db": br.grad, "sum": zr64.sum(dim=(0, 2, 3)),
+           "sumsq": (zr64 * zr64).sum(dim=(0, 2, 3))}
+    cip, cop = conv_cin_pad(Ci), pad8(Co)
+    xd, dzd = to_nhwc(x, cip), to_nhwc(dz, cop)
+    got = run_conv(lib, xd, w.cuda().contiguous(), b.cuda(), dzd, Ci, Co, prec)
+    check_conv_results(got, ref, precision, ("conv", precision, case))
 
 
 @pytest.mark.parametrize("shape", [(2, 16, 32, 32), (1, 8, 25, 51), (1, 24, 6, 6), (2, 8, 3, 2)])
@@ -288,21 +285,9 @@ def test_bf16_conv_kernels_against_rounded_operand_reference(case):
     xr = x.clone().requires_grad_(True)
     F.pad(xr, (1, 1, 1, 1), mode="reflect").backward(torch.nn.grad.conv2d_input(xp.shape, r(w), r(dz)))
     dw_ref = torch.nn.grad.conv2d_weight(r(xp), w.shape, r(dz))
-    cip, cop, st = pad8(Ci), pad8(Co), L.current_stream()
-    xd, wd_, bd, dzd = to_nhwc(x, cip), w.cuda().contiguous(), b.cuda(), to_nhwc(dz, cop)
-    zd = torch.zeros(N, H, W, cop, device="cuda")
-    stats = torch.zeros(2, Co, dtype=torch.float64, device="cuda")
-    dxd = torch.zeros(N, H, W, cip, device="cuda")
-    dwd, dbd = torch.zeros(Co, Ci, 3, 3, device="cuda"), torch.zeros(Co, device="cuda")
-    L.check(lib.mimo_op_conv3x3_forward(xd.data_ptr(), wd_.data_ptr(), bd.data_ptr(), zd.data_ptr(), stats.data_ptr(), N, H, W,
-                                        Ci, cip, Co, cop, prec, st))
-    L.check(lib.mimo_op_conv3x3_dgrad(dzd.data_ptr(), wd_.data_ptr(), dxd.data_ptr(), N, H, W, Ci, cip, Co, cop, prec, st))
-    L.check(lib.mimo_op_conv3x3_wgrad(xd.data_ptr(), dzd.data_ptr(), dwd.data_ptr(), dbd.data_ptr(), N, H, W, Ci, cip, Co, cop,
-                                      prec, st))
-    torch.cuda.synchronize()
-    errs = (rel_err(from_nhwc(zd, Co), z_ref), rel_err(from_nhwc(dxd, Ci), xr.grad), rel_err(dwd.cpu(), dw_ref))
-    report("bf16 exact", case, ["%.2e" % e for e in errs])
-    assert max(errs) < 2e-6
+    cip, cop = pad8(Ci), pad8(Co)
+    got = run_conv(lib, to_nhwc(x, cip), w.cuda().contiguous(), b.cuda(), to_nhwc(dz, cop), Ci, Co, prec)
+    check_bf16_rounded(got, {"z": nhwc(z_ref), "dx": nhwc(xr.grad), "dw": dw_ref}, ("bf16 exact", case))
 
 
 @pytest.mark.parametrize("mode", ["bf16-mixed", "16-mixed"])
@@ -321,8 +306,7 @@ def test_storage_mode_conv_kernels_against_rounded_reference(case, mode):
     L = _lib()
     lib = L.load()
     prec = L.PRECISIONS[mode]
-    dt = torch.bfloat16 if mode == "bf16-mixed" else torch.float16
-    ulp = 2.0 ** -7 if mode == "bf16-mixed" else 2.0 ** -10  # largest relative spacing of the type (8 / 11 significant bits)
+    dt = STORAGE_TYPES[mode][0]
     N, H, W, Ci, Co = case
     r = lambda t: t.to(dt).float()
     g = torch.Generator().manual_seed(sum(case))
@@ -333,37 +317,14 @@ def test_storage_mode_conv_kernels_against_rounded_reference(case, mode):
     xp = F.pad(x, (1, 1, 1, 1), mode="reflect")
     z32 = F.conv2d(xp, r(w)) + b[None, :, None, None]
     xr = x.clone().requires_grad_(True)
+    # (the padded-domain data gradient rounded to the storage type, folded in fp32: check_storage_rounded rounds the fold)
     F.pad(xr, (1, 1, 1, 1), mode="reflect").backward(r(torch.nn.grad.conv2d_input(xp.shape, r(w), dz)))
     dw_ref = torch.nn.grad.conv2d_weight(xp, w.shape, dz)
-    cip, cop, st = pad8(Ci), pad8(Co), L.current_stream()
-    xd, wd_, bd, dzd = to_nhwc(x, cip), w.cuda().contiguous(), b.cuda(), to_nhwc(dz, cop)
-    zd = torch.zeros(N, H, W, cop, device="cuda")
-    stats = torch.zeros(2, Co, dtype=torch.float64, device="cuda")
-    dxd = torch.zeros(N, H, W, cip, device="cuda")
-    dwd, dbd = torch.zeros(Co, Ci, 3, 3, device="cuda"), torch.zeros(Co, device="cuda")
-    L.check(lib.mimo_op_conv3x3_forward(xd.data_ptr(), wd_.data_ptr(), bd.data_ptr(), zd.data_ptr(), stats.data_ptr(), N, H, W,
-                                        Ci, cip, Co, cop, prec, st))
-    L.check(lib.mimo_op_conv3x3_dgrad(dzd.data_ptr(), wd_.data_ptr(), dxd.data_ptr(), N, H, W, Ci, cip, Co, cop, prec, st))
-    L.check(lib.mimo_op_conv3x3_wgrad(xd.data_ptr(), dzd.data_ptr(), dwd.data_ptr(), dbd.data_ptr(), N, H, W, Ci, cip, Co, cop,
-                                      prec, st))
-    torch.cuda.synchronize()
-    z, dx = from_nhwc(zd, Co), from_nhwc(dxd, Ci)
-    assert torch.equal(r(z), z) and torch.equal(r(dx), dx)  # representable in the storage type
-    # element-wise: within one (two) unit(s) in the last place of the reference value
-    ez = ((z - r(z32)).abs() / z32.abs().clamp_min(1e-3)).max().item()
-    # data gradient: interior pixels are one rounded value (<= 1 ulp element-wise); the two border rows / columns are
-    # sums of up to four rounded padded-domain values, which may cancel: bounded relative to the tensor's scale
-    gref, gmax = r(xr.grad), float(xr.grad.abs().max())
-    rel = (dx - gref).abs() / xr.grad.abs().clamp_min(1e-3 * gmax)
-    e_int = rel[:, :, 2:-2, 2:-2].max().item() if H > 4 and W > 4 else 0.0
-    edx = max(e_int, float((dx - gref).abs().max()) / gmax / 2)
-    same = (z == r(z32)).float().mean().item()
-    e_dw = rel_err(dwd.cpu(), dw_ref)
-    e_s1 = rel_err(stats[0].cpu(), z32.double().sum(dim=(0, 2, 3)))
-    e_s2 = rel_err(stats[1].cpu(), (z32.double() ** 2).sum(dim=(0, 2, 3)))
-    report(f"{mode} storage kernels", case, f"z {ez / ulp:.2f} ulp ({100 * same:.2f} % identical), dx {edx / ulp:.2f} ulp, dW {e_dw:.1e}, "
-           f"sums {e_s1:.1e} / {e_s2:.1e}")
-    assert ez <= 1.01 * ulp and same > 0.98 and edx <= 1.01 * ulp and e_dw < 5e-6 and e_s1 < 1e-5 and e_s2 < 1e-5
+    cip, cop = pad8(Ci), pad8(Co)
+    got = run_conv(lib, to_nhwc(x, cip), w.cuda().contiguous(), b.cuda(), to_nhwc(dz, cop), Ci, Co, prec)
+    ref = {"z": nhwc(z32), "dx": nhwc(xr.grad), "dw": dw_ref, "sum": z32.double().sum(dim=(0, 2, 3)),
+           "sumsq": (z32.double() ** 2).sum(dim=(0, 2, 3))}
+    check_storage_rounded(got, ref, mode, (f"{mode} storage kernels", case))
 
 
 @pytest.mark.parametrize("case", [(2, 64, 64, 64, 64, 1e-6), (1, 96, 80, 30, 30, 1.0), (2, 32, 32, 120, 60, 3e-9), (1, 40, 40, 45, 30, 1e4)],
@@ -410,3 +371,105 @@ def test_two_mfma_weight_gradient_scaling_and_accuracy(case, monkeypatch):
     L.check(lib.mimo_op_conv3x3_wgrad(xd.data_ptr(), zero.data_ptr(), dwd.data_ptr(), dbd.data_ptr(), N, H, W, Ci, cip, Co, cop,
                                       L.PRECISIONS["split16"], st), "conv wgrad")
     assert float(dwd.abs().max()) == 0.0
+
+
+# ---- the convolutions at the batches the benchmark runs -------------------------------------------------------------------
+
+BENCH_LAYERS = benchmark_conv_layers()
+
+
+def _layers_of(config, n):
+    import bench
+    return set(config_conv_layers(bench.CONFIGS[config], n))
+
+
+def production_modes(layer):
+    """The precision modes test_conv3x3_at_benchmark_batches_vs_fp64 runs on one layer of benchmark_conv_layers()."""
+    cfg3_32, cfg3_4, cfg4_16 = _layers_of("cfg3", 32), _layers_of("cfg3", 4), _layers_of("cfg4", 16)
+    image = layer[3] <= 4
+    modes = ["split16"]
+    if layer in cfg3_32 or layer in cfg3_4:
+        modes.append("split16-np3")
+    if layer in cfg3_32:
+        modes.append("fp32")
+    if layer in cfg4_16:
+        modes.append("bf16")
+        if not image:
+            modes.append("bf16-mixed")
+    if layer in cfg3_32 and not image:
+        modes.append("16-mixed")
+    return modes
+
+
+@pytest.mark.parametrize("layer", BENCH_LAYERS, ids=lambda c: "x".join(map(str, c)))
+def test_conv3x3_at_benchmark_batches_vs_fp64(layer, monkeypatch):
+    """Forward, data gradient and weight gradient of every 3 x 3 convolution the benchmark runs (benchmark_conv_layers:
+    cfg3, cfg2 and cfg4 at their batches and their 2 / 4 / 8-GPU shards), through mimo_op_conv3x3_*, which take the
+    plan's per-geometry choices (wide or bf16x3 decomposition, K split, pair tail, weight-gradient split counts, the
+    plain-FMA image-layer weight gradient from 4 x (resident workgroups) tiles on), against conv3x3_reference_f64 on the
+    same device-generated operands.  Those choices depend on N: the small CONV_CASES never reach several of them.
+
+    Operands as in training: the image layer reads U[0, 1) pixels, every other layer post-ReLU activations (about half
+    zeros); init-scale weights; dz of the size a mean loss over N x S x H x W outputs leaves (1 / (2 N H W): the two-MFMA
+    weight gradient's power-of-two dz scaling at work), O(1) for 16-mixed (as a loss scaler leaves it).
+
+    Modes, and the layers they run on (production_modes):
+      split16 (the default, two-MFMA weight gradient): every layer, the bounds of conv_tolerances;
+      split16 under MIMO_WGRAD_NP=3 (the value_strict three-MFMA weight gradient): weight gradient of cfg3 at 32 and 4;
+      fp32 (the fallback when the fp16 range guard trips): cfg3 at 32;
+      bf16 (cfg4's arithmetic in bench.py): cfg4 at 16 — conv_tolerances("bf16") against the exact operands, and 2e-6
+        against the bf16-rounded operands (check_bf16_rounded);
+      bf16-mixed (cfg4's BASELINE precision): cfg4 at 16, 16-mixed (the reference's production precision): cfg3 at 32 —
+        check_storage_rounded against the rounded operands.  Not on the image layer: the plan keeps the packed image in
+        fp32 in these modes (plan.hip: the thin fp32 forward and an fp32-input weight gradient), while mimo_op_conv3x3_*
+        rounds x to 16 bits and runs the split kernels — a different decomposition from the one the plan runs.
+    The bounds are those of the small cases, except where the reduction is longer than the small cases' and the bound is
+    close to fp32 rounding itself — two of them, found by this test to fail as pure arithmetic (errors spread over every
+    image, row and channel block, growing as sqrt(K)): the bf16 rounded-operand bound 2e-6 (reached at K = 8640 forward,
+    K = 16384 ... 65536 weight gradient; the fp32 mode shows the same growth, 3.1e-6 at K = 8640, within its 2e-5) and
+    the 16-mixed forward's one-unit criterion near z = 0 (up to 1.95 units at |z| ~ 1e-3 for K >= 2160).  Both become
+    functions of the reduction length K: helpers.fp32_acc_bound (2^-24 * sqrt(K) of the tensor's scale, derivation and
+    observed numbers there) and check_storage_rounded's K floor.  Every mode's errors and the (image, row, column,
+    channel) / (cout, cin, ky, kx) of its worst element go through report()."""
+    L = _lib()
+    lib = L.load()
+    N, H, W, Ci, Co = layer
+    cip, cop = conv_cin_pad(Ci), pad8(Co)
+    modes = production_modes(layer)
+    g = torch.Generator(device="cuda").manual_seed(((N * 1009 + H) * 1013 + Ci) * 1019 + Co)
+    x = torch.zeros(N, H, W, cip, device="cuda")
+    x[..., :Ci] = torch.rand(N, H, W, Ci, device="cuda", generator=g) if Ci <= 4 else \
+        torch.randn(N, H, W, Ci, device="cuda", generator=g).clamp_min_(0.0)
+    w = torch.randn(Co, Ci, 3, 3, device="cuda", generator=g) / (3.0 * Ci ** 0.5)
+    b = (torch.rand(Co, device="cuda", generator=g) * 2.0 - 1.0) / (3.0 * Ci ** 0.5)
+    dz = torch.zeros(N, H, W, cop, device="cuda")
+    dz[..., :Co] = torch.randn(N, H, W, Co, device="cuda", generator=g) / (2.0 * N * H * W)
+    ref = conv3x3_reference_f64(x, w, b, dz)
+    acc_k = {"fwd": 9 * Ci, "dgrad": 9 * Co, "wgrad": N * H * W}  # reduction lengths (fp32_acc_bound)
+    rounded = {}  # storage type -> (x, w, dz) rounded to it and their reference (bf16 and bf16-mixed share one)
+    for mode in modes:
+        label = ("conv at benchmark batch", mode, layer)
+        if mode == "split16-np3":
+            with monkeypatch.context() as m:
+                m.setenv("MIMO_WGRAD_NP", "3")
+                got = run_conv(lib, x, w, b, dz, Ci, Co, L.PRECISIONS["split16"], fwd=False, dgrad=False)
+                check_conv_results(got, ref, "split16", label)
+            continue
+        dt = torch.float16 if mode == "16-mixed" else torch.bfloat16
+        if mode != "split16" and mode != "fp32" and dt not in rounded:
+            r = lambda t: t.to(dt).float()
+            ops = (r(x), r(w), r(dz * (2.0 * N * H * W)) if mode == "16-mixed" else r(dz))
+            rounded[dt] = ops + (conv3x3_reference_f64(ops[0], ops[1], b, ops[2]),)
+        if mode in ("split16", "fp32", "bf16"):
+            got = run_conv(lib, x, w, b, dz, Ci, Co, L.PRECISIONS[mode])  # (bf16: the kernels round x, w and dz themselves)
+            check_conv_results(got, ref, mode, label)
+            if mode == "bf16":
+                check_bf16_rounded(got, rounded[dt][3], label + ("rounded operands",), acc_k,
+                                   fp32_ref=ref if Ci <= 4 else None)
+        else:
+            xr, _, dzr, rref = rounded[dt]
+            got = run_conv(lib, xr, w, b, dzr, Ci, Co, L.PRECISIONS[mode])
+            check_storage_rounded(got, rref, mode, label, acc_k)
+        del got
+    del x, w, b, dz, ref, rounded
+    torch.cuda.empty_cache()
