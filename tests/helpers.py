@@ -380,3 +380,75 @@ def check_storage_rounded(got, ref, mode, label, acc_k=None):
     bad = {q: errs[q] for q, v in ok.items() if not v}
     assert not bad, (bad, {q: where.get(q) for q in bad})
     return errs, where
+
+
+# ---- the reference training step on any device, and the fp64-anchored gradient rule of the whole-network tests ----
+
+def oracle_state_to(ts, device, dtype):
+    """A copy of the oracle's TrainState `ts` with every floating tensor — parameters, BatchNorm buffers, Adam moments and
+    the loss buffer's ring — on `device` in `dtype` (num_batches_tracked keeps its integer type).  A `get_weights`
+    replaced on the instance (fixed subnetwork weights) is kept, its result moved the same way.  `ts` is not modified."""
+    import copy
+    mv = lambda t: (t.to(device, dtype) if t.is_floating_point() else t.to(device)).clone()
+    out = copy.copy(ts)
+    out.st = {k: mv(v) for k, v in ts.st.items()}
+    out.exp_avg = {k: mv(v) for k, v in ts.exp_avg.items()}
+    out.exp_avg_sq = {k: mv(v) for k, v in ts.exp_avg_sq.items()}
+    lb = copy.copy(ts.loss_buffer)
+    lb.buffer = mv(ts.loss_buffer.buffer)
+    if "get_weights" in vars(ts.loss_buffer):
+        lb.get_weights = lambda f=ts.loss_buffer.get_weights: f().to(device, dtype)
+    out.loss_buffer = lb
+    return out
+
+
+def reference_train_step(ts, image, label, mask, perms, device="cpu", dtype=torch.float64, **kw):
+    """O.train_step (keywords passed on) with every tensor on `device` in `dtype`: runs on oracle_state_to(ts, device,
+    dtype) and returns that state (stepped) and the step's results; `ts` itself is not modified.  MIOpen is switched off,
+    so on the GPU the reference convolutions are torch's own im2col GEMMs in `dtype`, not an algorithm MIOpen picks (and,
+    for float64, one that exists at all).  Pinned to O.train_step on the CPU by tests/test_reference_step_cpu.py."""
+    ts = oracle_state_to(ts, device, dtype)
+    cast = lambda t: None if t is None else t.to(device, dtype)
+    with torch.backends.cudnn.flags(enabled=False):
+        res = O.train_step(ts, cast(image), cast(label), cast(mask), perms.to(device), **kw)
+    return ts, res
+
+
+def to_cpu(obj):
+    """tensors (also inside dicts) moved to the host"""
+    if isinstance(obj, dict):
+        return {k: to_cpu(v) for k, v in obj.items()}
+    return obj.cpu() if isinstance(obj, torch.Tensor) else obj
+
+
+def check_grads_vs_fp64(grads, g32, g64, small_net=False):
+    """The gradient rule of the whole-network parity tests (test_network_gpu.py::_oracle_vs_hip): ReLU / max-pool
+    derivatives are discontinuous, so the gradients are anchored on the fp64 reference and judged against what fp32
+    arithmetic itself does on the same problem (the fp32 reference `g32` against `g64`).  Per tensor (the pre-BatchNorm
+    biases excluded: mathematically zero), the HIP gradient's relative L2 error must stay within floor + 5 x the larger of
+    the fp32 reference's error on that tensor and over all tensors; floor 1e-3 (5e-3 with `small_net`).  Asserts that and
+    returns the whole-gradient cosine and relative L2 error (the callers bound those), the worst tensor (name, error,
+    fp32-reference error), the fp32 reference's whole-gradient error and how often its arm decided.  All tensors on one
+    device."""
+    ks = [k for k in g64 if not is_prebn_bias(k)]
+    eo_all = (sum(float(((g32[k].double() - g64[k]) ** 2).sum()) for k in ks)
+              / sum(float((g64[k] ** 2).sum()) for k in ks)) ** 0.5
+    worst, dot, nh, nr, nd = ("", 0.0, 0.0), 0.0, 0.0, 0.0, 0.0
+    n_tensors = arm_all = need_all = 0
+    floor = 5e-3 if small_net else 1e-3
+    for k in ks:
+        g, r = grads[k].double(), g64[k]
+        eh = float((g - r).norm() / r.norm())
+        eo = float((g32[k].double() - r).norm() / r.norm())
+        if eh > worst[1]:
+            worst = (k, eh, eo)
+        assert eh <= floor + 5.0 * max(eo, eo_all), (k, eh, eo, eo_all)
+        n_tensors += 1
+        arm_all += eo_all > eo               # the whole-gradient arm is the larger of the two for this tensor
+        need_all += eh > floor + 5.0 * eo    # ... and the tensor would NOT have passed on its own fp32-reference error
+        dot += float((g * r).sum())
+        nh += float((g ** 2).sum())
+        nr += float((r ** 2).sum())
+        nd += float(((g - r) ** 2).sum())
+    return {"cos": dot / (nh * nr) ** 0.5, "rel_l2": (nd / nr) ** 0.5, "worst": worst, "eo_all": eo_all,
+            "arm_all": arm_all, "need_all": need_all, "n_tensors": n_tensors}

@@ -7,8 +7,8 @@ import pytest
 import torch
 
 from oracle import mimo_oracle as O
-from tests.helpers import (adam_flip_bound, adam_flip_statistic, cfg_from_meta, golden_grad_tol, load_npz, rel_err, report,
-                           state_from, wgrad_two_mfma)
+from tests.helpers import (adam_flip_bound, adam_flip_statistic, cfg_from_meta, check_grads_vs_fp64, golden_grad_tol, load_npz,
+                           reference_train_step, rel_err, report, state_from, to_cpu, wgrad_two_mfma)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -224,17 +224,21 @@ def test_mc_dropout_ensemble_golden():
     assert ens.num_subnetworks == S
 
 
-def _oracle_run(cfg, st, image, label, mask, perms, lb_w, loss, dtype):
-    cast = lambda t: None if t is None else t.to(dtype)
+def _oracle_run(cfg, st, image, label, mask, perms, lb_w, loss, dtype, device="cpu"):
+    """one step of the oracle on `device` in `dtype` (tests/helpers.py::reference_train_step); state and results on the host"""
     ts = O.TrainState(cfg=cfg, st={k: (v.clone().to(dtype) if v.is_floating_point() else v.clone()) for k, v in st.items()},
                       loss_kind=loss, loss_buffer=O.LossBuffer(cfg.num_subnetworks, 0.3, 10))
     ts.loss_buffer.get_weights = lambda: lb_w.to(dtype)
-    return ts, O.train_step(ts, cast(image), cast(label), cast(mask), perms, apply_optimizer=False)
+    ts, res = reference_train_step(ts, image, label, mask, perms, device=device, dtype=dtype, apply_optimizer=False)
+    if device != "cpu":
+        ts.st, res = to_cpu(ts.st), to_cpu(res)
+    return ts, res
 
 
 def _oracle_vs_hip(cfg, N, H, W, seed, loss="laplace_nll", with_mask=False, precision="split16", small_net=False,
-                   repetitions=1, irp=0.0):
-    """One training step (forward, loss, backward) of the HIP path against the CPU oracle.
+                   repetitions=1, irp=0.0, ref_device="cpu"):
+    """One training step (forward, loss, backward) of the HIP path against the oracle (run on `ref_device`: the CPU by
+    default, "cuda" for batches the CPU oracle does not finish in seconds).
 
     Outputs, losses and BatchNorm buffers: 1e-3 relative against the fp32 oracle.
 
@@ -264,8 +268,8 @@ def _oracle_vs_hip(cfg, N, H, W, seed, loss="laplace_nll", with_mask=False, prec
     model.loss_buffer.get_weights = lambda: lb_w  # fixed non-uniform weights on both sides
     out = model.training_step_with_perms(image.cuda(), label.cuda(), None if mask is None else mask.cuda(), perms.cuda())
     out["loss"].backward()
-    ts32, ref = _oracle_run(cfg, st, image, label, mask, perms, lb_w, loss, torch.float32)
-    _, ref64 = _oracle_run(cfg, st, image, label, mask, perms, lb_w, loss, torch.float64)
+    ts32, ref = _oracle_run(cfg, st, image, label, mask, perms, lb_w, loss, torch.float32, ref_device)
+    _, ref64 = _oracle_run(cfg, st, image, label, mask, perms, lb_w, loss, torch.float64, ref_device)
     half = cfg.out_channels // 2
     preds = out["preds"].view(N * repetitions, cfg.num_subnetworks, half, H, W).cpu()
     e_out = rel_err(preds, ref["out"][:, :, :half])
@@ -273,31 +277,12 @@ def _oracle_vs_hip(cfg, N, H, W, seed, loss="laplace_nll", with_mask=False, prec
     sd = model.state_dict()
     e_buf = max(rel_err(sd["model." + k].cpu(), v) for k, v in ts32.st.items() if "running" in k)
     grads = {k[len("model."):]: p.grad.detach().cpu().double() for k, p in model.named_parameters()}
-    worst, dot, nh, nr, nd = ("", 0.0, 0.0), 0.0, 0.0, 0.0, 0.0
-    n_tensors = arm_all = need_all = 0
     # The yardstick is what fp32 arithmetic itself does on this problem (fp32 oracle against the fp64 oracle): per tensor,
     # and over all tensors — training-mode BatchNorm over a small batch amplifies rounding into every gradient at once,
     # and WHICH tensor the fp32 oracle happens to get right depends on its thread count (reduction order)
-    ks = [k for k in ref64["grads"] if not is_prebn_bias(k)]
-    eo_all = (sum(float(((ref["grads"][k].double() - ref64["grads"][k]) ** 2).sum()) for k in ks)
-              / sum(float((ref64["grads"][k] ** 2).sum()) for k in ks)) ** 0.5
-    for k, g64 in ref64["grads"].items():
-        if is_prebn_bias(k):
-            continue  # mathematically zero; rounding noise on both sides
-        eh = float((grads[k] - g64).norm() / g64.norm())
-        eo = float((ref["grads"][k].double() - g64).norm() / g64.norm())
-        if eh > worst[1]:
-            worst = (k, eh, eo)
-        floor = 5e-3 if small_net else 1e-3
-        assert eh <= floor + 5.0 * max(eo, eo_all), (k, eh, eo, eo_all)
-        n_tensors += 1
-        arm_all += eo_all > eo               # the whole-gradient arm is the larger of the two for this tensor
-        need_all += eh > floor + 5.0 * eo    # ... and the tensor would NOT have passed on its own fp32-oracle error
-        dot += float((grads[k] * g64).sum())
-        nh += float((grads[k] ** 2).sum())
-        nr += float((g64 ** 2).sum())
-        nd += float(((grads[k] - g64) ** 2).sum())
-    cos, rel_l2 = dot / (nh * nr) ** 0.5, (nd / nr) ** 0.5
+    gc = check_grads_vs_fp64(grads, ref["grads"], ref64["grads"], small_net)
+    worst, eo_all, arm_all, need_all, n_tensors = gc["worst"], gc["eo_all"], gc["arm_all"], gc["need_all"], gc["n_tensors"]
+    cos, rel_l2 = gc["cos"], gc["rel_l2"]
     report(f"[{precision}] out {e_out:.2e} loss {e_loss:.2e} bn-buffers {e_buf:.2e}; grads vs fp64: cos {cos:.7f} rel-L2 {rel_l2:.2e}; "
           f"worst tensor {worst[0]} hip {worst[1]:.2e} (fp32 oracle {worst[2]:.2e}; fp32 oracle over all tensors {eo_all:.2e}); "
           f"bound arms: eo_all > eo on {arm_all} of {n_tensors} tensors, {need_all} needed it to pass")
@@ -343,6 +328,31 @@ def test_more_geometries_vs_oracle(case):
     e_out, worst = _oracle_vs_hip(O.NetConfig(Ci, Co, S, f), N=N, H=H, W=W, seed=sum(case[:7]), loss=loss,
                                   with_mask=with_mask, small_net=f < 16)
     report(f"{case}: out err {e_out:.2e}; worst grad {worst}")
+
+
+def test_oracle_on_the_device_vs_on_the_host():
+    """The references on the GPU (ref_device="cuda", as the benchmark-batch tests run them): the fp64 reference step there
+    agrees with the host's within 1e-9 of each tensor's scale (outputs, losses, BatchNorm buffers, every gradient), and
+    _oracle_vs_hip passes with it on the odd-size geometry of test_more_geometries_vs_oracle."""
+    cfg = O.NetConfig(3, 2, 2, 6)
+    g = torch.Generator().manual_seed(31)
+    ts = O.TrainState(cfg=cfg, st=O.init_state(cfg, 31), loss_buffer=O.LossBuffer(2, 0.3, 10))
+    image, label = torch.rand(2, 3, 50, 70, generator=g), torch.rand(2, 1, 50, 70, generator=g)
+    mask = (torch.rand(2, 1, 50, 70, generator=g) > 0.3).float()
+    perms = O.draw_perms(2, 2, generator=g)
+    th, rh = reference_train_step(ts, image, label, mask, perms, device="cpu", dtype=torch.float64, apply_optimizer=False)
+    td, rd = reference_train_step(ts, image, label, mask, perms, device="cuda", dtype=torch.float64, apply_optimizer=False)
+    assert rd["out"].is_cuda
+    rd, std = to_cpu(rd), to_cpu(td.st)
+    errs = {k: rel_err(rd[k], rh[k]) for k in ("out", "loss", "total")}
+    errs.update({k: rel_err(std[k], v) for k, v in th.st.items() if "running" in k})
+    errs.update({k: rel_err(rd["grads"][k], v) for k, v in rh["grads"].items() if not is_prebn_bias(k)})
+    worst = max(errs, key=errs.get)
+    report(f"fp64 reference on the device vs on the host: worst {worst} {errs[worst]:.1e}")
+    assert errs[worst] < 1e-9, (worst, errs[worst])
+    e_out, worst = _oracle_vs_hip(cfg, N=2, H=50, W=70, seed=3 + 2 + 2 + 6 + 2 + 50 + 70, with_mask=True, small_net=True,
+                                  ref_device="cuda")
+    report(f"references on the device: out err {e_out:.2e}; worst grad {worst}")
 
 
 def test_batch_repetitions_and_input_repetition_vs_oracle():
