@@ -55,14 +55,6 @@ __device__ __forceinline__ f32x4_ mfma16(Elem<true>::V8 a, Elem<true>::V8 b, f32
 }
 constexpr float kF16WeightScale = 256.f;  // 2^8, exact
 
-#ifdef MIMO_CONV_STAMPS
-// timing-only instrumentation (-DMIMO_CONV_STAMPS): per kernel role, shader-clock ticks summed over one wave of every
-// workgroup — [0] forward consumers: barrier wait, [1] their total, [2] forward producers: wait (DMA / barrier), [3]
-// their total, [4..7] the same for the data gradient
-__device__ unsigned long long g_conv_stamps[8];
-#define STAMP_NOW() __builtin_amdgcn_s_memtime()
-#endif
-
 // Kernel modes (template parameter MODE of the convolution kernels and launchers):
 //   0  split16 data gradient : bf16 (hi, lo) pairs, input pre-split (dz),       3 MFMAs per product
 //   1  split16 forward       : fp16 (hi, lo) pairs, fp32 input split on the way, 3 MFMAs per product
@@ -373,11 +365,11 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(ConvLaunch a, int T
 // rewritten in an exclusive barrier-to-barrier section.  Here waves 0-3 ("consumers") only issue
 // ds_read_b128 + MFMA and waves 4-7 ("producers", one next to a consumer on every SIMD) do all the
 // staging: global loads two stages ahead in registers, fp32 -> hi/lo split (forward) or plain copy
-// (data gradient, pre-split dz), LDS writes into the OTHER input-tile / weight buffer.  The
+// (data gradient, pre-split dz), LDS writes into the OTHER input-tile buffer, weights by LDS-DMA.  The
 // workgroup is persistent over output tiles, so the first chunk of the next tile is staged under the
 // last chunk of the current one and the output epilogue of the consumers overlaps the producers.
 //   tile = 256 output pixels (4 consumers x 4 fragments of 16 pixels) x NF*16 output channels
-//   LDS  = 2 input tiles (360 x 144 B) + 2 weight tap rows (3 x NB x 144 B) <= 159 KB
+//   LDS  = 2 input tiles (360 x 144 B) + 2 weight tap rows (3 x NB x 128 B) <= 153 KB
 //   one workgroup barrier per phase (tap row of a 32-channel chunk)
 // BatchNorm partial sums: accumulated in registers over the workgroup's tiles, the four consumer waves combined
 // through LDS once at the end: one row per workgroup for the column reduction that follows.
@@ -403,7 +395,7 @@ constexpr int kWsMaxMF = 4;
 // (lane base) + (scalar of the phase) + (immediate of the step), and phases keep their three steps, so the
 // alternation of the two B register sets is the same compile-time pattern as without pairing.
 //
-// WDMA: the weights of a phase go global -> LDS by LDS-DMA (global_load_lds_dwordx4: no registers, no ds_write) into
+// Weights: the weights of a phase go global -> LDS by LDS-DMA (global_load_lds_dwordx4: no registers, no ds_write) into
 // the buffer the consumers released at the last barrier, one phase ahead; the producers wait for them with a counted
 // vmcnt that leaves their own (younger) input-tile loads in flight, then pass a raw s_barrier.  A DMA instruction
 // writes 64 x 16 contiguous bytes, so the weight rows are unpadded 128-byte rows with the slot index XORed by
@@ -414,14 +406,14 @@ constexpr int kWsMaxMF = 4;
 // arithmetic) in front of the fp16 split, so the activated tensor between the two convolutions of a DoubleConv
 // (components.py:24-25) is never written.  A thread's units all hold one channel quad of a chunk; its constants are loaded
 // one stage ahead, in front of that phase's weight DMA and input loads (the counted vmcnt waits stay valid).
-template <int NF, int MODE, int MF_, bool PAIR = false, bool WDMA = true, bool FIN = false>
+template <int NF, int MODE, int MF_, bool PAIR = false, bool FIN = false>
 __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws_kernel(ConvLaunch a, int TR, int TC,
                                                                                           int tilesY, int tilesX,
                                                                                           int numTiles, int xcd_order,
                                                                                           int gx, int coTiles) {
   MIMO_CONV_MODE_CONSTANTS
   static_assert(!PAIR || (NP == 3 && !IN16), "tap pairing: split16 modes");
-  static_assert(!FIN || (MODE == 1 && WDMA), "fused input BatchNorm + ReLU: the split16 forward, weights by DMA");
+  static_assert(!FIN || MODE == 1, "fused input BatchNorm + ReLU: the split16 forward");
   typedef typename Elem<F16>::T ET;
   typedef typename Elem<F16>::V8 bf16x8;
   typedef typename Elem<F16>::V4 bf16x4;
@@ -441,8 +433,7 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
   // ds_read_b128 of 16 consecutive rows; conflict-free XOR-swizzled 128-byte input rows measured the same kernel
   // times in rounds 1 and 2 and were removed in round 3)
   constexpr int PITCH = kPitchB;
-  constexpr bool WSWZ = WDMA;                      // weight rows: swizzled 128-byte rows (the DMA writes 1 KB runs)
-  constexpr int WPITCH = WSWZ ? 128 : kPitchB;
+  constexpr int WPITCH = 128;  // weight rows: swizzled 128-byte rows (the DMA writes 1 KB runs)
   constexpr int XBYTES = kWsMaxPix * PITCH, WROWB = 3 * NB * WPITCH;
   __shared__ __attribute__((aligned(128))) unsigned char xs[2 * XBYTES];
   __shared__ __attribute__((aligned(128))) unsigned char ws[2 * WROWB];
@@ -457,14 +448,6 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
   // coTiles workgroups that read the SAME input tiles sit on one XCD and fetch them from HBM once (measured
   // before: 11 x re-read of the input on the 480-channel layers, one per channel tile), and an XCD owns
   // gx / 8 CONSECUTIVE columns — vertically adjacent tile rows, whose halo rows they share.
-#ifdef MIMO_CONV_ABLATE
-  // timing-only builds (-DMIMO_CONV_ABLATE=bits, results are wrong; WDMA instances only): 1 = producers skip the
-  // input-tile loads, 2 = the input-tile LDS stores, 4 = the weight staging; 8 = consumers skip the MFMAs, 16 = the
-  // fragment reads, 32 = the per-tile epilogue (stores, bias / statistics arithmetic; the accumulators stay live)
-  constexpr int abl = MIMO_CONV_ABLATE;
-#else
-  constexpr int abl = 0;
-#endif
   // K split (ConvLaunch::ksplit > 1; round 6): the workgroups of a (pixel-tile column, channel tile) pair come ksplit-fold, each
   // walks nck consecutive 32-channel chunks from ck0 and stores its partial sums into slab ks of a.y; ksplit == 1: ck0 = 0,
   // nck = nchunks, one slab — the arithmetic below is then the old one.  Virtual order: (column, split, channel tile), so
@@ -483,8 +466,7 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
     // =============================== producers ===============================
     const int ptid = tid - 256;
     f32x4 xreg[XU];
-    u32x4 wreg[WDMA ? 1 : 3][WDMA ? 1 : WU];
-    // WDMA: 16-byte unit (u & 7) ^ (row & 7) of weight row u >> 3 of the phase lands at LDS unit u = ptid + 256 k
+    // 16-byte unit (u & 7) ^ (row & 7) of weight row u >> 3 of the phase lands at LDS unit u = ptid + 256 k
     const unsigned ws_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ws;  // LDS byte address
     int wsrc[WU];
 #pragma unroll
@@ -599,29 +581,7 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
       }                                                                                              \
     }                                                                                                \
   }
-    // weights of global phase PH = 3 * stage + r: chunk = stage % nchunks, tap row r
-#define WS_LOAD_W(SLOT, PH)                                                                          \
-  {                                                                                                  \
-    const int phw_ = (PH);                                                                           \
-    const int ck_ = ck0 + (phw_ / 3) % nck, r_ = phw_ % 3;                                           \
-    _Pragma("unroll") for (int k_ = 0; k_ < WU; ++k_) {                                              \
-      const int u_ = min(ptid + k_ * 256, WUNITS - 1);                                               \
-      const int t_ = u_ / (NB * 8);                                                                  \
-      const int rem_ = u_ - t_ * (NB * 8);                                                           \
-      wreg[SLOT][k_] = wpk[(((size_t)ck_ * 9 + (r_ * 3 + t_)) * a.cout_pad + co0 + (rem_ >> 3)) * 8 + (rem_ & 7)]; \
-    }                                                                                                \
-  }
-#define WS_STORE_W(SLOT, BUF)                                                                        \
-  _Pragma("unroll") for (int k_ = 0; k_ < WU; ++k_) {                                                \
-    const int u_ = ptid + k_ * 256;                                                                  \
-    if (u_ < WUNITS) {                                                                               \
-      const int t_ = u_ / (NB * 8);                                                                  \
-      const int rem_ = u_ - t_ * (NB * 8);                                                           \
-      const int wrow_ = t_ * NB + (rem_ >> 3);                                                       \
-      *reinterpret_cast<u32x4*>(ws + (BUF) * WROWB + wrow_ * WPITCH + (((rem_ & 7) ^ (WSWZ ? (wrow_ & 7) : 0)) << 4)) = wreg[SLOT][k_]; \
-    }                                                                                                \
-  }
-    // WDMA: weights of phase PH straight into weight buffer BUF (wave-uniform LDS base + lane * 16)
+    // weights of phase PH (= 3 * stage + tap row) straight into weight buffer BUF (wave-uniform LDS base + lane * 16)
 #define WS_DMA_W(BUF, PH)                                                                            \
   {                                                                                                  \
     const int phw_ = (PH);                                                                           \
@@ -642,41 +602,17 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
     }                                                                                                \
   }
     // all vector-memory operations but the N youngest (this phase's input loads) are done: the DMA'd weights are in LDS
-#ifdef MIMO_CONV_STAMPS
-    unsigned long long sp_wait = 0;
-    const unsigned long long sp_begin = STAMP_NOW();
-#define WS_DMA_WAIT(N)                                                                               \
-  {                                                                                                  \
-    const unsigned long long s0_ = STAMP_NOW();                                                      \
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");    \
-    sp_wait += STAMP_NOW() - s0_;                                                                    \
-  }
-#else
 #define WS_DMA_WAIT(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-#endif
     const int nphases = 3 * nstages;
     WS_LOAD_SS(in_sc, in_sh, 0)
     WS_LOAD_X(0, XU, 0)  // nstages >= 1: the grid never exceeds the tile count
-    if (WDMA) {
-      WS_DMA_W(0, 0)
-    } else {
-      WS_LOAD_W(0, 0)
-      WS_LOAD_W(1, 1)
-      WS_LOAD_W(2, 2)
-    }
+    WS_DMA_W(0, 0)
     WS_STORE_X(0, XU, 0)
-    if (!WDMA) {
-      WS_STORE_W(0, 0)
-    }
     WS_LOAD_SS(in_sc_n, in_sh_n, min(1, nstages - 1))
     WS_LOAD_X(0, XU, min(1, nstages - 1))
-    if (WDMA) {
-      WS_DMA_WAIT(XU)
-    } else {
-      __syncthreads();  // phase 0 is staged
-    }
-    // during phase (j, r): store W(phase + 1) and part r of input stage j + 1 into the buffers the
-    // consumers released at the last barrier; then refill those registers two / three phases ahead
+    WS_DMA_WAIT(XU)
+    // during phase (j, r): store part r of input stage j + 1 and DMA W(phase + 1) into the buffers the consumers
+    // released at the last barrier; then refill the input registers two stages ahead
     for (int j = 0; j < nstages; ++j) {
       const int xb = (j + 1) & 1;
       if (FIN) { /* the constants of stage j + 1: loaded one stage ago, older than every load still in flight */
@@ -689,29 +625,13 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
        buffers nobody reads any more -- straight-line code lets the compiler keep exact vmcnt counts \
        (a conditional load forces a full drain at the join and collapses the prefetch depth) */      \
     const int ph_ = 3 * j + (R);                                                                     \
-    if (WDMA) {                                                                                      \
-      if ((R) == 0) {                                                                                \
-        WS_LOAD_SS(in_sc_n, in_sh_n, min(j + 2, nstages - 1)) /* in front of this phase's DMA and input loads */ \
-      }                                                                                              \
-      if (!(abl & 2)) {                                                                              \
-        WS_STORE_X((R) * XP, ((R) + 1) * XP, xb)                                                     \
-      }                                                                                              \
-      if (!(abl & 4)) {                                                                              \
-        WS_DMA_W((ph_ + 1) & 1, min(ph_ + 1, nphases - 1))                                           \
-      }                                                                                              \
-      if (!(abl & 1)) {                                                                              \
-        WS_LOAD_X((R) * XP, ((R) + 1) * XP, min(j + 2, nstages - 1))                                 \
-        WS_DMA_WAIT(XP)                                                                              \
-      } else {                                                                                       \
-        WS_DMA_WAIT(0)                                                                               \
-      }                                                                                              \
-    } else {                                                                                         \
-      WS_STORE_W(((R) + 1) % 3, (ph_ + 1) & 1)                                                       \
-      WS_LOAD_W((R), min(ph_ + 3, nphases - 1))                                                      \
-      WS_STORE_X((R) * XP, ((R) + 1) * XP, xb)                                                       \
-      WS_LOAD_X((R) * XP, ((R) + 1) * XP, min(j + 2, nstages - 1))                                   \
-      __syncthreads();                                                                               \
+    if ((R) == 0) {                                                                                  \
+      WS_LOAD_SS(in_sc_n, in_sh_n, min(j + 2, nstages - 1)) /* in front of this phase's DMA and input loads */ \
     }                                                                                                \
+    WS_STORE_X((R) * XP, ((R) + 1) * XP, xb)                                                         \
+    WS_DMA_W((ph_ + 1) & 1, min(ph_ + 1, nphases - 1))                                               \
+    WS_LOAD_X((R) * XP, ((R) + 1) * XP, min(j + 2, nstages - 1))                                     \
+    WS_DMA_WAIT(XP)                                                                                  \
   }
       WS_PHASE(0)
       WS_PHASE(1)
@@ -721,33 +641,13 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
 #undef WS_LOAD_SS
 #undef WS_LOAD_X
 #undef WS_STORE_X
-#undef WS_LOAD_W
-#undef WS_STORE_W
 #undef WS_DMA_W
 #undef WS_DMA_WAIT
-#ifdef MIMO_CONV_STAMPS
-    if (ptid == 0) {
-      atomicAdd(&g_conv_stamps[(FWD ? 0 : 4) + 2], sp_wait);
-      atomicAdd(&g_conv_stamps[(FWD ? 0 : 4) + 3], STAMP_NOW() - sp_begin);
-    }
-#endif
     if (FWD && a.stats) __syncthreads();  // the consumers combine their BatchNorm sums through LDS (see the end)
     return;
   }
 
   // =============================== consumers ===============================
-#ifdef MIMO_CONV_STAMPS
-  unsigned long long st_wait = 0;
-  const unsigned long long st_begin = STAMP_NOW();
-#define STAMP_BAR_C                                  \
-  {                                                  \
-    const unsigned long long s0_ = STAMP_NOW();      \
-    __syncthreads();                                 \
-    st_wait += STAMP_NOW() - s0_;                    \
-  }
-#else
-#define STAMP_BAR_C __syncthreads();
-#endif
   // Software pipeline over taps: the 2*(MF+NF) fragment reads of tap t+1 are issued before the 3*MF*NF
   // MFMAs of tap t (two register sets; sched_group_barrier pins the order — left alone, the compiler
   // reads every fragment right before its first use and the lone MFMA wave of the SIMD eats the LDS
@@ -767,8 +667,8 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
   // phases of a paired chunk (see the kernel comment); second phase: K groups 2-3 meet zero weights and re-read slots
   // 0-1 of their own row (any finite data)
   const int pair_d = g >= 2 ? TCP * PITCH - 32 : 0, pair_d2 = g >= 2 ? -32 : 0;
-  const int wbase = WSWZ ? lr * WPITCH + ((g ^ (lr & 7)) << 4) : lr * WPITCH + g * 16;
-  const int wlo = WSWZ ? ((wbase ^ 64) - wbase) : 64;
+  const int wbase = lr * WPITCH + ((g ^ (lr & 7)) << 4);
+  const int wlo = (wbase ^ 64) - wbase;
   // Accumulators are kept TRANSPOSED (MFMA called with the weight fragment as A and the pixel fragment as B):
   // lane (lr, g) of fragment (m, nf) holds pixel lr of the fragment and output channels nf*16 + g*4 .. +3, so the
   // epilogue issues one 16-byte store per fragment and one pixel-address computation per m — the
@@ -806,30 +706,26 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
   // The order is pinned with sched_group_barriers for the data gradient only: measured 7.9 -> 7.3 ms per
   // step there, but 6.9 -> 7.4 ms for the forward, whose producers carry the fp32 -> fp16 split and share
   // the SIMD's vector issue with the MFMAs (a v_mfma_16x16x32 holds it for 8 of its 16 cycles).
-#ifdef MIMO_CONV_PIN_FWD
-  constexpr bool PINNED = true;  // A/B build: the forward's consumers pinned as well (round 2 measured it slower; round 4 re-checked)
-#else
   constexpr bool PINNED = !CVT;
-#endif
   constexpr int RA = NP == 3 ? 2 : 1, RB = NF * RA;  // LDS reads per A fragment / per tap's B fragments
   // register sets: A fragments alternate per 16-pixel fragment m, B fragments per tap
   bf16x8 ah[2], al[2], bh[2][NF], bl[2][NF];
 
 #define C_READ_B(BS, KW)                                                                             \
-  if (!(abl & 16)) _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                                \
+  _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                               \
     bh[BS][nf] = *reinterpret_cast<const bf16x8*>(wb_ + ((KW) * NB + nf * 16) * WPITCH);             \
     if (NP == 3) bl[BS][nf] = *reinterpret_cast<const bf16x8*>(wb_ + ((KW) * NB + nf * 16) * WPITCH + wlo); \
   }
   // ro_: tile row of the phase's taps (r_; phases of a paired chunk: 0 and 2); pd_: the per-lane constant of a paired
   // chunk's phases (first: K groups 2-3 read one tile row down, slots 0-1), else 0
 #define C_READ_A(AS, KW, M)                                                                     \
-  if (!(abl & 16)) {                                                                                                  \
+  {                                                                                                  \
     const unsigned char* p_ = xb_ + pbase[M] + pd_ + (ro_ * TCP + (KW)) * PITCH;                     \
     ah[AS] = *reinterpret_cast<const bf16x8*>(p_);                                                   \
     if (NP == 3) al[AS] = *reinterpret_cast<const bf16x8*>(p_ + 64);                                 \
   }
 #define C_MFMA(AS, BS, M)                                                                            \
-  if (!(abl & 8)) _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                                \
+  _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                               \
     if (NP == 3) {                                                                                   \
       acc[M][nf] = mfma16(bh[BS][nf], al[AS], acc[M][nf]);                                           \
       acc[M][nf] = mfma16(bl[BS][nf], ah[AS], acc[M][nf]);                                           \
@@ -875,13 +771,7 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
     const int n_ = t_ / tilesY;                                                                      \
     const int y0_ = ty_ * TR, x0_ = tx_ * TC;                                                        \
     OT* yimg = reinterpret_cast<OT*>(a.y) + ((size_t)ks * a.N + n_) * a.Ho * a.Wo * a.ldy + co0 + g * 4; \
-    if (abl & 32) { /* timing only: keep the accumulators alive, no stores / arithmetic per element */ \
-      f32x4 k_ = acc[0][0];                                                                          \
-      _Pragma("unroll") for (int m = 0; m < MF; ++m)                                                 \
-        _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) k_ = k_ + acc[m][nf];                      \
-      if (k_[0] + k_[1] + k_[2] + k_[3] == 12345.678f) yimg[0] = (OT)k_[0];                          \
-    }                                                                                                \
-    if (!(abl & 32)) _Pragma("unroll") for (int m = 0; m < MF; ++m) {                                \
+    _Pragma("unroll") for (int m = 0; m < MF; ++m) {                                                 \
       const int oy = y0_ + (prc[m] >> 16), ox = x0_ + (prc[m] & 0xffff);                             \
       if (oy < a.Ho && ox < a.Wo) {                                                                  \
         OT* yp = yimg + ((size_t)oy * a.Wo + ox) * a.ldy;                                            \
@@ -934,7 +824,7 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
     const bool pc_ = PAIR && (j_ + 1) % nchunks == 0; /* phase of a paired chunk (r_ = 0, 1) */       \
     const int ro_ = pc_ ? 2 * r_ : r_;                                                               \
     const int pd_ = pc_ ? (r_ == 0 ? pair_d : pair_d2) : 0;                                          \
-    STAMP_BAR_C /* this phase is staged; the buffers of the previous one are released */             \
+    __syncthreads(); /* this phase is staged; the buffers of the previous one are released */        \
     C_READ_B((P) ^ 1, 0)                                                                             \
     C_READ_A(0, 0, 0)                                                                                \
     if (!(FIRST)) {                                                                                  \
@@ -973,12 +863,6 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
     C_MFMA(1, 0, MF - 1)
   }
   C_EPILOGUE(ti)
-#ifdef MIMO_CONV_STAMPS
-  if (tid == 0) {
-    atomicAdd(&g_conv_stamps[(FWD ? 0 : 4) + 0], st_wait);
-    atomicAdd(&g_conv_stamps[(FWD ? 0 : 4) + 1], STAMP_NOW() - st_begin);
-  }
-#endif
   __syncthreads();  // matches the producers' last barrier: their (dead) LDS stores are done
   if (FWD && a.stats) {
     // one partial-statistics row per workgroup: the four consumer waves add their sums through LDS (4 x fewer rows
@@ -1026,8 +910,7 @@ int conv3x3_ws_stat_rows(int, int, int) { return 512 * 4; }  // <= 512 persisten
 // Tap pairing of a <= 16-channel last chunk (see conv3x3_ws_kernel): decided per layer from what the dispatch below
 // will launch — the packer lays the chunk's weights out for it, the launch selects the PAIR instance (ConvLaunch::pair).
 int conv3x3_pair_tail(int mode, int cin_p, int Ho, int Wo) {
-  static const bool on = !(getenv("MIMO_CONV_PAIR_TAIL") && atoi(getenv("MIMO_CONV_PAIR_TAIL")) == 0);
-  if (!on || mode < 0 || mode > 1 || !conv_ws_enabled() || Ho * Wo < 256) return 0;
+  if (mode < 0 || mode > 1 || !conv_ws_enabled() || Ho * Wo < 256) return 0;
   const int tail = cin_p - 32 * (ceil_div(cin_p, 32) - 1);
   return tail <= 16 ? 1 : 0;
 }
@@ -1057,20 +940,17 @@ static int launch_ws(const ConvLaunch& a, int* rows, hipStream_t stream) {
   gx = ceil_div(numTiles, per);
   if (rows) *rows = gx;  // one partial-statistics row per workgroup
   dim3 grid(gx * coTiles * ksplit);
-  static const int xcd_ = !(getenv("MIMO_CONV_XCD_ORDER") && atoi(getenv("MIMO_CONV_XCD_ORDER")) == 0);
-  // MIMO_CONV_WDMA=0: weights staged through registers (ds_write) as before
-  static const bool wdma = !(getenv("MIMO_CONV_WDMA") && atoi(getenv("MIMO_CONV_WDMA")) == 0);
-  const int xcd = xcd_;
+  const int xcd = 1;  // XCD-aware workgroup order (xcd_virtual_index)
   if (a.in_scale) {
     if constexpr (MODE == 1) {
-      if (!wdma || a.ep_scale || !a.in_shift || (a.pair && a.pair != conv3x3_pair_tail(MODE, a.cin_p, a.Ho, a.Wo))) {
-        set_error("conv3x3 split: the input BatchNorm + ReLU can be fused into the split16 training forward (weights by DMA) only");
+      if (a.ep_scale || !a.in_shift || (a.pair && a.pair != conv3x3_pair_tail(MODE, a.cin_p, a.Ho, a.Wo))) {
+        set_error("conv3x3 split: the input BatchNorm + ReLU can be fused into the split16 training forward only");
         return MIMO_ERR_INVALID;
       }
       if (a.pair)
-        hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, true, true, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
+        hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, true, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
       else
-        hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, false, true, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
+        hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, false, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
       MIMO_KERNEL_CHECK();
       return MIMO_OK;
     } else {
@@ -1089,10 +969,8 @@ static int launch_ws(const ConvLaunch& a, int* rows, hipStream_t stream) {
       set_error("conv3x3 split: tap pairing exists for the split16 modes only");
       return MIMO_ERR_INVALID;
     }
-  } else if (wdma)
+  } else
     hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
-  else
-    hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, false, false>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
@@ -1115,8 +993,7 @@ static bool use_big_tile(int Ho, int Wo) { return Ho * Wo >= 1024; }
 // 1 when the launch runs on a kernel whose loaders can apply ConvLaunch::in_scale / in_shift (the wide kernel and the
 // 256-pixel wave-specialised kernel, split16 forward)
 int conv3x3_split_fuses_input(int mode, int wide, int Ho, int Wo) {
-  static const bool wdma = !(getenv("MIMO_CONV_WDMA") && atoi(getenv("MIMO_CONV_WDMA")) == 0);
-  return mode == 1 && (wide != 0 || (conv_ws_enabled() && wdma && Ho * Wo >= 256)) ? 1 : 0;
+  return mode == 1 && (wide != 0 || (conv_ws_enabled() && Ho * Wo >= 256)) ? 1 : 0;
 }
 
 template <int MODE>
@@ -1133,8 +1010,7 @@ static int conv3x3_split_dispatch(const ConvLaunch& a, int* rows, hipStream_t st
     // (pixel tile, channel tile) pairs than CUs (the 16x16 .. 64x64 layers at a few images per GPU — the per-GPU
     // batch of a strong-scaling run) finishes sooner with narrow channel tiles on many CUs than with wide ones on a
     // few: time ~ (tiles per workgroup) x (per-phase fixed cost + NF x MFMA time), fixed cost ~ one NF unit.
-    static const bool adapt = !(getenv("MIMO_CONV_ADAPTIVE_NF") && atoi(getenv("MIMO_CONV_ADAPTIVE_NF")) == 0);
-    if (adapt && a.ksplit <= 1) {  // (a K split keeps the widest channel tile: conv3x3_ksplit priced it that way)
+    if (a.ksplit <= 1) {  // (a K split keeps the widest channel tile: conv3x3_ksplit priced it that way)
       int TR, TC;
       pick_tile_n(a.Ho, a.Wo, WsTile<4>::NPIX, WsTile<4>::MAXPIX, &TR, &TC);
       const int numTiles = a.N * ceil_div(a.Ho, TR) * ceil_div(a.Wo, TC);
@@ -1146,14 +1022,10 @@ static int conv3x3_split_dispatch(const ConvLaunch& a, int* rows, hipStream_t st
         if (best < 0 || cost < best) best = cost, nf = c;
       }
     }
-  }
-  // NF <= 2: little MFMA work per tile -> 256-pixel tiles so that two workgroups share a CU and
-  // one's loads / stores overlap the other's MFMAs
-  if (conv_ws_enabled() && a.Ho * a.Wo >= 256) {
-    // 128-pixel tiles / two workgroups per CU: forward only (measured per layer on one box: forward 30->30 at
-    // 256x256 169 -> 147 us, 45->30 282 -> 253 us; the data gradient of the same shapes 132 -> 145 us)
-    static const bool mf2_on = !(getenv("MIMO_CONV_WS_MF2") && atoi(getenv("MIMO_CONV_WS_MF2")) == 0);
-    const bool mf2 = mf2_on && (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 6);
+    // NF <= 2: little MFMA work per tile -> 128-pixel tiles so that two workgroups share a CU and one's loads / stores
+    // overlap the other's MFMAs.  Forward only (measured per layer on one box: forward 30->30 at 256x256 169 -> 147 us,
+    // 45->30 282 -> 253 us; the data gradient of the same shapes 132 -> 145 us)
+    const bool mf2 = (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 6);
     switch (nf) {
       case 4: return launch_ws<4, MODE, 4>(a, rows, stream);
       case 3: return launch_ws<3, MODE, 4>(a, rows, stream);
@@ -1189,8 +1061,7 @@ static int conv3x3_split_dispatch(const ConvLaunch& a, int* rows, hipStream_t st
 constexpr int kKsplitReduceUnits = 14;
 int conv3x3_ksplit(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo) {
   static const int force = [] { const char* e = getenv("MIMO_CONV_KSPLIT"); return e ? atoi(e) : -1; }();
-  static const bool wdma = !(getenv("MIMO_CONV_WDMA") && atoi(getenv("MIMO_CONV_WDMA")) == 0);
-  if (force == 0 || (mode != 0 && mode != 1) || !conv_ws_enabled() || !wdma || Ho * Wo < 256 || cin_p % 32 != 0 ||
+  if (force == 0 || (mode != 0 && mode != 1) || !conv_ws_enabled() || Ho * Wo < 256 || cin_p % 32 != 0 ||
       cout_pad % 16 != 0)
     return 1;
   const int nchunks = cin_p / 32;
@@ -1490,16 +1361,6 @@ int pack_jobs_launch(const PackJob* jobs_dev, int njobs, int max_total, const fl
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
-
-#ifdef MIMO_CONV_STAMPS
-}  // namespace mimo
-extern "C" int mimo_debug_conv_stamps(unsigned long long* out) {  // reads and clears the counters
-  unsigned long long z[8] = {0};
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mimo::g_conv_stamps), sizeof(z)) != hipSuccess) return -1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(mimo::g_conv_stamps), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-namespace mimo {
-#endif
 
 int pack_weights_bf16x3_launch(const float* w, void* dst, int f16, int cout, int cin, int rows_pad, int cols,
                                const int* row_map, const int* col_map, int transposed, hipStream_t stream, int pair) {

@@ -38,11 +38,6 @@
 #include "common.h"
 #include "tile_sched.h"
 
-#ifndef MIMO_WIDE_DEFER
-#define MIMO_WIDE_DEFER 1  // 0: the per-tile epilogue runs between the tiles as in rounds 3-4 (A/B builds)
-#endif
-#define WD_DEFER_ENABLED (MIMO_WIDE_DEFER != 0)
-
 namespace mimo {
 
 namespace {
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
   constexpr int EPIB = FWD ? 3 * NB * 4 : 0;  // per-channel epilogue constants: bias, inference scale, shift
   // deferred epilogue (see the consumers): the lane-private BatchNorm partial sums live in LDS (16 floats per consumer
   // lane), not in 16 registers next to the 64 saved accumulators
-  constexpr bool DEFER = NF == 1 && MODE == 0 && !EPI && WD_DEFER_ENABLED;  // (the forward: measured slower, see DEFER below)
+  constexpr bool DEFER = NF == 1 && MODE == 0 && !EPI;  // (the forward: measured slower, see DEFER below)
   constexpr int SUMB = (DEFER && FWD) ? 4 * 2 * 256 * 8 : 0;
   static_assert(2 * kXBytes + NWB * WPHB + EPIB + SUMB <= 160 * 1024, "LDS budget");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * kXBytes + NWB * WPHB + EPIB + SUMB];
@@ -126,15 +121,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
   unsigned char* const ws = lds + 2 * kXBytes;
   float* const epi = reinterpret_cast<float*>(lds + 2 * kXBytes + NWB * WPHB);
 
-#ifdef MIMO_WIDE_ABLATE
-  // timing-only builds (-DMIMO_WIDE_ABLATE=bits, results are wrong): 1 = producers skip the input-tile loads, 2 = the
-  // input-tile LDS stores, 4 = the weight DMA; 8 = consumers skip the MFMAs, 16 = the fragment reads, 32 = the per-tile
-  // epilogue (the accumulators stay live); 64 = every input tile addressed as an interior one, 128 = ... and read
-  // from the first tile's addresses (cache-hot)
-  constexpr int abl = MIMO_WIDE_ABLATE;
-#else
-  constexpr int abl = 0;
-#endif
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int TCP = TC + 2, TRP = TR + 2;
@@ -249,9 +235,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
     // input units K0..K1 of the load stage -> registers.  Masked-out units are LOADED from the zero page (common.h),
     // never selected after the load.  A short last chunk takes the path with per-unit channel tests.
 #define WD_LOAD_X(K0, K1)                                                                            \
-  if (abl & 1) {                                                                                     \
-    _Pragma("unroll") for (int k_ = (K0); k_ < (K1); ++k_) xreg[k_] = f32x4{1.f, 2.f, 3.f, 4.f};     \
-  } else {                                                                                           \
+  {                                                                                                  \
     if (l_new) {                                                                                     \
       WD_OFFS(K0, K1)                                                                                \
     }                                                                                                \
@@ -297,9 +281,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
     }                                                                                                \
   }
 #define WD_STORE_X(K0, K1, BUF)                                                                      \
-  if (abl & 2) {                                                                                     \
-    _Pragma("unroll") for (int k_ = (K0); k_ < (K1); ++k_) asm volatile("" ::"v"(xreg[k_]));         \
-  } else _Pragma("unroll") for (int k_ = (K0); k_ < (K1); ++k_) {                                    \
+  _Pragma("unroll") for (int k_ = (K0); k_ < (K1); ++k_) {                                           \
     const int p_ = (ptid + k_ * 256) >> 2;                                                           \
     /* UNCONDITIONAL: rows [npix_lds, 640) are slack nobody reads.  A store skipped by a branch leaves its load    \
        un-waited on that path, and hipcc then drains the whole queue (vmcnt(0)) before it reuses the register —   \
@@ -339,13 +321,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
     const int pht_n = PARTS * nchunks;
 #define WD_DMA_W(BUF)                                                                                \
   {                                                                                                  \
-    if (!(abl & 4)) {                                                                                \
-      _Pragma("unroll") for (int k_ = 0; k_ < WU; ++k_) {                                            \
-        const unsigned dst_ = wdst0 + (unsigned)((BUF) * WPHB + k_ * 4096);                          \
-        unsigned keep_;                                                                              \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                     : "=&s"(keep_) : "v"(w_src + wsrc[k_]), "s"(dst_) : "memory");                  \
-      }                                                                                              \
+    _Pragma("unroll") for (int k_ = 0; k_ < WU; ++k_) {                                              \
+      const unsigned dst_ = wdst0 + (unsigned)((BUF) * WPHB + k_ * 4096);                            \
+      unsigned keep_;                                                                                \
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
+                   : "=&s"(keep_) : "v"(w_src + wsrc[k_]), "s"(dst_) : "memory");                    \
     }                                                                                                \
     if (w_ph + 1 < nphases) { /* past the end: the last phase's weights again, into a buffer nobody reads */ \
       ++w_ph;                                                                                        \
@@ -357,7 +337,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
     }                                                                                                \
   }
     // all vector-memory operations but the N youngest are done; LDS stores retired; phase barrier
-#define WD_WAIT_BAR(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"((abl & 5) ? 0 : (N)) : "memory");
+#define WD_WAIT_BAR(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 
     // ---- prologue: stage 0 in input buffer 0, weights of phase 0 (and 1) on their way; input of stage 1 in registers
     WD_TILE(0)
@@ -488,14 +468,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
 
   // weights of tap T (within the phase) -> register set WS_
 #define WC_READ_W(WS_, T)                                                                            \
-  if (!(abl & 16)) _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                                \
+  _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                                \
     wf[WS_][nf][0] = *reinterpret_cast<const V8*>(wb_ + ((T) * NB + nf * 32) * 64 + w_hi);           \
     wf[WS_][nf][1] = *reinterpret_cast<const V8*>(wb_ + ((T) * NB + nf * 32) * 64 + w_lo);           \
   }
   // pixel fragments of slot S, tap T -> register set AS_.  Tap T of a phase: TPP = 3: (tap row of the phase, T);
   // TPP = 9: (T / 3, T % 3)
 #define WC_READ_A(AS_, T, S)                                                                         \
-  if (!(abl & 16)) _Pragma("unroll") for (int i = 0; i < SM; ++i) {                                                   \
+  _Pragma("unroll") for (int i = 0; i < SM; ++i) {                                                   \
     const unsigned char* p_ = xb_ + pbase[(S) * SM + i] +                                            \
                               (TPP == 3 ? ro_ + (T) * kXPitch : ((T) / 3) * row1 + ((T) % 3) * kXPitch); \
     af[AS_][i][0] = *reinterpret_cast<const V8*>(p_);                                                \
@@ -504,14 +484,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
 #define WC_MFMA(AS_, WS_, S) WC_MFMA_Z(AS_, WS_, S, false)
   // Z: the first MFMA of each accumulator tile starts from a zero C operand (first tap of a tile in the DEFER path)
 #define WC_MFMA_Z(AS_, WS_, S, Z)                                                                    \
-  if (abl & 8) {                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < SM; ++i) {                                                 \
-      asm volatile("" ::"v"(af[AS_][i][0]), "v"(af[AS_][i][1]));                                     \
-    }                                                                                                \
-    _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                              \
-      asm volatile("" ::"v"(wf[WS_][nf][0]), "v"(wf[WS_][nf][1]));                                   \
-    }                                                                                                \
-  } else _Pragma("unroll") for (int i = 0; i < SM; ++i)                                              \
+  _Pragma("unroll") for (int i = 0; i < SM; ++i)                                                     \
     _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) {                                              \
       if (S16) { /* the row's halves are channels 0-15 and 16-31 of the chunk */                     \
         acc[(S) * SM + i][nf] = mfma32(wf[WS_][nf][1], af[AS_][i][1], acc[(S) * SM + i][nf]);        \
@@ -543,7 +516,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
     _Pragma("unroll") for (int m = 0; m < MF; ++m) {                                                 \
       const int oy = y0_ + (prc[m] >> 16), ox = x0_ + (prc[m] & 0xffff);                             \
       yo_[m] = (oy < a.Ho && ox < a.Wo) ? (oy * a.Wo + ox) * a.ldy : -1;                             \
-      if (abl & 32) yo_[m] = (acc[m][0][0] + acc[m][NF - 1][15] == 12345.678f) ? yo_[m] : -1;        \
     }                                                                                                \
     _Pragma("unroll") for (int nf = 0; nf < NF; ++nf)                                                \
       _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                \

@@ -853,8 +853,7 @@ int upcat_fwd_launch(const void* skip, int dt, int lds, int csp, const void* low
     set_error("upcat: skip smaller than upsampled input");
     return MIMO_ERR_INVALID;
   }
-  static const bool blocks2x2 = !(getenv("MIMO_UPCAT_2X2") && atoi(getenv("MIMO_UPCAT_2X2")) == 0);
-  if (!skip && H == 2 * h && W == 2 * w && blocks2x2) {
+  if (!skip && H == 2 * h && W == 2 * w) {
     MIMO_ST_DISPATCH(dt, T, hipLaunchKernelGGL(upcat_fwd2x2_kernel<T>, pq_grid(clp / 4, (int64_t)N * h * w, 4096), dim3(256), 0, st,
                                                csp / 4, (const T*)low, ldl, clp / 4, N, h, w, (T*)out, lo_scale, lo_shift));
     MIMO_KERNEL_CHECK();
@@ -1644,17 +1643,9 @@ int split_pairs_launch(const float* src, float* dst, int64_t P, int Cp, hipStrea
 
 // (plain / folded sources: held to 72 registers = 7 waves per SIMD, the occupancy round 3's grid scan found best — the
 // max |dz| tracking of round 5 had pushed the folded instance to 74 and cost the class 7 %)
-#ifndef MIMO_APPLY_MINWAVES
-#define MIMO_APPLY_MINWAVES 7
-#endif
-#ifndef MIMO_APPLY_REVERSE
-#define MIMO_APPLY_REVERSE 1  // 0: front to back (A/B builds)
-#endif
-#ifndef MIMO_APPLY_ABSMAX
-#define MIMO_APPLY_ABSMAX 1  // 0: A/B build without the max |dz| tracking (the two-MFMA weight gradient then reads garbage)
-#endif
+constexpr int kApplyMinWaves = 7;
 template <typename TZ, typename TA, int SRC>
-__global__ __launch_bounds__(256, (SRC == GS_PLAIN || SRC == GS_FOLD) ? MIMO_APPLY_MINWAVES : 1) void bn_bwd_apply_kernel(const GradSrc src, const TZ* __restrict__ z, int ldz, const float* __restrict__ scale,
+__global__ __launch_bounds__(256, (SRC == GS_PLAIN || SRC == GS_FOLD) ? kApplyMinWaves : 1) void bn_bwd_apply_kernel(const GradSrc src, const TZ* __restrict__ z, int ldz, const float* __restrict__ scale,
                                     const float* __restrict__ shift, const float* __restrict__ mean,
                                     const float* __restrict__ invstd, const float* __restrict__ mask, int C,
                                     const float* __restrict__ c1, const float* __restrict__ c2, int Cv, int N, int H,
@@ -1681,7 +1672,7 @@ __global__ __launch_bounds__(256, (SRC == GS_PLAIN || SRC == GS_FOLD) ? MIMO_APP
       else
         st4(dz + (size_t)p * Cp + 4 * t.q, r);
       acc = f4add(acc, r);
-      if (MIMO_APPLY_ABSMAX) amax = absmax4(amax, r);
+      amax = absmax4(amax, r);
     };
     if constexpr (SRC == GS_POOL) {
       const int Hc = (H + 1) / 2, Wc = (W + 1) / 2, P = N * Hc * Wc;
@@ -1697,7 +1688,6 @@ __global__ __launch_bounds__(256, (SRC == GS_PLAIN || SRC == GS_FOLD) ? MIMO_APP
       }
     } else {
       const int P = N * H * W;
-#if MIMO_APPLY_REVERSE
       // back to front: the statistics pass in front of this one read the same two tensors front to back, so their LAST
       // part is what the last-level cache still holds
       if (t.p < P) {
@@ -1709,17 +1699,9 @@ __global__ __launch_bounds__(256, (SRC == GS_PLAIN || SRC == GS_FOLD) ? MIMO_APP
           emit(p, relu_grad4<SRC, TZ, TA>(src, hl, mask, C, p, it, t.q, H, W, v, sc, sh, &d0, &d1), v);
         }
       }
-#else
-      PixIter it = pix_iter(t.p, t.pstep, H, W);
-      for (int p = t.p; p < P; p += t.pstep, pix_next(it, H, W)) {
-        const float4 v = ld4(z + (size_t)p * ldz + 4 * t.q);
-        float d0, d1;
-        emit(p, relu_grad4<SRC, TZ, TA>(src, hl, mask, C, p, it, t.q, H, W, v, sc, sh, &d0, &d1), v);
-      }
-#endif
     }
   }
-  if (MIMO_APPLY_ABSMAX && absmax) block_absmax_store(absmax, amax);
+  if (absmax) block_absmax_store(absmax, amax);
   if (!partial) return;  // training mode: the bias gradient is exactly zero, no column sums wanted
   const float4 s = quad_block_sum(acc, t, red);
   if (t.pl == 0 && t.q < Cv) st4(partial + (size_t)blockIdx.x * Cp + 4 * t.q, s);

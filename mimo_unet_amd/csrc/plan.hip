@@ -56,7 +56,6 @@ struct Act {
   // [0, Cp), pixel pitch skipgrad_ld) until the MaxPool backward of the same tensor folds it in
   const float* skipgrad = nullptr;
   int skipgrad_ld = 0;
-  bool pooled = false;  // some Down block pools this tensor (its pool_bwd then takes the skip gradient along)
   // Pooled gradient of this tensor left in the pooling Down block's own padded-domain buffer (pixel pitch poolgrad_ld) for
   // the BatchNorm backward of the producing convolution(s) to route through the max-pool windows themselves (GS_POOL,
   // elementwise.h): pool_bwd is not launched and `da` is not written.  A channel slice of a concat tensor (down1[s] inside
@@ -122,7 +121,6 @@ struct DoubleConv {
   Act* src1 = nullptr;   // IN_UPCAT: low-resolution tensor
   float* in_buf = nullptr;  // materialised input (packed image / pooled / concat)
   int in_ld = 0;
-  bool skip_in_place = false;  // IN_UPCAT: the skip tensor already lives in channels [0, Cs) of in_buf
   bool pool_fused = false;     // IN_POOL: in_buf is written by the producers' BatchNorm + ReLU pass
   float* dxpad_own = nullptr;  // IN_UPCAT: private buffer of c1's padded-domain data gradient (holds the skip slice
                                // until the skip tensor's pool backward has read it)
@@ -196,9 +194,6 @@ struct mimo_plan {
   // test hook (MIMO_DEBUG_WGRAD_DELAY_US, read per plan): an idle kernel of that many microseconds in front of every weight
   // gradient, on the stream it runs on — the consumer of dz and its max |dz| slots arrives late (tests/test_streams_gpu.py)
   int wg_delay_us = 0;
-  // the hand-off events between the two streams ride on the launches that produce what they announce (hipExtLaunchKernelGGL
-  // stop event) instead of hipEventRecord calls behind them: MIMO_EVENT_ON_LAUNCH=0 restores the records (A/B; read per plan)
-  bool ev_attach = true;
   // BatchNorm backward forms the gradient arriving at a pooled tensor / at the head's input itself (GS_POOL / GS_HEAD):
   // fp32 storage, MIMO_FUSE_BWD_SRC=0 switches it off (read per plan)
   bool fuse_bwd_src = false;
@@ -620,7 +615,6 @@ struct mimo_plan {
       dc->out.a = dc->c2.a;
       dc->out.ld = up->in_ld;
     }
-    up->skip_in_place = true;
   }
 
   int set_input(DoubleConv* dc, InputKind kind, Act* s0, Act* s1, int in_cp, int h, int w) {
@@ -628,9 +622,9 @@ struct mimo_plan {
     dc->src0 = s0;
     dc->src1 = s1;
     MIMO_TRY(alloc_act(&dc->in_buf, (size_t)N * h * w * in_cp, kind == IN_IMAGE ? ST_F32 : st));  // the packed image stays fp32
-    if (kind == IN_POOL) s0->pooled = true;
-    static const bool skip_keep = !(getenv("MIMO_SKIP_GRAD_IN_PLACE") && atoi(getenv("MIMO_SKIP_GRAD_IN_PLACE")) == 0);
-    if (kind == IN_UPCAT && skip_keep && s0->pooled && !cfg.inference_only)
+    // the skip slice of the data gradient stays in this block's own buffer until the pool backward of the skip tensor folds
+    // it in (every skip tensor is pooled by a Down block)
+    if (kind == IN_UPCAT && !cfg.inference_only)
       MIMO_TRY(alloc_act(&dc->dxpad_own, (size_t)N * (h + 2) * (w + 2) * in_cp, st));
     // the pooled gradient stays in this block's own buffer until the producers' BatchNorm backward has routed it (GS_POOL)
     if (kind == IN_POOL && fuse_bwd_pool) MIMO_TRY(alloc_act(&dc->dxpad_own, (size_t)N * (h + 2) * (w + 2) * in_cp, st));
@@ -680,8 +674,6 @@ struct mimo_plan {
       const char* e = getenv("MIMO_WGRAD_CUS");
       const int v = e ? atoi(e) : 0;
       wg_cus = (v >= 8 && v <= 256) ? v : sched::wg_side_cus((long)N * H * W, S * f);
-      const char* ea = getenv("MIMO_EVENT_ON_LAUNCH");
-      ev_attach = !(ea && atoi(ea) == 0);
       const char* d = getenv("MIMO_DEBUG_WGRAD_DELAY_US");
       wg_delay_us = d ? std::max(0, std::min(atoi(d), 5000)) : 0;
     }
@@ -697,7 +689,6 @@ struct mimo_plan {
               W5 = W4 / 2;
     std::vector<int> imgmap(Ci_p);
     for (int i = 0; i < Ci_p; ++i) imgmap[i] = i < Ci ? i : -1;
-    const bool skip_alias = !(getenv("MIMO_SKIP_IN_PLACE") && atoi(getenv("MIMO_SKIP_IN_PLACE")) == 0);
 
     // ---- encoder (model.py:150-175) ----
     for (int s = 0; s < S; ++s) {
@@ -747,25 +738,23 @@ struct mimo_plan {
       MIMO_TRY(make_dc(&up1, "core.up1.conv.double_conv", m, 16 * f * S, 8 * f * S, 4 * f * S, H4, W4, pc, nullptr, 0,
                        nullptr, 0));
       MIMO_TRY(set_input(up1, IN_UPCAT, &down3->out, &down4->out, (int)m.size(), H4, W4));
-      if (skip_alias) rehome_skip(down3->out, up1, {{down3, 0}});
+      rehome_skip(down3->out, up1, {{down3, 0}});
     }
     {
       std::vector<int> m = cat_map(down2->out, up1->out);
       MIMO_TRY(make_dc(&up2, "core.up2.conv.double_conv", m, 8 * f * S, 4 * f * S, 2 * f * S, H3, W3, pc, nullptr, 0,
                        nullptr, 0));
       MIMO_TRY(set_input(up2, IN_UPCAT, &down2->out, &up1->out, (int)m.size(), H3, W3));
-      if (skip_alias) rehome_skip(down2->out, up2, {{down2, 0}});
+      rehome_skip(down2->out, up2, {{down2, 0}});
     }
     {
       std::vector<int> m = cat_map(x2cat, up2->out);
       MIMO_TRY(make_dc(&up3, "core.up3.conv.double_conv", m, 4 * f * S, 2 * f * S, f * S, H2, W2, pc, nullptr, 0, nullptr,
                        0));
       MIMO_TRY(set_input(up3, IN_UPCAT, &x2cat, &up2->out, (int)m.size(), H2, W2));
-      if (skip_alias) {
-        std::vector<std::pair<DoubleConv*, int>> pr;
-        for (int s = 0; s < S; ++s) pr.push_back({down1[s], s * c2p});
-        rehome_skip(x2cat, up3, pr);
-      }
+      std::vector<std::pair<DoubleConv*, int>> pr;
+      for (int s = 0; s < S; ++s) pr.push_back({down1[s], s * c2p});
+      rehome_skip(x2cat, up3, pr);
     }
     // the outputs of the core's Up blocks are read only by the next block's bilinear up-sampling: it applies their
     // BatchNorm + ReLU itself and the activated tensor is not written in a training forward (elide_output)
@@ -773,7 +762,7 @@ struct mimo_plan {
     elide_output(up2);
     elide_output(up3);
     // MaxPool2d inputs are produced by the BatchNorm + ReLU pass of the tensor they pool (one pass less per Down block)
-    if (!(getenv("MIMO_POOL_FUSED") && atoi(getenv("MIMO_POOL_FUSED")) == 0)) {
+    {
       auto fuse = [this](DoubleConv* producer, DoubleConv* consumer, int choff) {
         producer->c2.pool_out = eoff(consumer->in_buf, choff);
         producer->c2.pool_ld = consumer->in_ld;
@@ -792,7 +781,7 @@ struct mimo_plan {
       MIMO_TRY(make_dc(&dc, "decoder.up4s." + std::to_string(s) + ".conv.double_conv", m, cin_dec, cin_dec / 2, f, H1, W1,
                        cfg.decoder_dropout_rate, nullptr, 0, nullptr, 0));
       MIMO_TRY(set_input(dc, IN_UPCAT, &enc_in[s]->out, &up3->out, (int)m.size(), H1, W1));
-      if (skip_alias) rehome_skip(enc_in[s]->out, dc, {{enc_in[s], 0}});
+      rehome_skip(enc_in[s]->out, dc, {{enc_in[s], 0}});
       // read by the 1x1 head (forward and backward) only; the element-wise final dropout would need the activated tensor
       if (cfg.final_dropout_rate <= 0.f) elide_output(dc);
       up4.push_back(dc);
@@ -839,13 +828,10 @@ struct mimo_plan {
         // round 6 in bench.py's one-rank RCCL route, where the process group's streams had taken the other queues: no
         // overlap at all, 5.8 instead of 4.4 ms per step at 4 images per GPU (profiles/r06/b4/queue_collision.txt).  The
         // priority classes draw from separate queue pools, and callers run on default-priority streams.
-        // MIMO_WGRAD_STREAM_PRIORITY=0 restores a default-priority stream (A/B).
         {
           int least = 0, greatest = 0;
           MIMO_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-          const char* pe = getenv("MIMO_WGRAD_STREAM_PRIORITY");
-          const bool low = !(pe && atoi(pe) == 0) && least != greatest;
-          if (low)
+          if (least != greatest)
             MIMO_HIP_CHECK(hipStreamCreateWithPriority(&wg_stream, hipStreamNonBlocking, least));
           else
             MIMO_HIP_CHECK(hipStreamCreateWithFlags(&wg_stream, hipStreamNonBlocking));
@@ -1091,7 +1077,7 @@ struct mimo_plan {
       Act *sk = dc->src0, *lo = dc->src1;
       const int pr = prof_begin(MIMO_PROF_UPCAT_FWD, st);
       const bool lz = lo->z_live;  // the low-resolution tensor through its BatchNorm + ReLU
-      MIMO_TRY(upcat_fwd_launch(dc->skip_in_place ? nullptr : sk->a, this->st, sk->ld, sk->Cp, lz ? lo->z : lo->a,
+      MIMO_TRY(upcat_fwd_launch(nullptr, this->st, sk->ld, sk->Cp, lz ? lo->z : lo->a,
                                 lz ? lo->z_ld : lo->ld, lo->Cp, N, h, w, lo->H, lo->W, dc->in_buf, st, lz ? lo->z_scale : nullptr,
                                 lz ? lo->z_shift : nullptr));
       // writes the up-sampled channels at (h, w), reads the low-resolution tensor once
@@ -1398,7 +1384,7 @@ struct mimo_plan {
     // "dz exists" travels with the launch that writes it (a stop event on the kernel, no hipEventRecord behind it) whenever that
     // launch is the last writer — not when a split copy of dz follows — and not under stream capture
     const bool needs_split_copy = L.wg_split && !L.dg_split && !thin_wg;
-    const bool ev_on_launch = async && ev_attach && !capturing && !needs_split_copy;
+    const bool ev_on_launch = async && !capturing && !needs_split_copy;
     MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask,
                                  L.Cout, L.c1, L.c2, L.cout_p, L.N, L.H, L.W, dz, (L.dg_split && !mixed && !thin_wg) ? 1 : 0,
                                  fwd_training ? nullptr : s_partial, &rows, st, (L.wg_np2 && !thin_wg) ? s_dzmax2[b] : nullptr,
@@ -1485,7 +1471,7 @@ struct mimo_plan {
     else
       MIMO_TRY(wgrad_launch(wg, ws));
     prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), ws);
-    const bool wg_ev_on_launch = async && ev_attach && !capturing && !thin_wg;
+    const bool wg_ev_on_launch = async && !capturing && !thin_wg;
     if (!thin_wg)  // (the plain-FMA kernel's launch reduces its own partials)
       MIMO_TRY(wgrad_reduce_launch(s_wslab, L.wg_splits, L.wg_cin_pad, L.wg_cout_pad, L.cin_map, L.cin_p, L.Cin, L.Cout,
                                    grads + L.off_w, ws, wg.dz_absmax, wg.dz_absmax_n, wg_ev_on_launch ? ev_wg[b] : nullptr));
@@ -1555,12 +1541,9 @@ struct mimo_plan {
       s->skipgrad = nullptr;
     } else if (dc->kind == IN_UPCAT) {
       Act *sk = dc->src0, *lo = dc->src1;
-      if (dc->dxpad_own) {  // the skip slice stays where the data gradient wrote it; the pool backward of sk folds it in
-        sk->skipgrad = dxB;
-        sk->skipgrad_ld = ldp;
-      } else {
-        MIMO_TRY(fold_slice_launch(dxB, this->st, ldp, 0, sk->da, sk->ldda, N, h, w, sk->Cp, acc_flag(sk), st));
-      }
+      // the skip slice stays where the data gradient wrote it (dxpad_own); the pool backward of sk folds it in
+      sk->skipgrad = dxB;
+      sk->skipgrad_ld = ldp;
       const int pr = prof_begin(MIMO_PROF_UP_BWD, st);
       MIMO_TRY(up_bwd_launch(dxB, this->st, ldp, sk->Cp, lo->da, lo->ldda, N, h, w, lo->H, lo->W, lo->Cp, acc_flag(lo), st));
       // reads the up-sampled slice of the padded-domain gradient once, writes the low-resolution gradient

@@ -97,12 +97,12 @@ static inline bool wg_use_ws(int CI, int CO, bool ws_enabled) {
 static inline int wg_ws_tr(int CI, bool s16 = false) { return (CI == 32 || s16) ? 4 : 2; }
 static inline int wg_num_tiles(int N, int H, int W, int tr) { return N * cdiv(H, tr) * cdiv(W, kWgTC); }
 // pixel splits (slabs) of a layer's weight gradient: >= 1, <= min(tiles, 1024)
-static inline int wg_pick_splits(int N, int H, int W, int cin_pad, int cout_pad, int CI, int CO, bool ws_enabled, int mode,
+static inline int wg_pick_splits(int N, int H, int W, int cin_pad, int cout_pad, int CI, int CO, bool ws_enabled,
                                  bool s16 = false, int cus = 256) {
   const int wtiles = (cin_pad / CI) * (cout_pad / CO);
   const bool ws = wg_use_ws(CI, CO, ws_enabled);
   const int tiles = wg_num_tiles(N, H, W, ws ? wg_ws_tr(CI, s16) : 4);
-  if (!ws || mode == 0) {
+  if (!ws) {
     int splits = cdiv(512, wtiles);  // one 4-wave workgroup per CU: ~2 rounds of workgroups
     if (splits > tiles) splits = tiles;
     if (splits > 1024) splits = 1024;

@@ -25,18 +25,6 @@
 
 #include "common.h"
 
-#ifndef MIMO_WGRAD_NP2_DEPTH
-// taps the activation fragments of the two-MFMA weight gradient are read ahead of their MFMAs (a tap is 2 * NI MFMAs = 128
-// matrix-pipe cycles at NI = 4, about the latency of a transposed LDS read)
-#define MIMO_WGRAD_NP2_DEPTH 1
-#endif
-#ifndef MIMO_WGRAD_PIN_PROLOGUE
-// 1: pin the prologue's LDS reads into a scheduling group of their own, which puts the consumers' fragment reads really
-// one tap ahead of their MFMAs in the ISA.  Measured SLOWER (round 4, profiles/r04/wgrad_read_pipeline.txt: +3.5 % per
-// layer, wgrad class 6.16-6.29 -> 6.29-6.41 ms in four alternating step pairs): off.
-#define MIMO_WGRAD_PIN_PROLOGUE 0
-#endif
-
 namespace mimo {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -385,15 +373,8 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_ws_kernel(WgradLaunch a, i
   constexpr int kWsTR = TR_, kWsAPix = (kWsTR + 2) * kWgTCP, kWsDPix = kWsTR * kWgTC;
   constexpr int PA = X16 ? wg_pitch16(CI) : wg_pitch(CI), PD = D16 ? wg_pitch16(CO) : wg_pitch(CO);
   constexpr int QA = X16 ? CI / 8 : CI / 4, QD = D16 ? CO / 8 : CO / 4;  // 16-byte units per pixel
-#ifdef MIMO_WGRAD_ABLATE
-  // timing-only builds (results are wrong): 1 = the producers stage only the first half of the activation halo tile (what
-  // a row ring that shares halo rows between vertically adjacent tiles would stage per tile); 2 = none of it; 4 = no dz
-  constexpr int XA = (MIMO_WGRAD_ABLATE & 2) ? 1 : (MIMO_WGRAD_ABLATE & 1) ? (kWsAPix * QA / 2 + 255) / 256 : (kWsAPix * QA + 255) / 256;
-  constexpr int XD = (MIMO_WGRAD_ABLATE & 4) ? 1 : (kWsDPix * QD + 255) / 256;
-#else
   constexpr int XA = (kWsAPix * QA + 255) / 256;  // per producer thread
   constexpr int XD = NP == 2 ? 2 * ((kWsDPix * (CO / 8) + 255) / 256) : (kWsDPix * QD + 255) / 256;
-#endif
   constexpr int ABYTES = kWsAPix * PA, DBYTES = kWsDPix * PD, BUFBYTES = ABYTES + DBYTES;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUFBYTES];
 
@@ -598,7 +579,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_ws_kernel(WgradLaunch a, i
       // r.  One MFMA per product (16-bit storage, bf16 mode): a tap is NI MFMAs = 16 * NI cycles of matrix-pipe time,
       // far below the ~130-cycle latency of a transposed LDS read -> two taps ahead (round 3: with one tap ahead that
       // path waited for LDS at every tap, 598 -> 789 TFLOP/s on the class).  Three MFMAs per product: one tap ahead.
-      constexpr int kDepth = NP == 3 ? 1 : NP == 2 ? MIMO_WGRAD_NP2_DEPTH : 2;
+      // Two MFMAs per product: a tap is 2 * NI MFMAs = 128 matrix-pipe cycles at NI = 4, about the latency of a transposed
+      // LDS read -> one tap ahead.
+      constexpr int kNp2Depth = 1;
+      constexpr int kDepth = NP == 3 ? 1 : NP == 2 ? kNp2Depth : 2;
       bf16x8 bh[2][NI], bl[NP >= 2 ? 2 : 1][NI], ah[kDepth + 1][MI], al[NP == 3 ? kDepth + 1 : 1][MI];
       // the fragment addresses of all TR x taps steps are loop-invariant; hoisted out of the tile loop they would take
       // ~45 registers (spills) — an opaque copy of the lane's row index per tile keeps them recomputed in place
@@ -629,10 +613,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_ws_kernel(WgradLaunch a, i
     WS_READ_B(0, 0)                                                                  \
     _Pragma("unroll") for (int s_ = 0; s_ < kDepth; ++s_)                            \
       WS_READ_A1(s_ % (kDepth + 1), s_ / (NT), (T0) + s_ % (NT))                     \
-    /* Without this pin the FIRST in-loop group (the reads of step kDepth) takes the prologue's reads and every later \
-       group moves one step down: in the ISA the fragments of a tap are read right in front of its MFMAs.  With it   \
-       they are read one tap ahead, as the source says — and the kernel is 3.5 % slower (see the switch's comment). */ \
-    if (MIMO_WGRAD_PIN_PROLOGUE) __builtin_amdgcn_sched_group_barrier(0x100, kRB + kDepth * kRA, 0); \
+    /* The prologue's reads are deliberately not pinned into a scheduling group of their own.  Unpinned, the FIRST \
+       in-loop group (the reads of step kDepth) takes them and every later group moves one step down: in the ISA the \
+       fragments of a tap are read right in front of its MFMAs.  Pinned, they are read one tap ahead, as the source   \
+       says — and the kernel was 3.5 % slower (round 4, profiles/r04/wgrad_read_pipeline.txt). */                     \
     _Pragma("unroll") for (int s_ = 0; s_ < kSteps; ++s_) {                          \
       const int r_ = s_ / (NT), tt = s_ % (NT);                                      \
       const bool rb_ = tt == 0 && r_ + 1 < kWsTR, ra_ = s_ + kDepth < kSteps;        \
@@ -695,8 +679,7 @@ static bool wgrad_ws_enabled() {
 void wgrad_split_tiles(int cin_p, int cout_p, int* CI, int* CO) { sched::wg_tiles(cin_p, cout_p, wgrad_ws_enabled(), CI, CO); }
 static bool wgrad_use_ws(int CI, int CO) { return sched::wg_use_ws(CI, CO, wgrad_ws_enabled()); }
 int wgrad_split_pick_splits(int N, int H, int W, int cin_pad, int cout_pad, int CI, int CO, int store, int cus) {
-  static const int mode = [] { const char* e = getenv("MIMO_WGRAD_SPLIT_MODE"); return e ? atoi(e) : 1; }();
-  return sched::wg_pick_splits(N, H, W, cin_pad, cout_pad, CI, CO, wgrad_ws_enabled(), mode, wgrad_s16(store),
+  return sched::wg_pick_splits(N, H, W, cin_pad, cout_pad, CI, CO, wgrad_ws_enabled(), wgrad_s16(store),
                                cus >= 8 && cus <= 256 ? cus : 256);
 }
 

@@ -18,19 +18,12 @@ VARIANTS = {
         "MIMO_WGRAD_WS": "0",              # 4-wave weight gradient for 64x64 tiles too
         "MIMO_WGRAD_STREAM": "0",          # weight gradients on the caller's stream (the default is the side stream)
         "MIMO_HIP_GRAPH": "0",
-        "MIMO_SKIP_IN_PLACE": "0",         # skip tensors copied into the concat buffers
-        "MIMO_SKIP_GRAD_IN_PLACE": "0",    # skip-connection gradients copied out by fold_slice
-        "MIMO_POOL_FUSED": "0",            # separate MaxPool2d pass after BatchNorm + ReLU
         "MIMO_FUSE_BN_IN": "0",            # the activation between the two convolutions of a block materialised
         "MIMO_FUSE_BWD_SRC": "0",          # pool_bwd / head_bwd as separate kernels writing the gradient tensors
         "MIMO_CONV_THIN": "0",             # the image convolution on the fp32 MFMA kernels / the split weight gradient
     },
     "specialised_kernels_plain": {
-        "MIMO_CONV_WIDE": "0",             # 256-pixel kernels everywhere ...
-        "MIMO_CONV_WS_MF2": "0",           # ... thin forward layers on 256-pixel tiles, one workgroup per CU
-        "MIMO_CONV_WDMA": "0",             # convolution weights staged through registers, not by LDS-DMA
-        "MIMO_CONV_PAIR_TAIL": "0",        # short last K chunks with one tap per MFMA
-        "MIMO_WGRAD_SPLIT_MODE": "0",      # fixed split count of the weight gradient
+        "MIMO_CONV_WIDE": "0",             # 256-pixel kernels everywhere
     },
     "conv_wide_forced": {"MIMO_CONV_WIDE": "2"},  # every supported convolution on conv_wide.hip
     "image_conv_wgrad_forced": {"MIMO_CONV_THIN": "2"},  # 1-2-channel weight gradients on conv_thin.hip at every size
