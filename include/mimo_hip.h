@@ -320,6 +320,40 @@ int mimo_training_epilogue(const float* out, const float* label, const int64_t* 
                            int64_t hw, int32_t loss_kind, float* label_t, float* preds, float* aleatoric_std, float* err,
                            float* scalars, double* scratch, int32_t scratch_blocks, mimo_stream stream);
 
+/* ---- uncertainty evaluation: replaces the host half of scripts/test/test_nyuv2_depth.py (convert_to_pandas :93-106,
+ * compute_metrics :128-130, create_precision_recall_plot :133-144, create_calibration_plot :147-170) and of
+ * scripts/test/test_ndvi.py:86-128 — the frame of all test pixels, its sort and the 41 ppf sweeps — by three device
+ * passes over an 8-byte record per pixel.  Asynchronous on the stream; no allocation, no synchronisation.
+ * workspace: device memory of mimo_eval_workspace_bytes() bytes, 16-byte aligned, zeroed by the caller to reset the
+ * running sums; the calls that share a workspace must be issued on ONE stream (its partial rows and the record store are
+ * ordered by nothing else); records: the caller's device record store, one uint64 per pixel fed so far
+ * (low word: bit pattern of combined_std, high word: |error|; 0xFFFFFFFF in the low word marks a skipped pixel). */
+size_t mimo_eval_workspace_bytes(void);
+/* One batch (make_predictions' clip + `[:, 0]`, test_nyuv2_depth.py:73-74,85-89; convert_to_pandas' two square roots,
+ * :97-99; `error`, :129; `below = y_true < ppf`, :149,166).  mean / aleatoric_var / epistemic_var / label
+ * [batch,channels,hw] fp32, of which plane `channel` is used; mask [batch,mask_channels,hw] (mask_channels 1 or
+ * channels; pixels with 0 are skipped and counted) or NULL.  clip != 0 clamps mean and label to [clip_lo, clip_hi].
+ * thresholds: device [num_thresholds <= 64] ascending standard quantiles z_k of the expected confidences; a pixel is
+ * "below" at k when label < mean + (sqrt(aleatoric_var) / sqrt 2) z_k in fp32, never when aleatoric_var == 0.
+ * records points at the first free slot; batch * hw slots are written. */
+int mimo_eval_accumulate(const float* mean, const float* aleatoric_var, const float* epistemic_var, const float* label,
+                         const float* mask, int32_t batch, int32_t channels, int32_t channel, int32_t mask_channels,
+                         int64_t hw, int32_t clip, float clip_lo, float clip_hi, const float* thresholds,
+                         int32_t num_thresholds, uint64_t* records, void* workspace, mimo_stream stream);
+/* The cutoffs of `df.sort_values(by='combined_std', ascending=False)` + `(percentiles * N).astype(int)`
+ * (test_nyuv2_depth.py:134-137) without a sort: for each of the num_percentiles <= 128 values (device doubles) the exact
+ * key of the most uncertain pixel that survives, and how many records with exactly that key survive.
+ * num_records < 2^32 (32-bit histogram counters). */
+int mimo_eval_select(const uint64_t* records, int64_t num_records, const double* percentiles, int32_t num_percentiles,
+                     void* workspace, mimo_stream stream);
+/* The `df.iloc[cutoff:]["error"].mean()` rows (test_nyuv2_depth.py:139-142) and `below.mean(axis=1)` (:167) after
+ * mimo_eval_select.  out: device doubles [3 * num_percentiles + num_thresholds + 6] = mae | rmse | threshold value of
+ * combined_std per cutoff, observed share per threshold, then n, n_masked, n_nonfinite, mae, mse, rmse of all pixels.
+ * Records whose key ties with a threshold key contribute their mean error and mean squared error for the number of
+ * them that survive. */
+int mimo_eval_interval_sums(const uint64_t* records, int64_t num_records, int32_t num_percentiles, int32_t num_thresholds,
+                            void* workspace, double* out, mimo_stream stream);
+
 /* ---- single-operator entry points (NHWC, channel-padded) used by the parity tests -------
  * They run the same kernels the plan runs.  x [N,H,W,cin_p], w OIHW [cout][cin][3][3]. */
 int mimo_op_conv3x3_forward(const float* x, const float* w, const float* bias, float* z, double* stats,

@@ -88,6 +88,10 @@ _SIGNATURES = {
     "mimo_validation_epilogue": (C.c_int, [_P, _P, _P, _I, _I, _I, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mimo_loss_buffer_step": (C.c_int, [_P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "mimo_training_epilogue": (C.c_int, [_P, _P, _P, _I, _I, _I, _L, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mimo_eval_workspace_bytes": (C.c_size_t, []),
+    "mimo_eval_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _F, _F, _P, _I, _P, _P, _P]),
+    "mimo_eval_select": (C.c_int, [_P, _L, _P, _I, _P, _P]),
+    "mimo_eval_interval_sums": (C.c_int, [_P, _L, _I, _I, _P, _P, _P]),
     "mimo_op_conv3x3_forward": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mimo_op_conv3x3_dgrad": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mimo_op_conv3x3_wgrad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -1,0 +1,206 @@
+"""`UncertaintyEvaluator`: the sparsification and calibration tables of the reference's test scripts
+(``scripts/test/test_nyuv2_depth.py:93-170``, ``scripts/test/test_ndvi.py:52-128``), formed on the GPU.
+
+The reference moves every pixel of the test set to the host, builds a pandas frame, sorts it by `combined_std` for
+`precision_recall.csv` and sweeps 41 `scipy.stats.norm.ppf` calls over it for `calibration.csv`.  Here each batch is
+reduced where `EnsembleModule(keep_on_device=True)` leaves it: one pass (`mimo_eval_accumulate`) appends an 8-byte
+record per pixel to a device store and bumps the calibration counters; `compute()` selects the 100 cutoff keys exactly
+with three counting passes (`mimo_eval_select`), sums the intervals between them (`mimo_eval_interval_sums`) and copies
+one small buffer to the host.  No pandas, no scipy, no CPU path.
+
+    ev = UncertaintyEvaluator()
+    for batch in loader:
+        ev.update_from(ensemble, batch["image"].cuda(), batch["label"].cuda())
+    ev.write_csv(result_dir)
+"""
+from __future__ import annotations
+
+import os
+import warnings
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MAX_PERCENTILES = 128  # eval_stats.hip: kMaxP
+MAX_THRESHOLDS = 64    # eval_stats.hip: kMaxK
+PRECISION_RECALL_HEADER = ("percentile", "mae", "rmse")       # test_nyuv2_depth.py:142
+CALIBRATION_HEADER = ("Expected Conf.", "Observed Conf.")     # test_nyuv2_depth.py:169
+
+_NDTRI_P0 = (-5.99633501014107895267E1, 9.80010754185999661536E1, -5.66762857469070293439E1, 1.39312609387279679503E1,
+             -1.23916583867381258016E0)
+_NDTRI_Q0 = (1.95448858338141759834E0, 4.67627912898881538453E0, 8.63602421390890590575E1, -2.25462687854119370527E2,
+             2.00260212380060660359E2, -8.20372256168333339912E1, 1.59056225126211695515E1, -1.18331621121330003142E0)
+
+
+def cutoff_indices(percentiles, n: int) -> np.ndarray:
+    """How many of the most uncertain pixels each row drops: the truncation of the float64 product
+    `(percentiles * N).astype(int)` (test_nyuv2_depth.py:137) — not integer arithmetic.  The evaluator itself forms
+    these ranks on the device (eval_select_init_kernel: the pixel count never visits the host before the final copy),
+    with this arithmetic; the function mirrors that kernel for callers (plots, checks) and for the tests."""
+    p = np.asarray(percentiles, dtype=np.float64)
+    return np.clip((p * np.float64(n)).astype(np.int64), 0, n)
+
+
+def standard_quantiles(expected_p, distribution: str = "norm") -> np.ndarray:
+    """z_k = ppf(p_k) of the standard distribution in float64; -inf at p = 0 and +inf at p = 1.  "norm" is what the
+    reference passes for every model (test_nyuv2_depth.py:233); "laplace" is the closed form of scipy.stats.laplace."""
+    p = np.asarray(expected_p, dtype=np.float64)
+    if distribution == "norm":
+        z = torch.special.ndtri(torch.from_numpy(np.ascontiguousarray(p))).numpy()
+        # Central region (exp(-2) < p < 1 - exp(-2)): Cephes' rational approximation (ndtri.c, the routine behind
+        # scipy.special.ndtri) evaluated step by step in float64, so that the table does not depend on how a build of
+        # torch contracts the same polynomial (2 ulp were seen); the tails stay torch's.
+        mid = np.minimum(p, 1.0 - p) > 0.13533528323661269189
+        y = p[mid] - 0.5
+        y2 = y * y
+        num, den = np.full_like(y2, _NDTRI_P0[0]), y2 + _NDTRI_Q0[0]
+        for c in _NDTRI_P0[1:]:
+            num = num * y2 + c
+        for c in _NDTRI_Q0[1:]:
+            den = den * y2 + c
+        z[mid] = (y + y * (y2 * num / den)) * 2.50662827463100050242
+        return z
+    if distribution == "laplace":
+        with np.errstate(divide="ignore"):
+            return np.where(p > 0.5, -np.log(2.0 * (1.0 - p)), np.log(2.0 * p))
+    raise ValueError(f"distribution must be 'norm' or 'laplace', not {distribution!r}")
+
+
+def write_tables_csv(tables: dict, directory: str) -> Tuple[str, str]:
+    """`precision_recall.csv` and `calibration.csv` with the reference's headers (what `DataFrame.to_csv(index=False)`
+    writes, test_nyuv2_depth.py:229,234)."""
+    os.makedirs(directory, exist_ok=True)
+    pr, cal = tables["precision_recall"], tables["calibration"]
+    paths = (os.path.join(directory, "precision_recall.csv"), os.path.join(directory, "calibration.csv"))
+    with open(paths[0], "w") as f:
+        f.write(",".join(PRECISION_RECALL_HEADER) + "\n")
+        for row in zip(pr["percentile"], pr["mae"], pr["rmse"]):
+            f.write(",".join(repr(float(v)) for v in row) + "\n")
+    with open(paths[1], "w") as f:
+        f.write(",".join(CALIBRATION_HEADER) + "\n")
+        for row in zip(cal["expected"], cal["observed"]):
+            f.write(",".join(repr(float(v)) for v in row) + "\n")
+    return paths
+
+
+class UncertaintyEvaluator:
+    """Streaming reducer of `(mean, aleatoric_var, epistemic_var, label)` batches into the reference's two tables.
+
+    `update` is asynchronous on the current stream; `compute` is the one host synchronisation and may be called
+    repeatedly (running tables).  One evaluator is single-stream: `update`, `compute` and `reset` share one workspace
+    and one record store, ordered only by the stream they are issued on — call them all under the same current stream.  A single device: to merge evaluators of several GPUs the 65 + 5 accumulators would be
+    all-reduced and the three histogram passes all-gathered — not built."""
+
+    def __init__(self, expected_p: Optional[Sequence[float]] = None, percentiles: Optional[Sequence[float]] = None,
+                 distribution: str = "norm", clip: Optional[Tuple[float, float]] = (0.0, 1.0), channel: int = 0,
+                 device=None):
+        self.expected_p = np.arange(41) / 40.0 if expected_p is None else np.asarray(expected_p, dtype=np.float64)
+        self.percentiles = np.arange(100) / 100.0 if percentiles is None else np.asarray(percentiles, dtype=np.float64)
+        if not 1 <= self.expected_p.size <= MAX_THRESHOLDS or not 1 <= self.percentiles.size <= MAX_PERCENTILES:
+            raise ValueError(f"1..{MAX_THRESHOLDS} expected confidences and 1..{MAX_PERCENTILES} percentiles")
+        if np.any(np.diff(self.expected_p) < 0) or self.expected_p.min() < 0 or self.expected_p.max() > 1:
+            raise ValueError("expected_p must be ascending within [0, 1]")
+        self.distribution = distribution
+        self.z = standard_quantiles(self.expected_p, distribution)
+        self.clip = None if clip is None else (float(clip[0]), float(clip[1]))
+        self.channel = int(channel)
+        if not torch.cuda.is_available():
+            raise L.MimoHipError("UncertaintyEvaluator runs on an AMD GPU (mimo_eval_*); no GPU is visible")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._lib = L.load()
+        with torch.cuda.device(self.device):
+            self._z_dev = torch.from_numpy(self.z.astype(np.float32)).to(self.device)
+            self._pct_dev = torch.from_numpy(np.ascontiguousarray(self.percentiles)).to(self.device)
+            self._ws = torch.zeros(int(self._lib.mimo_eval_workspace_bytes()) // 8 + 1, dtype=torch.int64, device=self.device)
+            self._out = torch.empty(3 * self.percentiles.size + self.expected_p.size + 6, dtype=torch.float64,
+                                    device=self.device)
+        self._records = None  # int64 [capacity]: one record per pixel fed
+        self._used = 0
+
+    # ------------------------------------------------------------------ feeding
+    def reset(self) -> None:
+        self._ws.zero_()
+        self._used = 0
+
+    def _reserve(self, extra: int) -> None:
+        need = self._used + extra
+        cap = 0 if self._records is None else self._records.numel()
+        if need <= cap:
+            return
+        grown = torch.empty(max(need, 2 * cap, 1 << 20), dtype=torch.int64, device=self.device)
+        if self._used:
+            grown[: self._used].copy_(self._records[: self._used])  # device to device, on the current stream
+        self._records = grown
+
+    def update(self, mean, aleatoric_var, epistemic_var, label, mask=None) -> None:
+        """Device tensors [B,C,H,W] (mask [B,1,H,W] or [B,C,H,W]).  Enqueues one pass; returns without synchronising."""
+        if mean.dim() != 4:
+            raise ValueError("update expects [B,C,H,W] tensors")
+        b, c, h, w = mean.shape
+        if not 0 <= self.channel < c:
+            raise ValueError(f"channel {self.channel} of {c}")
+        ts = []
+        for name, t in (("mean", mean), ("aleatoric_var", aleatoric_var), ("epistemic_var", epistemic_var), ("label", label)):
+            if tuple(t.shape) != (b, c, h, w):
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {(b, c, h, w)}")
+            if not t.is_cuda:
+                raise L.MimoHipError(f"UncertaintyEvaluator.update: {name} is not on the GPU (there is no CPU path)")
+            ts.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        mc = 1
+        if mask is not None:
+            if mask.dim() != 4 or mask.shape[0] != b or mask.shape[1] not in (1, c) or tuple(mask.shape[2:]) != (h, w):
+                raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(b, 1, h, w)} or {(b, c, h, w)}")
+            mc = mask.shape[1]
+            mask = mask.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        hw = h * w
+        with torch.cuda.device(self.device):
+            self._reserve(b * hw)
+            lo, hi = self.clip if self.clip is not None else (0.0, 0.0)
+            L.check(self._lib.mimo_eval_accumulate(
+                ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(), L.ptr(mask) or None, b, c,
+                self.channel, mc, hw, int(self.clip is not None), lo, hi, self._z_dev.data_ptr(), self.z.size,
+                self._records.data_ptr() + 8 * self._used, self._ws.data_ptr(), L.current_stream()), "mimo_eval_accumulate")
+        self._used += b * hw
+
+    def update_from(self, ensemble, image, label, mask=None) -> None:
+        """Run an `EnsembleModule` on `image` and feed its `(mean, aleatoric_var, epistemic_var)` without leaving the
+        device (the module's `keep_on_device` is switched on for the call)."""
+        keep, raw = ensemble.keep_on_device, ensemble.return_raw_predictions
+        ensemble.keep_on_device, ensemble.return_raw_predictions = True, False
+        try:
+            mean, av, ev = ensemble(image)
+        finally:
+            ensemble.keep_on_device, ensemble.return_raw_predictions = keep, raw
+        self.update(mean, av, ev, label.to(mean.device), None if mask is None else mask.to(mean.device))
+
+    # ------------------------------------------------------------------ tables
+    def compute(self) -> dict:
+        p, k = self.percentiles.size, self.expected_p.size
+        if self._used == 0:
+            o = np.full(3 * p + k + 6, np.nan)
+            o[3 * p + k: 3 * p + k + 3] = 0.0
+        else:
+            with torch.cuda.device(self.device):
+                s = L.current_stream()
+                L.check(self._lib.mimo_eval_select(self._records.data_ptr(), self._used, self._pct_dev.data_ptr(), p,
+                                                   self._ws.data_ptr(), s), "mimo_eval_select")
+                L.check(self._lib.mimo_eval_interval_sums(self._records.data_ptr(), self._used, p, k, self._ws.data_ptr(),
+                                                          self._out.data_ptr(), s), "mimo_eval_interval_sums")
+                o = self._out.cpu().numpy()  # the one transfer (and the one synchronisation)
+        n, n_masked, n_nonfinite = (int(v) for v in o[3 * p + k: 3 * p + k + 3])
+        if n_nonfinite:
+            warnings.warn(f"UncertaintyEvaluator: {n_nonfinite} pixels with a non-finite value or a negative variance were "
+                          "skipped (the reference's tables would be NaN in every row)", RuntimeWarning, stacklevel=2)
+        return {
+            "precision_recall": {"percentile": self.percentiles.copy(), "mae": o[:p].copy(), "rmse": o[p: 2 * p].copy()},
+            "calibration": {"expected": self.expected_p.copy(), "observed": o[3 * p: 3 * p + k].copy()},
+            "cutoff_keys": o[2 * p: 3 * p].copy(),
+            "n": n, "n_masked": n_masked, "n_nonfinite": n_nonfinite,
+            "mae": float(o[3 * p + k + 3]), "mse": float(o[3 * p + k + 4]), "rmse": float(o[3 * p + k + 5]),
+        }
+
+    def write_csv(self, directory: str, tables: Optional[dict] = None) -> Tuple[str, str]:
+        return write_tables_csv(self.compute() if tables is None else tables, directory)

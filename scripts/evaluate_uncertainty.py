@@ -1,0 +1,152 @@
+"""Uncertainty evaluation of an ensemble on the GPU: precision_recall.csv + calibration.csv (the second half of the
+reference's scripts/test/test_nyuv2_depth.py / test_ndvi.py), with HIP-event timings of the device route and the time
+of the host route (the same tables from `.cpu()` copies: numpy argsort + 41 quantile sweeps) next to it.
+
+    python scripts/evaluate_uncertainty.py --synthetic 8 --result_dir out            # seeded maps, no network
+    python scripts/evaluate_uncertainty.py --synthetic_model --synthetic 2 --monte_carlo_steps 4 --result_dir out
+    python scripts/evaluate_uncertainty.py --model_checkpoint_paths a.ckpt b.ckpt --batch_dir batches/ --result_dir out
+
+--batch_dir: `*.npy` files holding one dict each ({"image": [B,C,H,W], "label": [B,1,H,W], optional "mask"}), saved with
+np.save(..., allow_pickle=True).  --synthetic N without a model feeds N seeded batches of (mean, aleatoric_var,
+epistemic_var, label) maps of --batch x 1 x --size x --size straight into the evaluator."""
+import argparse
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mimo.evaluation import UncertaintyEvaluator  # noqa: E402
+
+
+def seeded_maps(seed, b, size, device):
+    g = torch.Generator(device=device).manual_seed(seed)
+    shape = (b, 1, size, size)
+    label = torch.rand(shape, generator=g, device=device) * 0.8 + 0.1
+    a_std = torch.exp(torch.rand(shape, generator=g, device=device) * 2.3026 - 3.912)  # 0.02 .. 0.2
+    mean = label + a_std * torch.randn(shape, generator=g, device=device)
+    e_var = (0.3 * a_std * torch.randn(shape, generator=g, device=device)) ** 2
+    return mean, a_std ** 2, e_var, label
+
+
+def host_tables(batches, z, percentiles, clip=(0.0, 1.0)):
+    """the reference's recipe on host copies, in numpy: what the device route replaces (batches: mean, aleatoric_var,
+    epistemic_var, label, mask-or-None; masked pixels are dropped first)"""
+    keep = np.concatenate([np.ones(b[0][:, 0].numel(), bool) if b[4] is None else (b[4].cpu().numpy()[:, 0].reshape(-1) != 0)
+                           for b in batches])
+    mu, av, ev, y = (np.concatenate([b[k].cpu().numpy()[:, 0].reshape(-1) for b in batches])[keep] for k in range(4))
+    mu, y = np.clip(mu, *clip), np.clip(y, *clip)
+    err, a_std, c_std = np.abs(y - mu), np.sqrt(av), np.sqrt(av + ev)
+    e = err[np.argsort(-c_std, kind="stable")].astype(np.float64)
+    suf, suf2 = np.cumsum(e[::-1])[::-1], np.cumsum((e * e)[::-1])[::-1]
+    cut = (percentiles * e.size).astype(int)
+    mae, rmse = suf[cut] / (e.size - cut), np.sqrt(suf2[cut] / (e.size - cut))
+    s = a_std.astype(np.float64) / np.sqrt(2.0)
+    with np.errstate(invalid="ignore"):
+        obs = np.array([(y < mu + s * zk).mean() for zk in z])
+    return mae, rmse, obs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model_checkpoint_paths", nargs="*", default=[])
+    ap.add_argument("--synthetic_model", action="store_true", help="a seeded MIMO U-Net instead of checkpoints")
+    ap.add_argument("--monte_carlo_steps", type=int, default=0)
+    ap.add_argument("--batch_dir")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--distribution", default="norm", choices=["norm", "laplace"])
+    ap.add_argument("--result_dir", required=True)
+    ap.add_argument("--no_host_route", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+
+    ensemble = None
+    if args.model_checkpoint_paths or args.synthetic_model:
+        from mimo.models.ensemble import EnsembleModule
+        models = None
+        if args.synthetic_model:
+            from mimo.models.mimo_unet import MimoUnetModel
+            torch.manual_seed(0)
+            models = [MimoUnetModel(in_channels=3, out_channels=2, num_subnetworks=2, filter_base_count=8, center_dropout_rate=0.0,
+                                    final_dropout_rate=0.0, encoder_dropout_rate=0.1, core_dropout_rate=0.1,
+                                    decoder_dropout_rate=0.1, loss="laplace_nll", weight_decay=0.0, learning_rate=1e-3, seed=0,
+                                    loss_buffer_size=10, loss_buffer_temperature=0.3).cuda()]
+        ensemble = EnsembleModule(args.model_checkpoint_paths, monte_carlo_steps=args.monte_carlo_steps, models=models,
+                                  keep_on_device=True).to(dev)
+
+    ev = UncertaintyEvaluator(distribution=args.distribution)
+    kept, update_ms, masked = [], [], False
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed_update(maps, mask=None):
+        e0.record()
+        ev.update(*maps, mask=mask)
+        e1.record()
+        e1.synchronize()
+        update_ms.append(e0.elapsed_time(e1))
+        if not args.no_host_route:
+            kept.append(tuple(t[:, :1] for t in maps) + (None if mask is None else mask[:, :1],))
+
+    if ensemble is not None:
+        if args.batch_dir:
+            batches = [np.load(f, allow_pickle=True).item() for f in sorted(glob.glob(os.path.join(args.batch_dir, "*.npy")))]
+        else:
+            g = torch.Generator().manual_seed(1)
+            batches = [{"image": torch.rand(args.batch, 3, args.size, args.size, generator=g),
+                        "label": torch.rand(args.batch, 1, args.size, args.size, generator=g)} for _ in range(max(1, args.synthetic))]
+        for b in batches:
+            image, label = (torch.as_tensor(b[k]).to(dev) for k in ("image", "label"))
+            mask = torch.as_tensor(b["mask"]).to(dev) if b.get("mask") is not None else None
+            masked = masked or mask is not None
+            if args.no_host_route:
+                ev.update_from(ensemble, image, label, mask)  # the three-line form of INTEGRATION.md
+            else:  # the same two steps apart, to time the update alone and to keep the maps for the host route
+                timed_update(ensemble(image) + (label,), mask)
+    else:
+        if args.synthetic < 1:
+            ap.error("give checkpoints, --synthetic_model or --synthetic N")
+        ev.update(*seeded_maps(999, args.batch, args.size, dev))  # first call: allocations, code load
+        ev.reset()
+        for i in range(args.synthetic):
+            timed_update(seeded_maps(i, args.batch, args.size, dev))
+
+    ev.compute()  # first call
+    compute_ms = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        e0.record()
+        tables = ev.compute()
+        e1.record()
+        e1.synchronize()
+        compute_ms.append(e0.elapsed_time(e1))
+    ev.write_csv(args.result_dir, tables)
+
+    pixels = args.batch * args.size * args.size
+    res = {"n": tables["n"], "pixels_per_update": pixels, "compute_ms": [round(v, 3) for v in compute_ms], "mae": tables["mae"],
+           "rmse": tables["rmse"]}
+    if update_ms:
+        # HIP events around one update(): the accumulate pass AND its 70-workgroup fold launch.  Bytes of the pass: four
+        # fp32 maps in (five with a mask), one 8-byte record out.
+        res.update(update_ms_median=float(np.median(update_ms)), update_ms_min=float(np.min(update_ms)),
+                   bytes_per_pixel=28 if masked else 24)
+        res["update_GBps_at_min"] = res["bytes_per_pixel"] * pixels / (res["update_ms_min"] * 1e-3) / 1e9
+    if kept:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mae, rmse, obs = host_tables(kept, ev.z, ev.percentiles)
+        res["host_route_s"] = time.perf_counter() - t0
+        res["host_vs_device_mae_max_rel"] = float(np.nanmax(np.abs(mae - tables["precision_recall"]["mae"]) / mae))
+        res["host_vs_device_observed_max_abs"] = float(np.abs(obs - tables["calibration"]["observed"]).max())
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
