@@ -95,9 +95,14 @@ typedef struct mimo_config {
   float eps_min, eps_max;    /* clamp of the scale/variance, losses.py:42-45,127-130: 1e-5, 1e3 */
   int32_t device;            /* HIP device ordinal */
   int32_t precision;         /* mimo_precision: arithmetic of the 3x3 forward / data-gradient convolutions */
-  int32_t inference_only;    /* != 0: no buffers for a backward (pre-activations, activation gradients, dz /
-                              * weight-gradient scratch, data-gradient weights); mimo_forward then requires
-                              * training = 0 and no_grad = 1.  What torch.no_grad() + eval() means for memory. */
+  int32_t inference_only;    /* 0: full plan.  1 (or any value but 0 and 2): no buffers for a backward (pre-activations,
+                              * activation gradients, dz / weight-gradient scratch, data-gradient weights); mimo_forward then
+                              * requires training = 0 and no_grad = 1.  What torch.no_grad() + eval() means for memory.
+                              * 2: input gradient only — what mimo_input_gradient needs (pre-activations, activation
+                              * gradients, one dz buffer, data-gradient weights) and nothing only a weight gradient needs
+                              * (slabs, split copies of dz, max |dz| slots, further dz buffers, the side stream);
+                              * mimo_forward requires training = 0, mimo_plan_bind accepts grads = NULL, mimo_backward* fail
+                              * with MIMO_ERR_STATE.  fp32 and split16 only. */
   float center_dropout_rate, final_dropout_rate; /* element-wise nn.Dropout (model.py:213, :277-281): the rates the
                               * in-engine generator uses for those sites (mimo_forward_args.rng_sites) */
   int32_t norm_kind, act_kind, up_kind; /* mimo_norm_kind / mimo_act_kind / mimo_up_kind: 0 = the reference's blocks */
@@ -121,7 +126,7 @@ int mimo_plan_tensor_info(const mimo_plan* plan, int index, char* name, int name
 int64_t mimo_plan_param_floats(const mimo_plan* plan);
 int64_t mimo_plan_buffer_floats(const mimo_plan* plan);
 
-/* Bind the torch-owned flat storage.  grads may be NULL for inference-only plans. */
+/* Bind the torch-owned flat storage.  grads may be NULL for inference-only and input-gradient-only plans. */
 int mimo_plan_bind(mimo_plan* plan, float* params, float* grads, float* bn_buffers);
 
 /* ---- forward: replaces MimoUNet.forward (model.py:94-117) ------------------------------
@@ -226,6 +231,29 @@ int mimo_backward_stage(mimo_plan* plan, int stage, const float* dout, const flo
 int mimo_backward_stage_async(mimo_plan* plan, int stage, const float* dout, const float* dloss, float* dx,
                               mimo_stream stream, mimo_stream* ready_stream);
 int64_t mimo_plan_encoder_param_floats(const mimo_plan* plan);
+
+/* ---- input gradient only: replaces, for an evaluation, `loss.backward(); data_grad = images.grad.data`
+ * (scripts/test/test_nyuv2_depth.py:41-55) — autograd through the whole ensemble member for the sake of d loss / d image.
+ * Valid after a mimo_forward with training = 0, no_grad = 0 and perm = NULL (and, if dloss is given, a mimo_loss_forward);
+ * dout / dloss as in mimo_backward.  Walks the 8 stages of mimo_backward with the same data-gradient and BatchNorm-backward
+ * kernels — after an eval-mode forward the BatchNorm backward is dz = scale * relu'(.) * dy, no per-channel sums, one pass —
+ * and launches no weight gradient, no reduction and nothing on the side stream; it writes no byte of the bound grads buffer
+ * (which may be NULL) or of the BatchNorm buffers.  The data-gradient weight images are packed once per param_version.
+ * dimage [N,Ci,H,W]: gradient w.r.t. the image that repeat_subnetworks (utils.py:51-61) broadcast to the S encoders = the sum
+ * of their first-layer data gradients, added in the fixed order s = S-1, S-2, ..., 0 with fp32 adds; accumulate != 0 adds
+ * that sum, term by term in the same order, to what dimage holds (the members of an ensemble), 0 overwrites.
+ * Bit-identical to mimo_backward's dx summed in that order.  Works on full plans and on inference_only = 2 plans; fp32 and
+ * split16 precision (MIMO_ERR_INVALID otherwise). */
+int mimo_input_gradient(mimo_plan* plan, const float* dout, const float* dloss, float* dimage, int accumulate,
+                        mimo_stream stream);
+
+/* ---- FGSM: replaces fgsm_attack (scripts/test/test_nyuv2_depth.py:16-24) for all perturbation sizes of a sweep at once.
+ * out[k][i] = clamp(image[i] + eps[k] * sign(dimage[i]), lo, hi), i < elems, k < K, with torch.sign's and torch.clamp's
+ * arithmetic for every non-NaN gradient (sign(0) = 0; eps = 0 still clamps).  A NaN gradient or image pixel gives a NaN
+ * output pixel (torch.sign itself would map a NaN gradient to 0 and hide it).  eps: HOST array [K], eps and K by value into the launch.
+ * image and dimage are read once for all K outputs (8 B read + 4 K B written per element).  Asynchronous on the stream. */
+int mimo_fgsm_perturb(const float* image, const float* dimage, int64_t elems, const float* eps, int K, float lo, float hi,
+                      float* out, mimo_stream stream);
 
 /* ---- measurement (no reference counterpart): per-kernel-class device time from HIP events
  * recorded on the launch stream around every 3x3 convolution launch, with the ALGORITHMIC

@@ -1,0 +1,142 @@
+"""FGSM robustness sweep of an `EnsembleModule`, on the GPU: the first half of the reference's
+``scripts/test/test_nyuv2_depth.py`` (``fgsm_attack`` :16-24, ``make_predictions`` :26-90, driven per noise level at
+:190-205).
+
+The reference, per noise level, runs the ensemble under autograd, back-propagates the NLL through every member to the
+image, forms ``clamp(image + eps * sign(grad), 0, 1)`` and predicts again.  In eval mode the gradient is taken at the clean
+image and does not depend on eps, so here ONE gradient serves the whole sweep:
+
+* per member one eval-mode forward with its graph kept, the loss, and `mimo_input_gradient` — the data-gradient chain
+  only (no weight gradient, no reduction, no `.grad` write), accumulated over the members into one image gradient;
+* one `mimo_fgsm_perturb` launch that reads image and gradient once and writes the perturbed image of every eps;
+* the ordinary no-grad ensemble forward per eps.
+
+    sweep = fgsm_sweep(ensemble, image, label, (0.0, 0.02, 0.04))     # {eps: (mean, aleatoric_var, epistemic_var)}
+
+    rob = RobustnessEvaluator()                                        # the two tables per noise level
+    for batch in loader:
+        rob.update_from(ensemble, batch["image"].cuda(), batch["label"].cuda())
+    rob.write_csv(result_dir, "nyuv2")
+
+MC-dropout ensembles are rejected: the reference draws fresh dropout masks in each of its three forwards (clean, backward,
+perturbed), so there is no gradient "at the same network" to be in parity with.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+
+from .evaluation import UncertaintyEvaluator, write_tables_csv
+
+DEFAULT_EPSILONS = (0.0, 0.02, 0.04)  # test_nyuv2_depth.py:192
+
+
+def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
+    """Everything that can be refused is refused here, before anything touches the GPU."""
+    if getattr(ensemble, "monte_carlo_steps", 0) > 0:
+        raise NotImplementedError("fgsm_sweep: MC-dropout ensembles (monte_carlo_steps > 0) are not supported: the reference "
+                                  "draws fresh dropout masks in each of its forwards, there is nothing to be in parity with")
+    from .models.mimo_unet import MimoUnetModel
+    models = list(getattr(ensemble, "models", []))
+    if not models:
+        raise ValueError("fgsm_sweep: the ensemble has no members")
+    for m in models:
+        if not isinstance(m, MimoUnetModel):
+            raise NotImplementedError(f"fgsm_sweep: members must be MimoUnetModel (Laplace / Gaussian NLL heads), not "
+                                      f"{type(m).__name__}: the evidential model is not supported")
+    eps = tuple(float(e) for e in epsilons)
+    if not eps:
+        raise ValueError("fgsm_sweep: no epsilons")
+    if any(not e >= 0.0 for e in eps):
+        raise NotImplementedError(f"fgsm_sweep: negative (or NaN) epsilons are not supported: {eps}")
+    if len(set(eps)) != len(eps):
+        raise ValueError(f"fgsm_sweep: duplicate epsilons {eps}")
+    return eps
+
+
+def image_gradient(ensemble, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d loss / d image [B,C,H,W] of `loss_fn(y_pred, log_param, labels)` as the reference's script forms it
+    (test_nyuv2_depth.py:44-55): the mean NLL over the concatenated subnetwork axis of ALL members, i.e. a weight of
+    1 / S_total on every subnetwork's mean loss.  Members are summed in list order (member 0 assigns, the others add)."""
+    _validate(ensemble, (0.0,))
+    if not image.is_cuda:
+        from . import _lib as L
+        raise L.MimoHipError("fgsm_sweep runs on an AMD GPU through libmimo_hip.so; move the ensemble and its inputs to cuda")
+    s_total = ensemble.num_subnetworks
+    image = image.detach().contiguous().float()
+    label = label.detach().to(image.device)
+    mask = None if mask is None else mask.detach().to(image.device)
+    dimage = torch.empty_like(image)
+    with torch.no_grad():
+        for i, model in enumerate(ensemble.models):
+            dloss = torch.full((model.num_subnetworks,), 1.0 / s_total, device=image.device, dtype=torch.float32)
+            model.model.image_gradient(image, label, mask, dloss, dimage, accumulate=i > 0)
+    return dimage
+
+
+def fgsm_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Sequence[float] = DEFAULT_EPSILONS,
+               mask: Optional[torch.Tensor] = None, clip: Optional[Tuple[float, float]] = (0.0, 1.0),
+               return_perturbed: bool = False) -> Dict[float, tuple]:
+    """{eps: (mean, aleatoric_var, epistemic_var)} [B,Ct,H,W] on the device, for the image attacked with each eps
+    (eps = 0 is the clamped clean image, as in the reference).  image [B,C,H,W], label [B,Ct,H,W], mask [B,1,H,W] or None
+    (weights the loss the gradient is taken of).  clip: the range the perturbed image is clamped to; None = no clamp.
+    return_perturbed: the tuples get the perturbed image [B,C,H,W] as a fourth entry.
+    The members' `.grad`, BatchNorm buffers and train / eval flags are left as they were."""
+    eps = _validate(ensemble, epsilons)
+    from .engine import fgsm_perturb
+    dimage = image_gradient(ensemble, image, label, mask)
+    lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
+    perturbed = fgsm_perturb(image.detach(), dimage, eps, lo, hi)
+    keep, raw = ensemble.keep_on_device, ensemble.return_raw_predictions
+    ensemble.keep_on_device, ensemble.return_raw_predictions = True, False
+    out = {}
+    try:
+        for k, e in enumerate(eps):
+            res = tuple(ensemble(perturbed[k]))
+            out[e] = res + (perturbed[k],) if return_perturbed else res
+    finally:
+        ensemble.keep_on_device, ensemble.return_raw_predictions = keep, raw
+    return out
+
+
+class RobustnessEvaluator:
+    """One `UncertaintyEvaluator` per noise level, fed by `fgsm_sweep`: the sparsification and calibration tables of
+    test_nyuv2_depth.py:215-234 for every eps of its sweep (:192).  `evaluator_kwargs` go to every UncertaintyEvaluator."""
+
+    def __init__(self, epsilons: Sequence[float] = DEFAULT_EPSILONS, **evaluator_kwargs):
+        self.epsilons = tuple(float(e) for e in epsilons)
+        if not self.epsilons or any(not e >= 0.0 for e in self.epsilons):
+            raise NotImplementedError(f"RobustnessEvaluator: epsilons must be non-negative, got {self.epsilons}")
+        if len(set(self.epsilons)) != len(self.epsilons):
+            raise ValueError(f"RobustnessEvaluator: duplicate epsilons {self.epsilons}")
+        self.evaluators = {e: UncertaintyEvaluator(**evaluator_kwargs) for e in self.epsilons}
+
+    def reset(self) -> None:
+        for ev in self.evaluators.values():
+            ev.reset()
+
+    def update_from(self, ensemble, image, label, mask=None) -> None:
+        sweep = fgsm_sweep(ensemble, image, label, self.epsilons, mask=mask)
+        for e, (mean, av, ev) in sweep.items():
+            self.evaluators[e].update(mean, av, ev, label.to(mean.device), None if mask is None else mask.to(mean.device))
+
+    def compute(self) -> Dict[float, dict]:
+        return {e: ev.compute() for e, ev in self.evaluators.items()}
+
+    def write_csv(self, directory: str, name: str, tables: Optional[Dict[float, dict]] = None):
+        """`{name}_{eps}_precision_recall.csv` and `{name}_{eps}_calibration.csv` per noise level (test_nyuv2_depth.py:229,234;
+        eps formatted as Python prints the float: 0.0, 0.02, 0.04)."""
+        tables = self.compute() if tables is None else tables
+        os.makedirs(directory, exist_ok=True)
+        paths = {}
+        for e in self.epsilons:
+            tmp = os.path.join(directory, f".{name}_{e}")
+            a, b = write_tables_csv(tables[e], tmp)
+            pa, pb = (os.path.join(directory, f"{name}_{e}_{kind}.csv") for kind in ("precision_recall", "calibration"))
+            os.replace(a, pa)
+            os.replace(b, pb)
+            os.rmdir(tmp)
+            paths[e] = (pa, pb)
+        return paths

@@ -45,6 +45,11 @@ int pack_input_launch(const float* x, int64_t stride_n, int64_t stride_s, const 
 // dx[n][s][c][y][x] = fold(dxpad)[n][y][x][c]
 int unpack_dx_launch(const void* dxpad, int dt, int ldp, int N, int S, int s, int C, int H, int W, float* dx, hipStream_t st);
 
+// dimage[n][c][y][x] (=|+=) fold(dxpad)[n][y][x][c]: the first-layer data gradient of ONE encoder added into the gradient of
+// the image that repeat_subnetworks broadcast (utils.py:51-61) — mimo_input_gradient launches it once per subnetwork, in
+// the order s = S-1 ... 0, instead of S unpack_dx launches and a sum over the subnetwork axis (fp32 storage)
+int fold_image_grad_launch(const float* dxpad, int ldp, int N, int C, int H, int W, float* dimage, int accumulate, hipStream_t st);
+
 // ---- BatchNorm + ReLU (+ Dropout2d) forward ---------------------------------------------
 // training: sums = rowsum of the conv epilogue partials ([chunks][2*cout_pad]).
 int bn_fwd_finalize_launch(const double* sums, int chunks, int cout_pad, int C, int Cp, int64_t count,

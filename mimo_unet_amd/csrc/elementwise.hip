@@ -434,6 +434,34 @@ int unpack_dx_launch(const void* dxpad, int dt, int ldp, int N, int S, int s, in
   return MIMO_OK;
 }
 
+// One thread per pixel: one folded float4 read of the padded-domain gradient (the image has at most 4 padded channels per
+// quad), C coalesced plane accesses of the NCHW image gradient.  ldp is a multiple of 4 (padded channels).
+__global__ void fold_image_grad_kernel(const float* __restrict__ dxpad, int ldp, int N, int C, int H, int W,
+                                       float* __restrict__ dimage, int accumulate) {
+  const int64_t HW = (int64_t)H * W, total = (int64_t)N * HW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int n = (int)(i / HW);
+    const int yx = (int)(i - (int64_t)n * HW);
+    const int y = yx / W, x = yx - y * W;
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      const float4 v = fold_read(dxpad, ldp, n, y, x, H, W, c0);
+      const float vv[4] = {v.x, v.y, v.z, v.w};
+      for (int j = 0; j < 4 && c0 + j < C; ++j) {
+        float* d = dimage + ((int64_t)n * C + c0 + j) * HW + yx;
+        *d = accumulate ? *d + vv[j] : vv[j];
+      }
+    }
+  }
+}
+
+int fold_image_grad_launch(const float* dxpad, int ldp, int N, int C, int H, int W, float* dimage, int accumulate, hipStream_t st) {
+  const int64_t total = (int64_t)N * H * W;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
+  hipLaunchKernelGGL(fold_image_grad_kernel, dim3(blocks), dim3(256), 0, st, dxpad, ldp, N, C, H, W, dimage, accumulate);
+  MIMO_KERNEL_CHECK();
+  return MIMO_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // BatchNorm statistics -> scale/shift
 // ---------------------------------------------------------------------------------------

@@ -369,6 +369,14 @@ struct mimo_plan {
   bool derived_dgrad = false;     // ... including the data-gradient weight copies
   bool need_derive = true;        // per-call: (re)pack weights and eval BN constants in this forward
   int64_t encoder_param_floats = 0;
+  // mimo_input_gradient (evaluation-grade backward: the data-gradient chain only).  ig_only is set while it walks the stages:
+  // convbn_backward then launches the BatchNorm-backward apply pass and the data gradient and nothing else.
+  bool ig_only = false;
+  float* s_zero = nullptr;        // max cout_p zeros, never written: c1 / c2 of the apply pass after an eval-mode forward
+  size_t cap_cout = 0;
+  int64_t dgrad_version = -1;     // derived_version the data-gradient weight images were packed at by mimo_input_gradient (-1: none)
+  float* ig_dimage = nullptr;     // per call: the image gradient [N,Ci,H,W] the encoders' first-layer data gradients are folded into
+  bool ig_accumulate = false;     // ... the first fold adds to what is there
   float* out = nullptr;
   const float *label = nullptr, *lmask = nullptr;
   std::vector<const float*> elem_masks;  // [1 + S] element-wise dropout multipliers of the last forward (or empty)
@@ -462,7 +470,8 @@ struct mimo_plan {
     L.off_beta = add_tensor(L.bn_name + ".bias", {Cout}, 0);
     L.off_rm = add_tensor(L.bn_name + ".running_mean", {Cout}, 1);
     L.off_rv = add_tensor(L.bn_name + ".running_var", {Cout}, 1);
-    const bool train_bufs = !cfg.inference_only;  // everything only a backward reads or writes
+    const bool train_bufs = cfg.inference_only != 1;  // everything only a backward reads or writes
+    const bool wgrad_bufs = cfg.inference_only == 0;  // ... only a weight gradient (inference_only = 2: input gradient only)
     MIMO_TRY(dalloc(&L.wf, (size_t)9 * L.cout_pad * L.cin_p));
     if (train_bufs) MIMO_TRY(dalloc(&L.wd, (size_t)9 * L.dg_rows * L.cout_p));
     MIMO_TRY(dalloc(&L.bias_p, L.cout_pad));
@@ -475,13 +484,13 @@ struct mimo_plan {
       bool ident = true;  // (the packed image: logical channel i in padded channel i)
       for (int i = 0; i < Cin; ++i) ident = ident && i < (int)in_chmap.size() && in_chmap[i] == i;
       L.thin = !L.fwd_split && ident && conv3x3_thin_ok(Cin, L.cout_p);
-      if (L.thin && train_bufs) cap_slab = std::max(cap_slab, wgrad_thin_scratch(Cin, L.cout_p));
+      if (L.thin && wgrad_bufs) cap_slab = std::max(cap_slab, wgrad_thin_scratch(Cin, L.cout_p));
     }
     if (L.wg_split && !L.dg_split) any_mixed_dz = true;
     // two fp16 MFMAs per product: not for the image convolution (raw inputs need not fit fp16: its forward runs on the fp32
     // kernels), and only while the launch that writes dz has a max |dz| slot for each of its workgroups
     // (<= 2048 x ceil(Cp / 1024); wider layers keep the three-MFMA arithmetic)
-    L.wg_np2 = cfg.precision == MIMO_PREC_SPLIT16 && L.wg_split && train_bufs && L.fwd_split && wgrad_split_has_np2(L.cin_p, L.cout_p) &&
+    L.wg_np2 = cfg.precision == MIMO_PREC_SPLIT16 && L.wg_split && wgrad_bufs && L.fwd_split && wgrad_split_has_np2(L.cin_p, L.cout_p) &&
                2048 * ceil_div(L.cout_p / 4, 256) <= kDzMaxSlots;
     if (cfg.precision == MIMO_PREC_SPLIT16 || mixed) {  // decomposition per layer and direction (sched::wide_config)
       if (L.fwd_split) L.fwd_wide = conv3x3_wide_rows(fwd_mode(), n, L.cin_p, L.cout_p, h, w);
@@ -534,6 +543,7 @@ struct mimo_plan {
     const size_t padv = (size_t)n * (h + 2) * (w + 2) * L.cin_p;
     cap_act = std::max(cap_act, act);
     cap_pad = std::max(cap_pad, padv);
+    cap_cout = std::max(cap_cout, (size_t)L.cout_p);
     // slabs + the reduction's group-sum levels (geometric: < splits/15 extra slabs)
     cap_slab = std::max(cap_slab, (size_t)(L.wg_splits + L.wg_splits / 8 + 2) * 9 * L.wg_cin_pad * L.wg_cout_pad);
     const size_t stat_rows = std::max(conv3x3_stat_rows(n, h, w), conv3x3_ws_stat_rows(n, h, w));
@@ -571,7 +581,7 @@ struct mimo_plan {
       o.ldda = out_ldda;
     } else {
       MIMO_TRY(alloc_act(&o.a, (size_t)N * h * w * o.Cp, st));
-      if (!cfg.inference_only) MIMO_TRY(alloc_act(&o.da, (size_t)N * h * w * o.Cp, st));
+      if (cfg.inference_only != 1) MIMO_TRY(alloc_act(&o.da, (size_t)N * h * w * o.Cp, st));
       o.ld = o.ldda = o.Cp;
     }
     dc->c1.a = dc->mid;
@@ -624,7 +634,7 @@ struct mimo_plan {
     MIMO_TRY(alloc_act(&dc->in_buf, (size_t)N * h * w * in_cp, kind == IN_IMAGE ? ST_F32 : st));  // the packed image stays fp32
     // the skip slice of the data gradient stays in this block's own buffer until the pool backward of the skip tensor folds
     // it in (every skip tensor is pooled by a Down block)
-    if (kind == IN_UPCAT && !cfg.inference_only)
+    if (kind == IN_UPCAT && cfg.inference_only != 1)
       MIMO_TRY(alloc_act(&dc->dxpad_own, (size_t)N * (h + 2) * (w + 2) * in_cp, st));
     // the pooled gradient stays in this block's own buffer until the producers' BatchNorm backward has routed it (GS_POOL)
     if (kind == IN_POOL && fuse_bwd_pool) MIMO_TRY(alloc_act(&dc->dxpad_own, (size_t)N * (h + 2) * (w + 2) * in_cp, st));
@@ -641,13 +651,20 @@ struct mimo_plan {
   }
 
   int build() {
+    // 0: full plan; 2: input gradient only (mimo_input_gradient); any other value: 1, no backward at all
+    if (cfg.inference_only != 0 && cfg.inference_only != 2) cfg.inference_only = 1;
+    if (cfg.inference_only == 2 && cfg.precision != MIMO_PREC_FP32 && cfg.precision != MIMO_PREC_SPLIT16) {
+      set_error("inference_only = 2 (input gradient only) exists for the fp32 and split16 precisions, not for precision %d", cfg.precision);
+      return MIMO_ERR_INVALID;
+    }
     mixed = cfg.precision == MIMO_PREC_BF16_MIXED || cfg.precision == MIMO_PREC_FP16_MIXED;
     f16 = cfg.precision == MIMO_PREC_FP16_MIXED;
     st = !mixed ? ST_F32 : f16 ? ST_F16 : ST_BF16;
     esz = store_bytes(st);
     {
       const int v = getenv("MIMO_FUSE_BWD_SRC") ? atoi(getenv("MIMO_FUSE_BWD_SRC")) : 1;
-      fuse_bwd_src = !mixed && !cfg.inference_only && v != 0;
+      // (an input-gradient-only plan routes the gradients exactly as a full plan does: the same bits)
+      fuse_bwd_src = !mixed && cfg.inference_only != 1 && v != 0;
       fuse_bwd_pool = fuse_bwd_src && v != 3;
       fuse_bwd_head = fuse_bwd_src && v != 2;
     }
@@ -707,7 +724,7 @@ struct mimo_plan {
     x2cat.Cp = c2p * S;
     x2cat.ld = x2cat.ldda = x2cat.Cp;
     MIMO_TRY(alloc_act(&x2cat.a, (size_t)N * H2 * W2 * x2cat.Cp, st));
-    if (!cfg.inference_only) MIMO_TRY(alloc_act(&x2cat.da, (size_t)N * H2 * W2 * x2cat.Cp, st));
+    if (cfg.inference_only != 1) MIMO_TRY(alloc_act(&x2cat.da, (size_t)N * H2 * W2 * x2cat.Cp, st));
     x2cat.chmap.assign(x2cat.Cp, -1);
     for (int s = 0; s < S; ++s)
       for (int c = 0; c < 2 * f; ++c) x2cat.chmap[s * c2p + c] = s * 2 * f + c;
@@ -801,7 +818,9 @@ struct mimo_plan {
     const int fp = pad_channels(f);
     cap_partial = std::max(cap_partial, (size_t)kEwMaxBlocks * (Co * fp + Co));
     cap_sums = std::max(cap_sums, (size_t)kMaxChunks * 2 * round_up(Co * fp + Co, 64));
-    if (cfg.inference_only) cap_act = cap_pad = cap_slab = 1;  // backward scratch: never touched
+    if (cfg.inference_only == 1) cap_act = cap_pad = 1;  // backward scratch: never touched
+    if (cfg.inference_only) cap_slab = 1;               // weight-gradient slabs
+    if (cfg.inference_only != 1) MIMO_TRY(dalloc(&s_zero, cap_cout));
     MIMO_TRY(alloc_act(&s_dz, cap_act, st));
     {
       const char* we = getenv("MIMO_WGRAD_STREAM");
@@ -814,7 +833,7 @@ struct mimo_plan {
       for (int i = 0; i < kDzBufs; ++i) s_dz2[i] = s_dz;
       if (!cfg.inference_only)
         for (int i = 0; i < kDzBufs; ++i) MIMO_TRY(dalloc(&s_dzmax2[i], kDzMaxSlots));
-      if (any_mixed_dz) {
+      if (any_mixed_dz && !cfg.inference_only) {  // (read by weight gradients only)
         MIMO_TRY(dalloc(&s_dzs2[0], cap_act));
         for (int i = 1; i < kDzBufs; ++i) s_dzs2[i] = s_dzs2[0];
         if (wg_async)
@@ -847,7 +866,7 @@ struct mimo_plan {
     MIMO_TRY(dalloc(&s_wslab, cap_slab));
     if (cap_kpart) MIMO_TRY(dalloc(&s_kpart, cap_kpart));
     MIMO_TRY(dalloc(&s_partial, cap_partial));
-    if (fuse_bwd_src) MIMO_TRY(dalloc(&s_headpart, (size_t)kBnReduceMaxBlocks * (2 * pad_channels(f) + 2)));
+    if (fuse_bwd_src && !cfg.inference_only) MIMO_TRY(dalloc(&s_headpart, (size_t)kBnReduceMaxBlocks * (2 * pad_channels(f) + 2)));
     MIMO_TRY(dalloc(&s_sums, cap_sums));
     MIMO_TRY(dalloc(&s_tickets, kColsumMaxGroups));
     MIMO_TRY(dalloc(&s_losspart, (size_t)S * 512));
@@ -907,7 +926,7 @@ struct mimo_plan {
           dg.push_back(d);
         }
       n_fwd_jobs = (int)jobs.size();
-      if (!cfg.inference_only) jobs.insert(jobs.end(), dg.begin(), dg.end());
+      if (cfg.inference_only != 1) jobs.insert(jobs.end(), dg.begin(), dg.end());
       n_all_jobs = (int)jobs.size();
       for (auto& j : jobs) pack_max_total = std::max(pack_max_total, j.total);
       MIMO_TRY(dalloc(&pack_jobs, jobs.size()));
@@ -1099,8 +1118,12 @@ struct mimo_plan {
       set_error("mimo_forward: null argument");
       return MIMO_ERR_INVALID;
     }
-    if (cfg.inference_only && (args->training || !args->no_grad)) {
+    if (cfg.inference_only == 1 && (args->training || !args->no_grad)) {
       set_error("mimo_forward: inference-only plan (mimo_config.inference_only) needs training = 0 and no_grad = 1");
+      return MIMO_ERR_STATE;
+    }
+    if (cfg.inference_only == 2 && args->training) {
+      set_error("mimo_forward: input-gradient-only plan (mimo_config.inference_only = 2) needs training = 0");
       return MIMO_ERR_STATE;
     }
     // ---- in-engine dropout: draw the Dropout2d multipliers of the flagged sites, note the element-wise ones ----
@@ -1343,8 +1366,57 @@ struct mimo_plan {
   // gradient arriving at an activation: first writer assigns, later writers accumulate
   static int acc_flag(Act* t) { return t->grad_writes++ > 0 ? 1 : 0; }
 
+  // data gradient of layer L on the reflect-padded domain: dxpad_out [N,H+2,W+2,cin_p] from dz
+  int dgrad_conv(ConvBN& L, const float* dz, float* dxpad_out, hipStream_t st) {
+    const int64_t P = (int64_t)L.N * L.H * L.W;
+    ConvLaunch a;
+    a.x = dz;
+    a.y = dxpad_out;
+    a.w = L.wd;
+    a.bias = nullptr;
+    a.stats = nullptr;
+    a.N = L.N;
+    a.Hi = L.H;
+    a.Wi = L.W;
+    a.ldx = L.cout_p;
+    a.cin_p = L.cout_p;
+    a.Ho = L.H + 2;
+    a.Wo = L.W + 2;
+    a.ldy = L.cin_p;
+    a.cout_pad = L.dg_rows;
+    a.cout_store = L.cin_p;
+    a.off = 2;
+    a.wpk = L.wd16;
+    a.pair = (L.dg_split && !L.dg_wide) ? conv3x3_pair_tail(dgrad_mode(), L.cout_p, L.H + 2, L.W + 2) : 0;
+    a.wide = L.dg_wide;
+    int pr = prof_begin(MIMO_PROF_CONV_DGRAD, st);
+    if (L.dg_split)
+      MIMO_TRY(conv3x3_bf16x3_launch_k(a, dgrad_mode(), nullptr, st, s_kpart, cap_kpart));
+    else
+      MIMO_TRY(conv3x3_launch(a, nullptr, st));
+    prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
+    return MIMO_OK;
+  }
+
+  // mimo_input_gradient's form of convbn_backward: after an eval-mode forward BatchNorm is the fixed affine map of its running
+  // statistics, so its backward is dz = scale * relu'(.) * dy — bn_bwd_apply_kernel with c1 = c2 = 0 (the constant zero vector
+  // s_zero; mimo_backward's eval branch reaches the same zeros through the reduction pass and bn_bwd_stats_kernel, and the same
+  // bits).  No reduction, no column sums, no max |dz| slots, no event, nothing written outside the plan's scratch.
+  int convbn_input_grad(ConvBN& L, const GradSrc& src, const float* mask, float* dxpad_out, hipStream_t st) {
+    const int64_t P = (int64_t)L.N * L.H * L.W;
+    const double src_b = src.kind == GS_POOL ? (1.0 + (src.skip ? 4.0 : 0.0)) : src.kind == GS_HEAD ? 0.5 : 4.0;
+    float* dz = s_dz2[0];
+    int rows = 0;
+    const int pr = prof_begin(MIMO_PROF_BN_BWD_APPLY, st);
+    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, s_zero,
+                                 s_zero, L.cout_p, L.N, L.H, L.W, dz, (L.dg_split && !mixed) ? 1 : 0, nullptr, &rows, st));
+    prof_end(pr, 0.0, (8.0 + src_b) * (double)P * L.cout_p, st);
+    return dgrad_conv(L, dz, dxpad_out, st);
+  }
+
   // `src`: where the gradient arriving at L's activation comes from (GradSrc, elementwise.h)
   int convbn_backward(ConvBN& L, const GradSrc& src, const float* mask, bool need_dgrad, float* dxpad_out, hipStream_t st) {
+    if (ig_only) return need_dgrad ? convbn_input_grad(L, src, mask, dxpad_out, st) : MIMO_OK;
     int rows = 0;
     const int64_t P = (int64_t)L.N * L.H * L.W;
     // algorithmic bytes of the source per pixel and channel (z and dz are counted below): the pooled gradient is a quarter
@@ -1403,34 +1475,7 @@ struct mimo_plan {
     // conv bias gradient: exactly zero in front of a training-mode BatchNorm (written by bn_bwd_stats above);
     // a real column sum of dz only after an eval-mode forward (running statistics: dz = scale * dy)
     if (!fwd_training) MIMO_TRY(colsum_vec_launch(s_partial, rows, L.cout_p, L.Cout, grads + L.off_b, colsum(), st));
-    if (need_dgrad) {
-      ConvLaunch a;
-      a.x = dz;
-      a.y = dxpad_out;
-      a.w = L.wd;
-      a.bias = nullptr;
-      a.stats = nullptr;
-      a.N = L.N;
-      a.Hi = L.H;
-      a.Wi = L.W;
-      a.ldx = L.cout_p;
-      a.cin_p = L.cout_p;
-      a.Ho = L.H + 2;
-      a.Wo = L.W + 2;
-      a.ldy = L.cin_p;
-      a.cout_pad = L.dg_rows;
-      a.cout_store = L.cin_p;
-      a.off = 2;
-      a.wpk = L.wd16;
-      a.pair = (L.dg_split && !L.dg_wide) ? conv3x3_pair_tail(dgrad_mode(), L.cout_p, L.H + 2, L.W + 2) : 0;
-      a.wide = L.dg_wide;
-      pr = prof_begin(MIMO_PROF_CONV_DGRAD, st);
-      if (L.dg_split)
-        MIMO_TRY(conv3x3_bf16x3_launch_k(a, dgrad_mode(), nullptr, st, s_kpart, cap_kpart));
-      else
-        MIMO_TRY(conv3x3_launch(a, nullptr, st));
-      prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
-    }
+    if (need_dgrad) MIMO_TRY(dgrad_conv(L, dz, dxpad_out, st));
     hipStream_t ws = st;
     if (async) {
       MIMO_HIP_CHECK(hipStreamWaitEvent(wg_stream, ev_dz[b], 0));  // (a wait refers to the record made just above)
@@ -1582,6 +1627,10 @@ struct mimo_plan {
       set_error("mimo_backward: call mimo_forward first");
       return MIMO_ERR_STATE;
     }
+    if (cfg.inference_only == 2) {
+      set_error("mimo_backward: input-gradient-only plan (mimo_config.inference_only = 2): only mimo_input_gradient runs on it");
+      return MIMO_ERR_STATE;
+    }
     if (!grads) {
       set_error("mimo_backward: gradient buffer not bound");
       return MIMO_ERR_STATE;
@@ -1688,7 +1737,7 @@ struct mimo_plan {
         x2cat.grad_writes = 0;
         x2cat.skipgrad = nullptr;
         x2cat.poolgrad = nullptr;
-        if (!fwd_training) {  // eval-mode forward skipped the dgrad weight packing
+        if (!fwd_training && !ig_only) {  // eval-mode forward skipped the dgrad weight packing
           MIMO_TRY(pack_all(true, st));
         }
         const int fp = pad_channels(f);
@@ -1704,6 +1753,7 @@ struct mimo_plan {
             hs.head = HeadGrad{params + heads[s].off_w, f, Co, N, S, s, H * W, out, dout, dloss, label, lmask, lperm, cfg.loss_kind,
                                cfg.eps_min, cfg.eps_max, 1.f / (float)((double)N * (Co / 2) * H * W), s_headpart};
             MIMO_TRY(dc_backward(dc, true, st, &hs));
+            if (ig_only) continue;  // (no head weight / bias gradient)
             // (the head's partial rows: one per workgroup of that reduction)
             MIMO_TRY(head_bwd_stats_launch(s_headpart, head_rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, colsum(), st));
             continue;
@@ -1717,7 +1767,8 @@ struct mimo_plan {
                                    out, dout, dloss, label, lmask, lperm, cfg.loss_kind, cfg.eps_min, cfg.eps_max, dc->out.da,
                                    s_partial, &rows, st, oz ? o.z_scale : nullptr, oz ? o.z_shift : nullptr));
           prof_end(pr, 0.0, 4.0 * (double)N * H * W * (2.0 * fp + Co + Co / 2), st);
-          MIMO_TRY(head_bwd_stats_launch(s_partial, rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, colsum(), st));
+          if (!ig_only)
+            MIMO_TRY(head_bwd_stats_launch(s_partial, rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, colsum(), st));
           if (em || elem_rng_on[1 + s]) {
             const ElemRng g = elem_rng(1 + s);
             MIMO_TRY(elem_mask_mul_launch(dc->out.da, this->st, dc->out.ldda, em, N, dc->out.C, dc->out.Cp, H * W, st,
@@ -1747,11 +1798,60 @@ struct mimo_plan {
     }
   }
 
+  // The 8 stages of the backward with the data-gradient chain only, the S first-layer data gradients folded and summed into
+  // dimage [N,Ci,H,W] in the fixed order s = S-1, S-2, ..., 0 (fp32 adds; accumulate: on top of the caller's values).
+  int input_gradient(const float* dout, const float* dloss, float* dimage, int accumulate, hipStream_t st) {
+    if (cfg.inference_only == 1 || !s_zero) {
+      set_error("mimo_input_gradient: inference-only plan (no buffers for a backward)");
+      return MIMO_ERR_STATE;
+    }
+    if (cfg.precision != MIMO_PREC_FP32 && cfg.precision != MIMO_PREC_SPLIT16) {
+      set_error("mimo_input_gradient: implemented for the fp32 and split16 precisions, not for precision %d", cfg.precision);
+      return MIMO_ERR_INVALID;
+    }
+    if (!dimage || (!dout && !dloss)) {
+      set_error("mimo_input_gradient: need dimage and dout and/or dloss");
+      return MIMO_ERR_INVALID;
+    }
+    if (!fwd_done || fwd_no_grad || fwd_training) {
+      set_error("mimo_input_gradient: needs a mimo_forward with training = 0 and no_grad = 0 first");
+      return MIMO_ERR_STATE;
+    }
+    if (had_perm) {
+      set_error("mimo_input_gradient: needs a forward without perm");
+      return MIMO_ERR_STATE;
+    }
+    if (dloss && !loss_done) {
+      set_error("mimo_input_gradient: dloss given but mimo_loss_forward was not called");
+      return MIMO_ERR_STATE;
+    }
+    if (bwd_next_stage != 0) {
+      set_error("mimo_input_gradient: a staged mimo_backward is in progress (stage %d is next)", bwd_next_stage);
+      return MIMO_ERR_STATE;
+    }
+    // the data-gradient weight images: packed once per parameter version (an eval-mode forward packs the forward images only)
+    if (derived_version < 0 || dgrad_version != derived_version) {
+      MIMO_TRY(pack_jobs_launch(pack_jobs + n_fwd_jobs, n_all_jobs - n_fwd_jobs, pack_max_total, params, st));
+      dgrad_version = derived_version;
+    }
+    ig_only = true;
+    ig_dimage = dimage;
+    ig_accumulate = accumulate != 0;
+    int rc = MIMO_OK;
+    for (int stage = 0; stage < kBwdStages && rc == MIMO_OK; ++stage) rc = backward_stage(stage, dout, dloss, nullptr, st);
+    ig_only = false;
+    ig_dimage = nullptr;
+    return rc;
+  }
+
   int backward_encoders(float* dx, hipStream_t st) {
     for (int s = S - 1; s >= 0; --s) MIMO_TRY(dc_backward(down1[s], true, st));
     for (int s = S - 1; s >= 0; --s) {
-      MIMO_TRY(dc_backward(enc_in[s], dx != nullptr, st));
-      if (dx) MIMO_TRY(unpack_dx_launch(s_dxpadB, this->st, Ci_p, N, S, s, Ci, H, W, dx, st));
+      MIMO_TRY(dc_backward(enc_in[s], dx != nullptr || ig_only, st));
+      if (ig_only)  // s = S-1 assigns (or adds to the caller's values), S-2 ... 0 add: s_dxpadB is reused per encoder
+        MIMO_TRY(fold_image_grad_launch(s_dxpadB, Ci_p, N, Ci, H, W, ig_dimage, (s < S - 1 || ig_accumulate) ? 1 : 0, st));
+      else if (dx)
+        MIMO_TRY(unpack_dx_launch(s_dxpadB, this->st, Ci_p, N, S, s, Ci, H, W, dx, st));
     }
     return MIMO_OK;
   }
@@ -1815,6 +1915,7 @@ int mimo_plan_bind(mimo_plan* plan, float* params, float* grads, float* bn_buffe
   }
   if (plan->params != params || plan->bnbuf != bn_buffers) {
     plan->derived_version = -1;  // other tensors: re-derive
+    plan->dgrad_version = -1;
     plan->drop_graphs();         // the captured kernels hold the old parameter pointers
   }
   if (plan->grads != grads) plan->drop_graphs();
@@ -1960,6 +2061,14 @@ int mimo_backward_stage_async(mimo_plan* plan, int stage, const float* dout, con
   const int rc = plan->backward(dout, dloss, dx, stage, stage, (hipStream_t)stream, &ready);
   *ready_stream = (mimo_stream)ready;
   return rc;
+}
+
+int mimo_input_gradient(mimo_plan* plan, const float* dout, const float* dloss, float* dimage, int accumulate, mimo_stream stream) {
+  if (!plan) {
+    set_error("mimo_input_gradient: null plan");
+    return MIMO_ERR_INVALID;
+  }
+  return plan->input_gradient(dout, dloss, dimage, accumulate, (hipStream_t)stream);
 }
 
 int64_t mimo_plan_encoder_param_floats(const mimo_plan* plan) { return plan ? plan->encoder_param_floats : 0; }

@@ -47,18 +47,22 @@ class Plan:
     """One plan per (network geometry, batch, height, width, device)."""
 
     def __init__(self, geom: NetGeometry, batch: int, height: int, width: int, device: torch.device,
-                 inference_only: bool = False):
+                 inference_only=False):
+        """inference_only: False / True (no buffers for a backward), or the integer 2: input gradient only — what
+        `input_gradient` needs and nothing only a weight gradient needs (mimo_config.inference_only)."""
         if device.type != "cuda":
             raise L.MimoHipError("the MIMO U-Net engine runs on an AMD GPU only (no CPU fallback); got " + str(device))
         self.lib = L.load()
         self.geom, self.batch, self.height, self.width, self.device = geom, batch, height, width, device
+        flavour = 2 if (inference_only == 2 and not isinstance(inference_only, bool)) else int(bool(inference_only))
         cfg = L.MimoConfig(
             geom.in_channels, geom.out_channels, geom.num_subnetworks, geom.filter_base_count, batch, height, width,
             geom.encoder_dropout_rate, geom.core_dropout_rate, geom.decoder_dropout_rate,
             1e-5, 0.1, L.LOSS_KINDS[geom.loss], 1e-5, 1e3, device.index or 0, L.PRECISIONS[geom.precision],
-            int(bool(inference_only)), geom.center_dropout_rate, geom.final_dropout_rate,
+            flavour, geom.center_dropout_rate, geom.final_dropout_rate,
             0, 0, 0)  # BatchNorm2d + ReLU + bilinear up-sampling: the reference's blocks (the only variants that exist)
-        self.inference_only = bool(inference_only)
+        self.inference_only = flavour != 0  # no training backward on this plan
+        self.input_gradient_only = flavour == 2
         handle = C.c_void_p()
         with torch.cuda.device(device):
             L.check(self.lib.mimo_plan_create(C.byref(cfg), C.byref(handle)), "mimo_plan_create")
@@ -209,6 +213,16 @@ class Plan:
                 return ext
         return None
 
+    def input_gradient(self, dout: Optional[torch.Tensor], dloss: Optional[torch.Tensor], dimage: torch.Tensor,
+                       accumulate: bool = False) -> None:
+        """d loss / d image [N,Ci,H,W] of the image the last eval-mode forward (training=False, no_grad=False, no perm)
+        broadcast to the subnetworks: the data-gradient chain only, the subnetworks' gradients summed in the order
+        s = S-1 ... 0; accumulate adds to what `dimage` holds (mimo_input_gradient).  Writes no parameter gradient."""
+        g = self.geom
+        assert dimage.is_cuda and dimage.dtype == torch.float32 and dimage.is_contiguous()
+        assert tuple(dimage.shape) == (self.batch, g.in_channels, self.height, self.width), tuple(dimage.shape)
+        L.check(self.lib.mimo_input_gradient(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
+                                             int(bool(accumulate)), L.current_stream()), "mimo_input_gradient")
 
     PROF_KINDS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "bn_relu_fwd", "bn_bwd_reduce", "bn_bwd_apply",
                   "upcat_fwd", "up_bwd", "pool_bwd", "head_fwd", "head_bwd")
@@ -269,6 +283,22 @@ def adam_step_amp(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tens
                                    params.numel(), lr, betas[0], betas[1], eps, weight_decay, step_dev.data_ptr(),
                                    reduce_scale, L.ptr(amp_scale) or None, L.ptr(found_inf) or None, L.current_stream()),
             "mimo_adam_step_amp")
+
+
+def fgsm_perturb(image: torch.Tensor, dimage: torch.Tensor, epsilons: Sequence[float], lo: float = 0.0,
+                 hi: float = 1.0) -> torch.Tensor:
+    """[K, *image.shape] = clamp(image + eps_k * sign(dimage), lo, hi) for all K perturbation sizes in one pass over image
+    and gradient (mimo_fgsm_perturb; fgsm_attack of the reference's scripts/test/test_nyuv2_depth.py:16-24)."""
+    lib = L.load()
+    assert image.is_cuda and dimage.is_cuda and image.shape == dimage.shape
+    image, dimage = image.contiguous().float(), dimage.contiguous().float()
+    k = len(epsilons)
+    eps = (C.c_float * k)(*[float(e) for e in epsilons])
+    out = torch.empty((k,) + tuple(image.shape), device=image.device, dtype=torch.float32)
+    with torch.cuda.device(image.device):
+        L.check(lib.mimo_fgsm_perturb(image.data_ptr(), dimage.data_ptr(), image.numel(), eps, k, float(lo), float(hi),
+                                      out.data_ptr(), L.current_stream()), "mimo_fgsm_perturb")
+    return out
 
 
 def uncertainties(p1: torch.Tensor, p2: torch.Tensor, loss: str = "laplace_nll"):

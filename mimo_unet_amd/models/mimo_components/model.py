@@ -360,15 +360,17 @@ class MimoUNet(nn.Module):
             bn.num_batches_tracked.data = self._flat_counters[i]
 
     def _plan_for(self, x: torch.Tensor, perm: Optional[torch.Tensor], inference: bool = False,
-                  for_autograd: bool = False) -> Plan:
+                  for_autograd: bool = False, grad_only: bool = False) -> Plan:
         """inference: a plan without the buffers only a backward needs (pre-activation tensors, activation
         gradients, dz / padded-gradient / weight-gradient scratch, data-gradient weight copies) — what eval
-        mode under torch.no_grad() uses, e.g. the passes x B samples of an MC-dropout ensemble."""
+        mode under torch.no_grad() uses, e.g. the passes x B samples of an MC-dropout ensemble.
+        grad_only: a plan for `image_gradient` (pre-activations, activation gradients and data-gradient weights, nothing a
+        weight gradient needs)."""
         if not x.is_cuda:
             raise L.MimoHipError("MimoUNet runs on an AMD GPU through libmimo_hip.so; move the module and its inputs "
                                  "to cuda (there is no CPU execution path)")
         n = perm.shape[1] if perm is not None else x.shape[0]
-        key = (n, x.shape[-2], x.shape[-1], x.device.index, bool(inference))
+        key = (n, x.shape[-2], x.shape[-1], x.device.index, "input-gradient" if grad_only else bool(inference))
         plan = self._plans.get(key)
         if for_autograd and plan is not None and getattr(plan, "pending", None) is not None:
             # an earlier graph of this geometry is still alive and may yet be back-propagated (two forwards, then the
@@ -387,7 +389,7 @@ class MimoUNet(nn.Module):
                 # numerics status word (a NaN on a ragged last batch, say) outlives it: numerics_status() ORs it in
                 _, old = self._plans.popitem(last=False)
                 self._evicted_status = getattr(self, "_evicted_status", 0) | old.status(True)
-            plan = Plan(self._geom, n, x.shape[-2], x.shape[-1], x.device, inference_only=inference)
+            plan = Plan(self._geom, n, x.shape[-2], x.shape[-1], x.device, inference_only=2 if grad_only else inference)
             plan.generation = 0
             plan.pending = None
             self._plans[key] = plan
@@ -521,6 +523,33 @@ class MimoUNet(nn.Module):
         mask = None if mask is None else mask.contiguous().float()
         perms = None if perms is None else perms.to(device=image.device, dtype=torch.int64).contiguous()
         return self._call(image, label, mask, perms)
+
+    def image_gradient(self, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor], dloss: torch.Tensor,
+                       dimage: torch.Tensor, accumulate: bool = False):
+        """Evaluation-grade input gradient (mimo_input_gradient): eval-mode forward of `image` [B,C,H,W] broadcast to the
+        S subnetworks, the per-subnetwork mean NLL against `label` [B,Ct,H,W], and d sum_s(dloss[s] * loss[s]) / d image
+        written (accumulate: added) into `dimage` [B,C,H,W].  Touches no `.grad`, no BatchNorm buffer, no autograd graph.
+        Returns (logits [B,S,Co,H,W], loss [S])."""
+        if self._bn_training() or any(d.p > 0.0 and d.training for d in self._dropout_modules()):
+            raise NotImplementedError("MimoUNet.image_gradient: eval mode only (BatchNorm on running statistics, dropout off)")
+        image = image.contiguous().float()
+        if image.dim() != 4 or image.shape[1] != self.in_channels:
+            raise ValueError(f"expected [B,{self.in_channels},H,W], got {tuple(image.shape)}")
+        label = label.contiguous().float()
+        mask = None if mask is None else mask.contiguous().float()
+        dloss = dloss.to(device=image.device, dtype=torch.float32).contiguous()
+        assert dloss.shape == (self.num_subnetworks,)
+        plan = self._plan_for(image, None, grad_only=True)
+        out = torch.empty(image.shape[0], self.num_subnetworks, self.out_channels, plan.height, plan.width, device=image.device,
+                          dtype=torch.float32)
+        loss = torch.empty(self.num_subnetworks, device=image.device, dtype=torch.float32)
+        plan.bind(self._flat_params, None, self._flat_buffers)
+        plan.forward(image, out, training=False, broadcast_subnetworks=True, no_grad=False, param_version=self._param_version())
+        plan.loss_forward(label, mask, None, loss)
+        plan.input_gradient(None, dloss, dimage, accumulate)
+        plan.generation += 1
+        self._inference_keep = (image, label, mask, dloss, out)  # the plan still points at these
+        return out, loss
 
     def _run_backward(self, plan: Plan, dout, dloss, dx) -> None:
         g = self._flat_grads

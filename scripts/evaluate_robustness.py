@@ -1,0 +1,135 @@
+"""FGSM robustness sweep of an ensemble on the GPU (the first half of the reference's scripts/test/test_nyuv2_depth.py:
+make_predictions per noise level + the two tables), with the time of the sweep per batch and, with --compare, the time of
+the route the code base offered before `mimo.adversarial`: per eps, autograd through `MimoUnetModel` with the torch-side
+loss, `x.grad`, the torch expression of the attack, then the ensemble forward.
+
+    python scripts/evaluate_robustness.py --synthetic 4 --result_dir out                      # seeded model and batches
+    python scripts/evaluate_robustness.py --synthetic 4 --compare --result_dir out            # + the older route, alternating
+    python scripts/evaluate_robustness.py --model_checkpoint_paths a.ckpt b.ckpt --batch_dir batches/ --result_dir out
+
+--batch_dir: `*.npy` files holding one dict each ({"image": [B,C,H,W], "label": [B,1,H,W], optional "mask"}), saved with
+np.save(..., allow_pickle=True).  --synthetic N: N seeded batches of --batch x --channels x --size x --size (defaults: the
+benchmark geometry cfg3, 32 x 2 x 256 x 256) through a seeded S = 2, fbc = --fbc network."""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mimo.adversarial import RobustnessEvaluator, fgsm_sweep  # noqa: E402
+
+
+def older_route(ensemble, image, label, epsilons, mask=None):
+    """Per eps (the reference's loop, test_nyuv2_depth.py:38-61): gradient of the NLL w.r.t. the image through every member under
+    autograd (the whole training backward runs for it), sign / mul / add / clamp as torch launches, the ensemble forward."""
+    out = {}
+    s_total = ensemble.num_subnetworks
+    for eps in epsilons:
+        grad = torch.zeros_like(image)
+        for model in ensemble.models:
+            S = model.num_subnetworks
+            x5 = image[:, None].repeat(1, S, 1, 1, 1).requires_grad_(True)
+            p1, p2 = model(x5)
+            labels = label[:, None].repeat(1, S, 1, 1, 1)
+            raw = model.loss_fn.forward(p1, p2, labels, reduce_mean=False, mask=None if mask is None else mask[:, None])
+            (raw.mean() * (S / s_total)).backward()
+            grad += x5.grad.sum(dim=1)
+        perturbed = torch.clamp(image + eps * grad.sign(), 0, 1)
+        out[eps] = ensemble(perturbed)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model_checkpoint_paths", nargs="*", default=[])
+    ap.add_argument("--batch_dir")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--channels", type=int, default=2)
+    ap.add_argument("--fbc", type=int, default=30)
+    ap.add_argument("--members", type=int, default=1, help="seeded members of the synthetic ensemble")
+    ap.add_argument("--epsilons", type=float, nargs="+", default=[0.0, 0.02, 0.04])
+    ap.add_argument("--name", default="synthetic")
+    ap.add_argument("--compare", action="store_true", help="also time the autograd route, in alternating pairs")
+    ap.add_argument("--result_dir", required=True)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    from mimo.models.ensemble import EnsembleModule
+    models = None
+    if not args.model_checkpoint_paths:
+        if args.synthetic < 1:
+            ap.error("give checkpoints or --synthetic N")
+        from mimo.models.mimo_unet import MimoUnetModel
+        models = []
+        for i in range(args.members):
+            torch.manual_seed(i)
+            models.append(MimoUnetModel(in_channels=args.channels, out_channels=2, num_subnetworks=2, filter_base_count=args.fbc,
+                                        center_dropout_rate=0.0, final_dropout_rate=0.0, encoder_dropout_rate=0.0,
+                                        core_dropout_rate=0.0, decoder_dropout_rate=0.0, loss="laplace_nll", weight_decay=0.0,
+                                        learning_rate=1e-3, seed=i, loss_buffer_size=10, loss_buffer_temperature=0.3).cuda())
+    ensemble = EnsembleModule(args.model_checkpoint_paths, models=models, keep_on_device=True).to(dev)
+    if args.batch_dir:
+        batches = [np.load(f, allow_pickle=True).item() for f in sorted(glob.glob(os.path.join(args.batch_dir, "*.npy")))]
+    else:
+        g = torch.Generator().manual_seed(1)
+        batches = [{"image": torch.rand(args.batch, args.channels, args.size, args.size, generator=g),
+                    "label": torch.rand(args.batch, 1, args.size, args.size, generator=g)} for _ in range(args.synthetic)]
+    eps = tuple(args.epsilons)
+    rob = RobustnessEvaluator(eps)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0.record()
+        res = fn()
+        e1.record()
+        e1.synchronize()
+        return res, e0.elapsed_time(e1)
+
+    first = {k: torch.as_tensor(batches[0][k]).to(dev) for k in ("image", "label")}
+    fgsm_sweep(ensemble, first["image"], first["label"], eps)  # first calls: plans, code load
+    if args.compare:
+        older_route(ensemble, first["image"], first["label"], eps)
+    new_ms, old_ms, agree = [], [], []
+    for i, b in enumerate(batches):
+        image, label = (torch.as_tensor(b[k]).to(dev) for k in ("image", "label"))
+        mask = torch.as_tensor(b["mask"]).to(dev) if b.get("mask") is not None else None
+        order = ("new", "old") if i % 2 == 0 else ("old", "new")  # alternating pairs: drift hits both routes alike
+        res = {}
+        for which in order if args.compare else ("new",):
+            if which == "new":
+                res["new"], ms = timed(lambda: fgsm_sweep(ensemble, image, label, eps, mask=mask))
+                new_ms.append(ms)
+            else:
+                res["old"], ms = timed(lambda: older_route(ensemble, image, label, eps, mask=mask))
+                old_ms.append(ms)
+        if args.compare:  # the two routes' predictions differ only where a gradient's sign is within rounding of zero
+            e = eps[-1]
+            a, c = res["new"][e][0], res["old"][e][0]
+            agree.append(float((a - c).abs().max() / c.abs().max()))
+        line = f"batch {i}: sweep {new_ms[-1]:.3f} ms"
+        if args.compare:
+            line += f", autograd route {old_ms[-1]:.3f} ms, max |mean difference| / max |mean| at eps {eps[-1]}: {agree[-1]:.2e}"
+        print(line, flush=True)
+        for e, (mean, av, ev) in res["new"].items():
+            rob.evaluators[e].update(mean, av, ev, label, mask)
+    tables = rob.compute()
+    rob.write_csv(args.result_dir, args.name, tables)
+    out = {"epsilons": list(eps), "batches": len(batches), "pixels_per_batch": int(batches[0]["image"].shape[0]) * args.size * args.size
+           if not args.batch_dir else None, "sweep_ms_median": float(np.median(new_ms)), "sweep_ms_min": float(np.min(new_ms)),
+           "mae_per_eps": {str(e): tables[e]["mae"] for e in eps}}
+    if old_ms:
+        out.update(autograd_route_ms_median=float(np.median(old_ms)), autograd_route_ms_min=float(np.min(old_ms)),
+                   speedup_median=float(np.median(old_ms) / np.median(new_ms)))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
