@@ -9,7 +9,7 @@
 
 namespace mimo {
 
-constexpr int kMaxChunks = 64;   // second-level partial rows kept for finalize kernels
+constexpr int kMaxChunks = 64;   // second-level partial rows rowsum_launch leaves for bn_fwd_finalize_launch
 constexpr int kEwMaxBlocks = 1024;
 constexpr int kBnReduceMaxBlocks = 2048;  // upper bound of the BatchNorm-backward grids (partial-row capacity; 1792 used)
 constexpr int kMaxHeadOut = 8;   // out_channels supported by the fused head kernels
@@ -17,26 +17,23 @@ constexpr int kMaxHeadOut = 8;   // out_channels supported by the fused head ker
 // ---- generic two-level column reduction of per-workgroup partial rows -------------------
 // partial [rows][cols] (float) -> sums [chunks][cols] (double); returns chunks via *chunks.
 int rowsum_launch(const float* partial, int rows, int cols, double* sums, int* chunks, hipStream_t s);
-// one-launch reductions over fp32 partial rows (column sums + the finalize arithmetic); use while rows <= kColsumMaxRows.
-// ColsumScratch: doubles [kMaxChunks][2][round_up(columns, 64)] + one zero-initialised int ticket per 64-column group
-// (kColsumMaxGroups), owned by the plan; launches sharing it must be ordered on one stream.
+// one-launch reductions over fp32 partial rows (column sums + the finalize arithmetic, one workgroup per 64 columns, no
+// scratch); use while rows <= kColsumMaxRows.
+// status: numerics status word of the plan (mimo_plan_status) or nullptr: OR-ed when a finalized sum is not finite
 constexpr int kColsumMaxRows = 2048;
-constexpr int kColsumMaxGroups = 256;
-struct ColsumScratch {
-  double* sums;
-  int* tickets;
-  int* status = nullptr;  // numerics status word of the plan (mimo_plan_status): OR-ed when a finalized sum is not finite
-};
 // bits of the status word
 constexpr int kStatusFwdStats = 1, kStatusBwdStats = 2, kStatusLogits = 4;
-int colsum_vec_launch(const float* partial, int rows, int cols, int C, float* out, const ColsumScratch& cs, hipStream_t st);
+// out[c] = sum over rows of partial[r][c], c < C
+int colsum_vec_launch(const float* partial, int rows, int cols, int C, float* out, hipStream_t st);
 int bn_fwd_stats_launch(const float* partial, int rows, int cout_pad, int C, int Cp, int64_t count, const float* gamma,
                         const float* beta, float* running_mean, float* running_var, float momentum, float eps, float* mean,
-                        float* invstd, float* scale, float* shift, const ColsumScratch& cs, hipStream_t st);
+                        float* invstd, float* scale, float* shift, int* status, hipStream_t st);
+// partial rows of bnrelu_bwd_reduce_launch: c1 = sum_dy/count, c2 = sum_dyxhat/count (zero when !training); dgamma, dbeta ->
+// grads; dbias_zero != nullptr: the convolution's bias gradient, written as zeros
 int bn_bwd_stats_launch(const float* partial, int rows, int C, int Cp, int64_t count, int training, float* c1, float* c2,
-                        float* dgamma, float* dbeta, float* dbias_zero, const ColsumScratch& cs, hipStream_t st);
-int head_bwd_stats_launch(const float* partial, int rows, int C, int Cp, int Co, float* dw, float* db, const ColsumScratch& cs,
-                          hipStream_t st);
+                        float* dgamma, float* dbeta, float* dbias_zero, int* status, hipStream_t st);
+// partial rows of head_bwd_launch (or of the GS_HEAD reduction) -> dw [Co][C], db [Co]
+int head_bwd_stats_launch(const float* partial, int rows, int C, int Cp, int Co, float* dw, float* db, hipStream_t st);
 
 // ---- input / output layout conversion ---------------------------------------------------
 // x NCHW-strided (see mimo_forward_args) -> NHWC [N,H,W,cp] for subnetwork s (zero pad channels)
@@ -51,7 +48,7 @@ int unpack_dx_launch(const void* dxpad, int dt, int ldp, int N, int S, int s, in
 int fold_image_grad_launch(const float* dxpad, int ldp, int N, int C, int H, int W, float* dimage, int accumulate, hipStream_t st);
 
 // ---- BatchNorm + ReLU (+ Dropout2d) forward ---------------------------------------------
-// training: sums = rowsum of the conv epilogue partials ([chunks][2*cout_pad]).
+// training, more than kColsumMaxRows partial rows: sums = rowsum of the conv epilogue partials ([chunks][2*cout_pad]).
 int bn_fwd_finalize_launch(const double* sums, int chunks, int cout_pad, int C, int Cp, int64_t count,
                            const float* gamma, const float* beta, float* running_mean, float* running_var,
                            float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
@@ -168,9 +165,6 @@ int bnrelu_bwd_reduce_launch(const GradSrc& src, int dta, const void* z, int dtz
                              const float* scale, const float* shift, const float* mean, const float* invstd,
                              const float* mask, int C, int Cp, int N, int H, int W, float* partial, int* rows,
                              hipStream_t st);
-// c1 = sum_dy/count, c2 = sum_dyxhat/count (zero when !training); dgamma, dbeta -> grads
-int bn_bwd_finalize_launch(const double* sums, int chunks, int C, int Cp, int64_t count, int training, float* c1,
-                           float* c2, float* dgamma, float* dbeta, hipStream_t st);
 // pass 2: dz = scale * (dy - c1 - xhat*c2); partial rows of sum dz (conv bias gradient)
 int bn_bwd_apply_launch(const GradSrc& src, int dta, const void* z, int dtz, int ldz,
                         const float* scale, const float* shift, const float* mean, const float* invstd, const float* mask,
@@ -183,8 +177,6 @@ int bn_bwd_apply_launch(const GradSrc& src, int dta, const void* z, int dtz, int
 // absmax != nullptr: *absmax_n per-workgroup maxima of |src| are left there (WgradLaunch::dz_absmax; capacity kDzMaxSlots floats)
 int split_pairs_launch(const float* src, float* dst, int64_t P, int Cp, hipStream_t st, float* absmax = nullptr,
                        int* absmax_n = nullptr);
-// out[c] = sum over chunks of sums[chunk][c], c < C
-int vec_finalize_launch(const double* sums, int chunks, int cols, int C, float* out, hipStream_t st);
 
 // ---- 1x1 head + loss ------------------------------------------------------------------------
 // out[n][s][co][yx] = bias[co] + sum_c a[n,yx,c] * w[co][c]      (components.py:126)
@@ -204,7 +196,5 @@ int head_bwd_launch(const void* a, int dt, int lda, const float* w, int C, int C
                     const float* out, const float* dout, const float* dloss, const float* label, const float* mask,
                     const int64_t* perm, int kind, float eps_min, float eps_max, void* da, float* partial,
                     int* rows, hipStream_t st, const float* in_scale = nullptr, const float* in_shift = nullptr);
-int head_bwd_finalize_launch(const double* sums, int chunks, int C, int Cp, int Co, float* dw, float* db,
-                             hipStream_t st);
 
 }  // namespace mimo

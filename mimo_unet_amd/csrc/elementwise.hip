@@ -257,22 +257,10 @@ int rowsum_launch(const float* partial, int rows, int cols, double* sums, int* c
   return MIMO_OK;
 }
 
-// The finalize kernels run 256 threads per 64 columns: four groups each add every fourth chunk row (the
-// serial walk over up to kMaxChunks rows was most of their ~8 us), the group totals are added in fixed order.
-// Every thread of the workgroup must call this; the total is returned to all of them.
-__device__ __forceinline__ double chunk_total(const double* __restrict__ col, size_t stride, int chunks, bool valid,
-                                              double* red) {
-  double s = 0.0;
-  if (valid)
-    for (int k = threadIdx.x >> 6; k < chunks; k += 4) s += col[(size_t)k * stride];
-  __syncthreads();
-  red[threadIdx.x] = s;
-  __syncthreads();
-  const int cl = threadIdx.x & 63;
-  return (red[cl] + red[64 + cl]) + (red[128 + cl] + red[192 + cl]);
-}
-
-// two columns in one walk (the BatchNorm finalize kernels need sum and sum of squares): one barrier pair
+// The finalize kernel of the rowsum route runs 256 threads per 64 columns: four groups each add every fourth chunk row (the
+// serial walk over up to kMaxChunks rows was most of its ~8 us), the group totals are added in fixed order.  Two columns
+// in one walk (sum and sum of squares): one barrier pair.  Every thread of the workgroup must call this; the totals are
+// returned to all of them.
 __device__ __forceinline__ void chunk_total2(const double* __restrict__ col_a, const double* __restrict__ col_b, size_t stride,
                                              int chunks, bool valid, double* red /*[512]*/, double* ta, double* tb) {
   double sa = 0.0, sb = 0.0;
@@ -294,13 +282,12 @@ __device__ __forceinline__ void chunk_total2(const double* __restrict__ col_a, c
 // fp32 partial rows of its 64 columns in double, eight independent loads in flight per thread, then runs the
 // finalize arithmetic — one launch instead of the rowsum + finalize pair.  (Spreading the rows over several
 // workgroups with a last-workgroup ticket was measured SLOWER, 24 vs 13 us: the device-scope fence it needs writes
-// back / invalidates the whole L2 on this multi-XCD part.)  `scratch` / `tickets` are unused, kept for the signature.
+// back / invalidates the whole L2 on this multi-XCD part.)  Every thread of the workgroup must call grid_colsum2; the
+// totals are valid in its first 64 threads.
 constexpr int kColsumThreads = 1024;
-static int colsum_chunks(int) { return 1; }
 
-__device__ __forceinline__ bool grid_colsum2(const float* __restrict__ partial, int rows, size_t stride, int col_a, int col_b,
-                                             bool valid, bool two, double* red /*[2048]*/, double* __restrict__, int,
-                                             int* __restrict__, double* ta, double* tb) {
+__device__ __forceinline__ void grid_colsum2(const float* __restrict__ partial, int rows, size_t stride, int col_a, int col_b,
+                                             bool valid, bool two, double* red /*[2048]*/, double* ta, double* tb) {
   const int rg = threadIdx.x >> 6;
   double sa = 0.0, sb = 0.0;
   if (valid) {
@@ -347,38 +334,20 @@ __device__ __forceinline__ bool grid_colsum2(const float* __restrict__ partial, 
   }
   *ta = a;
   *tb = b;
-  return true;
 }
 
 // out[c] = sum over rows of partial[r][c]  (conv bias gradient)
 __global__ __launch_bounds__(kColsumThreads) void colsum_vec_kernel(const float* __restrict__ partial, int rows, int cols,
-                                                                    int C, float* __restrict__ out,
-                                                                    double* __restrict__ scratch, int scratch_cols,
-                                                                    int* __restrict__ tickets) {
+                                                                    int C, float* __restrict__ out) {
   __shared__ double red[2048];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   double s, unused;
-  if (!grid_colsum2(partial, rows, (size_t)cols, c, c, c < C, false, red, scratch, scratch_cols, tickets, &s, &unused)) return;
+  grid_colsum2(partial, rows, (size_t)cols, c, c, c < C, false, red, &s, &unused);
   if (c < C && threadIdx.x < 64) out[c] = (float)s;
 }
 
-int colsum_vec_launch(const float* partial, int rows, int cols, int C, float* out, const ColsumScratch& cs, hipStream_t st) {
-  const int groups = ceil_div(C, 64);
-  hipLaunchKernelGGL(colsum_vec_kernel, dim3(groups, colsum_chunks(rows)), dim3(kColsumThreads), 0, st, partial, rows, cols, C,
-                     out, cs.sums, groups * 64, cs.tickets);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-__global__ void vec_finalize_kernel(const double* __restrict__ sums, int chunks, int cols, int C, float* __restrict__ out) {
-  __shared__ double red[256];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const double s = chunk_total(sums + c, cols, chunks, c < C, red);
-  if (c < C && threadIdx.x < 64) out[c] = (float)s;
-}
-
-int vec_finalize_launch(const double* sums, int chunks, int cols, int C, float* out, hipStream_t st) {
-  hipLaunchKernelGGL(vec_finalize_kernel, dim3(ceil_div(C, 64)), dim3(256), 0, st, sums, chunks, cols, C, out);
+int colsum_vec_launch(const float* partial, int rows, int cols, int C, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(colsum_vec_kernel, dim3(ceil_div(C, 64)), dim3(kColsumThreads), 0, st, partial, rows, cols, C, out);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
@@ -465,17 +434,14 @@ int fold_image_grad_launch(const float* dxpad, int ldp, int N, int C, int H, int
 // ---------------------------------------------------------------------------------------
 // BatchNorm statistics -> scale/shift
 // ---------------------------------------------------------------------------------------
-__global__ void bn_fwd_finalize_kernel(const double* __restrict__ sums, int chunks, int cout_pad, int C, int Cp,
-                                       double count, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                       float* __restrict__ running_mean, float* __restrict__ running_var,
-                                       float momentum, float eps, float* __restrict__ mean, float* __restrict__ invstd,
-                                       float* __restrict__ scale, float* __restrict__ shift) {
-  __shared__ double red[512];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int cols = 2 * cout_pad;
-  double s1, s2;
-  chunk_total2(sums + c, sums + cout_pad + c, cols, chunks, c < C, red, &s1, &s2);
-  if (c >= Cp || threadIdx.x >= 64) return;
+// Channel c < Cp of a training forward from its sum s1 and sum of squares s2 over `count` elements: mean / invstd, the
+// scale / shift that BatchNorm + affine apply, the running statistics (pad channels c >= C: zeros).
+// status != nullptr: a convolution output that is not finite (an input / weight outside the fp16 range of the split forward, a
+// diverged run) shows in its channel sums: recorded for mimo_plan_status instead of surfacing only as NaNs downstream
+__device__ __forceinline__ void bn_fwd_finalize_channel(
+    int c, int C, double s1, double s2, double count, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ scale, float* __restrict__ shift, int* __restrict__ status) {
   if (c >= C) {
     mean[c] = 0.f;
     invstd[c] = 0.f;
@@ -483,42 +449,6 @@ __global__ void bn_fwd_finalize_kernel(const double* __restrict__ sums, int chun
     shift[c] = 0.f;
     return;
   }
-  const double m = s1 / count;
-  double var = s2 / count - m * m;
-  var = var > 0.0 ? var : 0.0;
-  const double is = 1.0 / sqrt(var + (double)eps);
-  const double sc = (double)gamma[c] * is;
-  mean[c] = (float)m;
-  invstd[c] = (float)is;
-  scale[c] = (float)sc;
-  shift[c] = (float)((double)beta[c] - m * sc);
-  const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-  running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
-  running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
-}
-
-// rowsum + bn_fwd_finalize in one launch: partial rows [rows][2][cout_pad] straight from the convolution epilogue
-__global__ __launch_bounds__(kColsumThreads) void bn_fwd_stats_kernel(
-    const float* __restrict__ partial, int rows, int cout_pad, int C, int Cp, double count, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float* __restrict__ running_mean, float* __restrict__ running_var, float momentum,
-    float eps, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale, float* __restrict__ shift,
-    double* __restrict__ scratch, int scratch_cols, int* __restrict__ tickets, int* __restrict__ status) {
-  __shared__ double red[2048];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  double s1, s2;
-  if (!grid_colsum2(partial, rows, (size_t)2 * cout_pad, c, cout_pad + c, c < C, true, red, scratch, scratch_cols, tickets, &s1,
-                    &s2))
-    return;
-  if (c >= Cp || threadIdx.x >= 64) return;
-  if (c >= C) {
-    mean[c] = 0.f;
-    invstd[c] = 0.f;
-    scale[c] = 0.f;
-    shift[c] = 0.f;
-    return;
-  }
-  // a convolution output that is not finite (an input / weight outside the fp16 range of the split forward, a
-  // diverged run) shows in its channel sums: recorded for mimo_plan_status instead of surfacing only as NaNs downstream
   if (status && !(isfinite(s1) && isfinite(s2))) atomicOr(status, kStatusFwdStats);
   const double m = s1 / count;
   double var = s2 / count - m * m;
@@ -534,13 +464,42 @@ __global__ __launch_bounds__(kColsumThreads) void bn_fwd_stats_kernel(
   running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
 }
 
+// second step of the rowsum route (more than kColsumMaxRows partial rows, ops_api.hip): no status word
+__global__ void bn_fwd_finalize_kernel(const double* __restrict__ sums, int chunks, int cout_pad, int C, int Cp,
+                                       double count, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                       float* __restrict__ running_mean, float* __restrict__ running_var,
+                                       float momentum, float eps, float* __restrict__ mean, float* __restrict__ invstd,
+                                       float* __restrict__ scale, float* __restrict__ shift) {
+  __shared__ double red[512];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int cols = 2 * cout_pad;
+  double s1, s2;
+  chunk_total2(sums + c, sums + cout_pad + c, cols, chunks, c < C, red, &s1, &s2);
+  if (c >= Cp || threadIdx.x >= 64) return;
+  bn_fwd_finalize_channel(c, C, s1, s2, count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift,
+                          nullptr);
+}
+
+// rowsum + bn_fwd_finalize in one launch: partial rows [rows][2][cout_pad] straight from the convolution epilogue
+__global__ __launch_bounds__(kColsumThreads) void bn_fwd_stats_kernel(
+    const float* __restrict__ partial, int rows, int cout_pad, int C, int Cp, double count, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ running_mean, float* __restrict__ running_var, float momentum,
+    float eps, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale, float* __restrict__ shift,
+    int* __restrict__ status) {
+  __shared__ double red[2048];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  double s1, s2;
+  grid_colsum2(partial, rows, (size_t)2 * cout_pad, c, cout_pad + c, c < C, true, red, &s1, &s2);
+  if (c >= Cp || threadIdx.x >= 64) return;
+  bn_fwd_finalize_channel(c, C, s1, s2, count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift,
+                          status);
+}
+
 int bn_fwd_stats_launch(const float* partial, int rows, int cout_pad, int C, int Cp, int64_t count, const float* gamma,
                         const float* beta, float* running_mean, float* running_var, float momentum, float eps, float* mean,
-                        float* invstd, float* scale, float* shift, const ColsumScratch& cs, hipStream_t st) {
-  const int groups = ceil_div(Cp, 64);
-  hipLaunchKernelGGL(bn_fwd_stats_kernel, dim3(groups, colsum_chunks(rows)), dim3(kColsumThreads), 0, st, partial, rows,
-                     cout_pad, C, Cp, (double)count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale,
-                     shift, cs.sums, groups * 64, cs.tickets, cs.status);
+                        float* invstd, float* scale, float* shift, int* status, hipStream_t st) {
+  hipLaunchKernelGGL(bn_fwd_stats_kernel, dim3(ceil_div(Cp, 64)), dim3(kColsumThreads), 0, st, partial, rows, cout_pad, C, Cp,
+                     (double)count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift, status);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
@@ -1543,34 +1502,16 @@ int bnrelu_bwd_reduce_launch(const GradSrc& src, int dta, const void* z, int dtz
   return MIMO_OK;
 }
 
-__global__ void bn_bwd_finalize_kernel(const double* __restrict__ sums, int chunks, int C, int Cp, double count,
-                                       int training, float* __restrict__ c1, float* __restrict__ c2,
-                                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  __shared__ double red[512];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  double s1, s2;
-  chunk_total2(sums + c, sums + Cp + c, (size_t)2 * Cp, chunks, c < Cp, red, &s1, &s2);
-  if (c >= Cp || threadIdx.x >= 64) return;
-  c1[c] = training ? (float)(s1 / count) : 0.f;
-  c2[c] = training ? (float)(s2 / count) : 0.f;
-  if (c < C) {
-    if (dgamma) dgamma[c] = (float)s2;
-    if (dbeta) dbeta[c] = (float)s1;
-  }
-}
-
-// rowsum + bn_bwd_finalize in one launch: partial rows [rows][2][Cp] from bnrelu_bwd_reduce
+// column sums + finalize in one launch: partial rows [rows][2][Cp] from bnrelu_bwd_reduce
 __global__ __launch_bounds__(kColsumThreads) void bn_bwd_stats_kernel(const float* __restrict__ partial, int rows, int C,
                                                                       int Cp, double count, int training,
                                                                       float* __restrict__ c1, float* __restrict__ c2,
                                                                       float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                      float* __restrict__ dbias_zero,
-                                                                      double* __restrict__ scratch, int scratch_cols,
-                                                                      int* __restrict__ tickets, int* __restrict__ status) {
+                                                                      float* __restrict__ dbias_zero, int* __restrict__ status) {
   __shared__ double red[2048];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   double s1, s2;
-  if (!grid_colsum2(partial, rows, (size_t)2 * Cp, c, Cp + c, c < Cp, true, red, scratch, scratch_cols, tickets, &s1, &s2)) return;
+  grid_colsum2(partial, rows, (size_t)2 * Cp, c, Cp + c, c < Cp, true, red, &s1, &s2);
   if (c >= Cp || threadIdx.x >= 64) return;
   if (status && c < C && !(isfinite(s1) && isfinite(s2))) atomicOr(status, kStatusBwdStats);
   c1[c] = training ? (float)(s1 / count) : 0.f;
@@ -1585,18 +1526,9 @@ __global__ __launch_bounds__(kColsumThreads) void bn_bwd_stats_kernel(const floa
 }
 
 int bn_bwd_stats_launch(const float* partial, int rows, int C, int Cp, int64_t count, int training, float* c1, float* c2,
-                        float* dgamma, float* dbeta, float* dbias_zero, const ColsumScratch& cs, hipStream_t st) {
-  const int groups = ceil_div(Cp, 64);
-  hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(groups, colsum_chunks(rows)), dim3(kColsumThreads), 0, st, partial, rows, C, Cp,
-                     (double)count, training, c1, c2, dgamma, dbeta, dbias_zero, cs.sums, groups * 64, cs.tickets, cs.status);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-int bn_bwd_finalize_launch(const double* sums, int chunks, int C, int Cp, int64_t count, int training, float* c1,
-                           float* c2, float* dgamma, float* dbeta, hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(256), 0, st, sums, chunks, C, Cp, (double)count,
-                     training, c1, c2, dgamma, dbeta);
+                        float* dgamma, float* dbeta, float* dbias_zero, int* status, hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(ceil_div(Cp, 64)), dim3(kColsumThreads), 0, st, partial, rows, C, Cp, (double)count,
+                     training, c1, c2, dgamma, dbeta, dbias_zero, status);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
@@ -2074,31 +2006,15 @@ int head_bwd_launch(const void* a, int dt, int lda, const float* w, int C, int C
   return MIMO_OK;
 }
 
-__global__ void head_bwd_finalize_kernel(const double* __restrict__ sums, int chunks, int C, int Cp, int Co,
-                                         float* __restrict__ dw, float* __restrict__ db) {
-  const int cols = Co * Cp + Co;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cols) return;
-  double s = 0.0;
-  for (int k = 0; k < chunks; ++k) s += sums[(size_t)k * cols + i];
-  if (i < Co * Cp) {
-    const int co = i / Cp, c = i - co * Cp;
-    if (c < C) dw[co * C + c] = (float)s;
-  } else {
-    db[i - Co * Cp] = (float)s;
-  }
-}
-
-// rowsum + head_bwd_finalize in one launch: partial rows [rows][Co*Cp + Co] from head_bwd
+// column sums + finalize in one launch: partial rows [rows][Co*Cp + Co] from head_bwd
 __global__ __launch_bounds__(kColsumThreads) void head_bwd_stats_kernel(const float* __restrict__ partial, int rows, int C,
                                                                         int Cp, int Co, float* __restrict__ dw,
-                                                                        float* __restrict__ db, double* __restrict__ scratch,
-                                                                        int scratch_cols, int* __restrict__ tickets) {
+                                                                        float* __restrict__ db) {
   __shared__ double red[2048];
   const int cols = Co * Cp + Co;
   const int i = blockIdx.x * 64 + (threadIdx.x & 63);
   double s, unused;
-  if (!grid_colsum2(partial, rows, (size_t)cols, i, i, i < cols, false, red, scratch, scratch_cols, tickets, &s, &unused)) return;
+  grid_colsum2(partial, rows, (size_t)cols, i, i, i < cols, false, red, &s, &unused);
   if (i >= cols || threadIdx.x >= 64) return;
   if (i < Co * Cp) {
     const int co = i / Cp, c = i - co * Cp;
@@ -2108,18 +2024,9 @@ __global__ __launch_bounds__(kColsumThreads) void head_bwd_stats_kernel(const fl
   }
 }
 
-int head_bwd_stats_launch(const float* partial, int rows, int C, int Cp, int Co, float* dw, float* db, const ColsumScratch& cs,
-                          hipStream_t st) {
-  const int groups = ceil_div(Co * Cp + Co, 64);
-  hipLaunchKernelGGL(head_bwd_stats_kernel, dim3(groups, colsum_chunks(rows)), dim3(kColsumThreads), 0, st, partial, rows, C, Cp,
-                     Co, dw, db, cs.sums, groups * 64, cs.tickets);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-int head_bwd_finalize_launch(const double* sums, int chunks, int C, int Cp, int Co, float* dw, float* db, hipStream_t st) {
-  const int cols = Co * Cp + Co;
-  hipLaunchKernelGGL(head_bwd_finalize_kernel, dim3(ceil_div(cols, 64)), dim3(64), 0, st, sums, chunks, C, Cp, Co, dw, db);
+int head_bwd_stats_launch(const float* partial, int rows, int C, int Cp, int Co, float* dw, float* db, hipStream_t st) {
+  hipLaunchKernelGGL(head_bwd_stats_kernel, dim3(ceil_div(Co * Cp + Co, 64)), dim3(kColsumThreads), 0, st, partial, rows, C, Cp,
+                     Co, dw, db);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }

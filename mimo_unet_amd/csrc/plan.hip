@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "dz_ring.h"
 #include "elementwise.h"
 
 namespace mimo {
@@ -136,6 +137,104 @@ struct Head {
   int64_t off_w = 0, off_b = 0;
 };
 
+// What one walk of the backward stages was called with (mimo_backward*, mimo_input_gradient): handed down by reference from
+// backward_stage to the layer functions, nothing of it is kept on the plan.
+struct BwdCall {
+  const float *dout = nullptr, *dloss = nullptr;
+  float* dx = nullptr;
+  // mimo_input_gradient (evaluation-grade backward: the data-gradient chain only): a layer launches the BatchNorm-backward
+  // apply pass and the data gradient and nothing else
+  bool ig = false;
+  float* dimage = nullptr;  // ... the image gradient [N,Ci,H,W] the encoders' first-layer data gradients are folded into
+  bool accumulate = false;  // ... the first fold adds to what is there
+};
+
+// The dz buffers between the caller's stream (BatchNorm backward writes dz, the data gradient reads it) and the side stream
+// (the weight gradient reads it): buffers, max |dz| slots, split copies and events, and every cross-stream wait / record of
+// the protocol.  Which slot and which wait is decided by sched::DzRingPolicy (dz_ring.h, walked by tests/host/dz_ring_test.cpp).
+struct DzRing {
+  static constexpr int kSlots = sched::DzRingPolicy::kSlots;
+  sched::DzRingPolicy policy;
+  hipStream_t side = nullptr;  // the weight gradients' stream (null: everything on the caller's stream)
+  hipEvent_t ev_dz[kSlots] = {}, ev_wg[kSlots] = {}, ev_join = nullptr;
+  float* dz[kSlots] = {};
+  float* dzmax[kSlots] = {};  // per-workgroup maxima of |dz| of the tensor in dz[i] (two-MFMA weight gradient)
+  // split (bf16 hi|lo) copy of dz for layers whose data gradient runs on the fp32 kernel while the weight
+  // gradient runs on the bf16-pair kernel (fewer than 16 output channels); null when no layer needs it
+  float* dzs[kSlots] = {};
+  // one layer's use of a slot, and what its BatchNorm backward left there for its weight gradient
+  struct Slot {
+    int b = 0, wait_on = -1;
+    bool async = false, dz_on_launch = false;  // async: the weight gradient of this layer runs on the side stream
+    const float* dz_wg = nullptr;  // dz as the weight gradient reads it (the split copy where one was made)
+    float* absmax = nullptr;       // per-workgroup maxima of |dz| (two-MFMA weight gradient), absmax_n of them
+    int absmax_n = 0;
+  };
+  ~DzRing() {
+    if (side) (void)hipStreamDestroy(side);
+    for (int i = 0; i < kSlots; ++i)
+      for (hipEvent_t e : {ev_dz[i], ev_wg[i]})
+        if (e) (void)hipEventDestroy(e);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+  }
+  // the slot the next layer writes (!async: the current one, nothing moves and nothing is waited for)
+  Slot acquire(bool async) {
+    Slot s;
+    s.b = policy.next;
+    s.async = async;
+    if (async) s.wait_on = policy.acquire().wait_on;
+    return s;
+  }
+  // in front of the launch that overwrites dz[s.b] and dzmax[s.b] on `st`
+  int wait_free(const Slot& s, hipStream_t st) {
+    if (s.wait_on >= 0) MIMO_HIP_CHECK(hipStreamWaitEvent(st, ev_wg[s.wait_on], 0));
+    return MIMO_OK;
+  }
+  // "dz exists" travels with the launch that writes it (a stop event on the kernel, no hipEventRecord behind it) whenever that
+  // launch is the last writer — not when a split copy of dz follows — and not under stream capture
+  hipEvent_t dz_event_on_launch(Slot& s, bool capturing, bool split_copy_follows) {
+    s.dz_on_launch = s.async && !capturing && !split_copy_follows;
+    return s.dz_on_launch ? ev_dz[s.b] : nullptr;
+  }
+  // behind the last writer of dz on `st`: wgrad(L) may start as soon as dz exists, next to dgrad(L)
+  int dz_written(const Slot& s, hipStream_t st) {
+    if (s.async && !s.dz_on_launch) MIMO_HIP_CHECK(hipEventRecord(ev_dz[s.b], st));
+    return MIMO_OK;
+  }
+  // the stream the weight gradient of this layer runs on, made to wait for dz
+  int reader_stream(const Slot& s, hipStream_t st, hipStream_t* ws) {
+    *ws = st;
+    if (s.async) {
+      MIMO_HIP_CHECK(hipStreamWaitEvent(side, ev_dz[s.b], 0));  // (a wait refers to the record made just above)
+      *ws = side;
+    }
+    return MIMO_OK;
+  }
+  // the release event travels with the weight gradient's reduction launch, unless there is none (thin: the plain-FMA kernel's
+  // launch reduces its own partials) or the stream is being captured
+  hipEvent_t release_on_launch(const Slot& s, bool capturing, bool thin) const {
+    return (s.async && !capturing && !thin) ? ev_wg[s.b] : nullptr;
+  }
+  // dz buffer b AND its max |dz| slots are free again — recorded behind the REDUCTION: it reads the slots too (to take the
+  // two-MFMA kernel's scale out again), and the BatchNorm backward of the layer after next overwrites them.  (Until the
+  // end of round 5 the event sat in front of the reduction: a race that showed as a weight gradient off by > 1e-4 of
+  // its scale in one small-geometry test when that test ran alone.)
+  int released(const Slot& s, bool rode_on_launch) {
+    if (!s.async) return MIMO_OK;
+    if (!rode_on_launch) MIMO_HIP_CHECK(hipEventRecord(ev_wg[s.b], side));
+    policy.released(s.b);
+    return MIMO_OK;
+  }
+  // the caller's stream waits for every weight gradient issued so far
+  int join(hipStream_t st) {
+    if (!side || !policy.any_pending()) return MIMO_OK;
+    MIMO_HIP_CHECK(hipEventRecord(ev_join, side));
+    MIMO_HIP_CHECK(hipStreamWaitEvent(st, ev_join, 0));
+    policy.joined();
+    return MIMO_OK;
+  }
+};
+
 }  // namespace
 }  // namespace mimo
 
@@ -176,9 +275,7 @@ struct mimo_plan {
         *s_partial = nullptr, *s_losspart = nullptr;
   float* s_headpart = nullptr;  // GS_HEAD: the head's weight / bias gradient partial rows, written by the BatchNorm-backward reduction
   int head_rows = 0;            // ... and how many (that launch's grid)
-  double* s_sums = nullptr;
-  int* s_tickets = nullptr;  // colsum tickets of the scratch set in use (zero between launches)
-  ColsumScratch colsum() const { return ColsumScratch{s_sums, s_tickets, d_status}; }
+  double* s_sums = nullptr;  // rowsum_launch's chunk sums (convolution epilogues with more than kColsumMaxRows partial rows)
   int* d_status = nullptr;  // numerics status word (mimo_plan_status)
   size_t cap_act = 0, cap_pad = 0, cap_slab = 0, cap_partial = 0, cap_sums = 0;
   float* s_kpart = nullptr;  // partial-sum slabs of the K-split convolution launches (conv3x3_bf16x3_launch_k)
@@ -186,9 +283,9 @@ struct mimo_plan {
 
   // MIMO_WGRAD_STREAM (default 1): weight gradients on a side stream — wgrad(L) (matrix-pipe bound, little HBM
   // traffic) overlaps the bandwidth-bound BatchNorm / gather kernels of the layers below it on the caller's stream;
-  // dz ping-pongs between two buffers so that layer L-1 can write its dz while wgrad(L) still reads the other one.
-  // (Measured and removed in round 3: per-layer dz buffers without back-pressure, 3-4 ping-pong buffers, releasing a
-  // weight gradient only after its layer's data gradient — none faster)
+  // dz goes round the buffers of `ring` so that the layers below L can write their dz while wgrad(L) still reads its own.
+  // (Measured and removed in round 3: per-layer dz buffers without back-pressure, 3-4 ping-pong buffers with a wait per
+  // layer, releasing a weight gradient only after its layer's data gradient — none faster)
   bool wg_async = false;
   int wg_cus = 256;  // CUs the weight-gradient launches are sized for (sched::wg_side_cus; MIMO_WGRAD_CUS overrides)
   // test hook (MIMO_DEBUG_WGRAD_DELAY_US, read per plan): an idle kernel of that many microseconds in front of every weight
@@ -198,26 +295,9 @@ struct mimo_plan {
   // fp32 storage, MIMO_FUSE_BWD_SRC=0 switches it off (read per plan)
   bool fuse_bwd_src = false;
   bool fuse_bwd_pool = false, fuse_bwd_head = false;  // (MIMO_FUSE_BWD_SRC=2: pooled tensors only, 3: head only — A/B)
-  hipStream_t wg_stream = nullptr;
-#ifndef MIMO_DZ_BUFS
-// dz buffers (with their max |dz| slots) the side stream's weight gradients may lag behind.  Round 6: 4 buffers, released in
-// PAIRS — the main stream waits for the side stream once per two layers (in front of an even buffer, for the event of the odd
-// one behind it: the side stream is in order, so that covers both) instead of once per layer.  A cross-stream wait in front
-// of a kernel costs the waiting stream ~4 us on this stack even when it is already satisfied (scripts/micro/event_cost.hip);
-// 2 buffers with a wait per layer (rounds 2-5) remain as the A/B build -DMIMO_DZ_BUFS=2.
-#define MIMO_DZ_BUFS 4
-#endif
-  static constexpr int kDzBufs = MIMO_DZ_BUFS;
-  static constexpr int wg_bufs = kDzBufs;
-  hipEvent_t ev_dz[kDzBufs] = {}, ev_wg[kDzBufs] = {}, ev_join = nullptr, ev_stage = nullptr;
-  bool wg_pending[kDzBufs] = {};
-  float* s_dz2[kDzBufs] = {};
-  float* s_dzmax2[kDzBufs] = {};  // per-workgroup maxima of |dz| of the tensor in s_dz2[i] (two-MFMA weight gradient)
-  // split (bf16 hi|lo) copy of dz for layers whose data gradient runs on the fp32 kernel while the weight
-  // gradient runs on the bf16-pair kernel (fewer than 16 output channels); null when no layer needs it
-  float* s_dzs2[kDzBufs] = {};
+  DzRing ring;  // dz buffers, their events and the side stream (ring.side)
+  hipEvent_t ev_stage = nullptr;
   bool any_mixed_dz = false;
-  int dz_idx = 0;
 
   // optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline)
   struct ProfRec {
@@ -369,14 +449,9 @@ struct mimo_plan {
   bool derived_dgrad = false;     // ... including the data-gradient weight copies
   bool need_derive = true;        // per-call: (re)pack weights and eval BN constants in this forward
   int64_t encoder_param_floats = 0;
-  // mimo_input_gradient (evaluation-grade backward: the data-gradient chain only).  ig_only is set while it walks the stages:
-  // convbn_backward then launches the BatchNorm-backward apply pass and the data gradient and nothing else.
-  bool ig_only = false;
   float* s_zero = nullptr;        // max cout_p zeros, never written: c1 / c2 of the apply pass after an eval-mode forward
   size_t cap_cout = 0;
   int64_t dgrad_version = -1;     // derived_version the data-gradient weight images were packed at by mimo_input_gradient (-1: none)
-  float* ig_dimage = nullptr;     // per call: the image gradient [N,Ci,H,W] the encoders' first-layer data gradients are folded into
-  bool ig_accumulate = false;     // ... the first fold adds to what is there
   float* out = nullptr;
   const float *label = nullptr, *lmask = nullptr;
   std::vector<const float*> elem_masks;  // [1 + S] element-wise dropout multipliers of the last forward (or empty)
@@ -394,11 +469,6 @@ struct mimo_plan {
     }
     drop_graphs();
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    if (wg_stream) (void)hipStreamDestroy(wg_stream);
-    for (int i = 0; i < kDzBufs; ++i)
-      for (hipEvent_t e : {ev_dz[i], ev_wg[i]})
-        if (e) (void)hipEventDestroy(e);
-    if (ev_join) (void)hipEventDestroy(ev_join);
     if (ev_stage) (void)hipEventDestroy(ev_stage);
   }
 
@@ -817,7 +887,6 @@ struct mimo_plan {
     // ---- scratch ----
     const int fp = pad_channels(f);
     cap_partial = std::max(cap_partial, (size_t)kEwMaxBlocks * (Co * fp + Co));
-    cap_sums = std::max(cap_sums, (size_t)kMaxChunks * 2 * round_up(Co * fp + Co, 64));
     if (cfg.inference_only == 1) cap_act = cap_pad = 1;  // backward scratch: never touched
     if (cfg.inference_only) cap_slab = 1;               // weight-gradient slabs
     if (cfg.inference_only != 1) MIMO_TRY(dalloc(&s_zero, cap_cout));
@@ -826,21 +895,21 @@ struct mimo_plan {
       const char* we = getenv("MIMO_WGRAD_STREAM");
       // default ON (round 2): the weight gradient of layer L runs on a side stream beside the BatchNorm-backward /
       // gather kernels of layer L-1 (bandwidth-bound: they co-reside with the persistent MFMA workgroup on a CU) and
-      // queues behind the data gradient of layer L; dz ping-pongs between wg_bufs buffers.  Measured +1.7 ... +4.7 %
+      // queues behind the data gradient of layer L; dz goes round DzRing::kSlots buffers.  Measured +1.7 ... +4.7 %
       // images/s on three boxes (within noise on a fourth); results are bit-identical to the single-stream order.
       // With the profiler armed (bench.py's second pass) everything runs on the caller's stream.
       wg_async = !(we && atoi(we) == 0) && !cfg.inference_only;
-      for (int i = 0; i < kDzBufs; ++i) s_dz2[i] = s_dz;
+      for (int i = 0; i < DzRing::kSlots; ++i) ring.dz[i] = s_dz;
       if (!cfg.inference_only)
-        for (int i = 0; i < kDzBufs; ++i) MIMO_TRY(dalloc(&s_dzmax2[i], kDzMaxSlots));
+        for (int i = 0; i < DzRing::kSlots; ++i) MIMO_TRY(dalloc(&ring.dzmax[i], kDzMaxSlots));
       if (any_mixed_dz && !cfg.inference_only) {  // (read by weight gradients only)
-        MIMO_TRY(dalloc(&s_dzs2[0], cap_act));
-        for (int i = 1; i < kDzBufs; ++i) s_dzs2[i] = s_dzs2[0];
+        MIMO_TRY(dalloc(&ring.dzs[0], cap_act));
+        for (int i = 1; i < DzRing::kSlots; ++i) ring.dzs[i] = ring.dzs[0];
         if (wg_async)
-          for (int i = 1; i < wg_bufs; ++i) MIMO_TRY(dalloc(&s_dzs2[i], cap_act));
+          for (int i = 1; i < DzRing::kSlots; ++i) MIMO_TRY(dalloc(&ring.dzs[i], cap_act));
       }
       if (wg_async) {
-        for (int i = 1; i < wg_bufs; ++i) MIMO_TRY(alloc_act(&s_dz2[i], cap_act, st));
+        for (int i = 1; i < DzRing::kSlots; ++i) MIMO_TRY(alloc_act(&ring.dz[i], cap_act, st));
         // LOWEST stream priority — not for the scheduling (round 4 measured no effect of the priority on the step) but for the
         // hardware queue: the runtime deals streams of one priority class round-robin onto a handful of hardware queues
         // (4 by default), and a side stream that lands on the caller's queue is silently serialised behind it — seen in
@@ -851,13 +920,13 @@ struct mimo_plan {
           int least = 0, greatest = 0;
           MIMO_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
           if (least != greatest)
-            MIMO_HIP_CHECK(hipStreamCreateWithPriority(&wg_stream, hipStreamNonBlocking, least));
+            MIMO_HIP_CHECK(hipStreamCreateWithPriority(&ring.side, hipStreamNonBlocking, least));
           else
-            MIMO_HIP_CHECK(hipStreamCreateWithFlags(&wg_stream, hipStreamNonBlocking));
+            MIMO_HIP_CHECK(hipStreamCreateWithFlags(&ring.side, hipStreamNonBlocking));
         }
-        for (int i = 0; i < wg_bufs; ++i)
-          for (hipEvent_t* e : {&ev_dz[i], &ev_wg[i]}) MIMO_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        MIMO_HIP_CHECK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+        for (int i = 0; i < DzRing::kSlots; ++i)
+          for (hipEvent_t* e : {&ring.ev_dz[i], &ring.ev_wg[i]}) MIMO_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        MIMO_HIP_CHECK(hipEventCreateWithFlags(&ring.ev_join, hipEventDisableTiming));
         MIMO_HIP_CHECK(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming));
       }
     }
@@ -868,7 +937,6 @@ struct mimo_plan {
     MIMO_TRY(dalloc(&s_partial, cap_partial));
     if (fuse_bwd_src && !cfg.inference_only) MIMO_TRY(dalloc(&s_headpart, (size_t)kBnReduceMaxBlocks * (2 * pad_channels(f) + 2)));
     MIMO_TRY(dalloc(&s_sums, cap_sums));
-    MIMO_TRY(dalloc(&s_tickets, kColsumMaxGroups));
     MIMO_TRY(dalloc(&s_losspart, (size_t)S * 512));
     MIMO_TRY(dalloc(&d_status, 1));
     // ---- weight repack job tables ----
@@ -1042,7 +1110,7 @@ struct mimo_plan {
       if (rows <= kColsumMaxRows) {
         MIMO_TRY(bn_fwd_stats_launch(s_partial, rows, L.cout_pad, L.Cout, L.cout_p, P, params + L.off_gamma,
                                      params + L.off_beta, bnbuf + L.off_rm, bnbuf + L.off_rv, cfg.bn_momentum, cfg.bn_eps,
-                                     L.mean, L.invstd, L.scale, L.shift, colsum(), st));
+                                     L.mean, L.invstd, L.scale, L.shift, d_status, st));
       } else {
         int chunks = 0;
         MIMO_TRY(rowsum_launch(s_partial, rows, 2 * L.cout_pad, s_sums, &chunks, st));
@@ -1398,96 +1466,79 @@ struct mimo_plan {
     return MIMO_OK;
   }
 
+  // algorithmic bytes of the gradient source per pixel and channel (z and dz are counted by the passes themselves): the pooled
+  // gradient is a quarter of the image, the head's logits / labels a few floats per pixel
+  static double src_bytes(const GradSrc& src) {
+    return src.kind == GS_POOL ? (1.0 + (src.skip ? 4.0 : 0.0)) : src.kind == GS_HEAD ? 0.5 : 4.0;
+  }
+
+  // pass 2 of the BatchNorm + ReLU backward of layer L: dz = scale * (dy - c1 - xhat * c2) into `dz`
+  // partial != nullptr: + partial rows of sum dz; absmax / done: bn_bwd_apply_launch
+  int bn_apply(ConvBN& L, const GradSrc& src, const float* mask, const float* c1, const float* c2, float* dz, bool split_out,
+               float* partial, int* rows, hipStream_t st, float* absmax = nullptr, int* absmax_n = nullptr, hipEvent_t done = nullptr) {
+    const int64_t P = (int64_t)L.N * L.H * L.W;
+    const int pr = prof_begin(MIMO_PROF_BN_BWD_APPLY, st);
+    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, c1, c2,
+                                 L.cout_p, L.N, L.H, L.W, dz, split_out ? 1 : 0, partial, rows, st, absmax, absmax_n, done));
+    prof_end(pr, 0.0, (8.0 + src_bytes(src)) * (double)P * L.cout_p, st);
+    return MIMO_OK;
+  }
+
   // mimo_input_gradient's form of convbn_backward: after an eval-mode forward BatchNorm is the fixed affine map of its running
   // statistics, so its backward is dz = scale * relu'(.) * dy — bn_bwd_apply_kernel with c1 = c2 = 0 (the constant zero vector
   // s_zero; mimo_backward's eval branch reaches the same zeros through the reduction pass and bn_bwd_stats_kernel, and the same
   // bits).  No reduction, no column sums, no max |dz| slots, no event, nothing written outside the plan's scratch.
   int convbn_input_grad(ConvBN& L, const GradSrc& src, const float* mask, float* dxpad_out, hipStream_t st) {
-    const int64_t P = (int64_t)L.N * L.H * L.W;
-    const double src_b = src.kind == GS_POOL ? (1.0 + (src.skip ? 4.0 : 0.0)) : src.kind == GS_HEAD ? 0.5 : 4.0;
-    float* dz = s_dz2[0];
+    float* dz = ring.dz[0];
     int rows = 0;
-    const int pr = prof_begin(MIMO_PROF_BN_BWD_APPLY, st);
-    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, s_zero,
-                                 s_zero, L.cout_p, L.N, L.H, L.W, dz, (L.dg_split && !mixed) ? 1 : 0, nullptr, &rows, st));
-    prof_end(pr, 0.0, (8.0 + src_b) * (double)P * L.cout_p, st);
+    MIMO_TRY(bn_apply(L, src, mask, s_zero, s_zero, dz, L.dg_split && !mixed, nullptr, &rows, st));
     return dgrad_conv(L, dz, dxpad_out, st);
   }
 
-  // `src`: where the gradient arriving at L's activation comes from (GradSrc, elementwise.h)
-  int convbn_backward(ConvBN& L, const GradSrc& src, const float* mask, bool need_dgrad, float* dxpad_out, hipStream_t st) {
-    if (ig_only) return need_dgrad ? convbn_input_grad(L, src, mask, dxpad_out, st) : MIMO_OK;
+  // BatchNorm + ReLU backward of layer L (`src`: where the gradient arriving at L's activation comes from, GradSrc,
+  // elementwise.h): BatchNorm parameter gradients, dz into slot `s` of the ring — released to the weight gradient behind its
+  // last writer — and the convolution's bias gradient.  training: the forward used batch statistics.
+  // thin_wg: the weight gradient reads dz as fp32 and nothing else reads it.
+  int bn_backward(ConvBN& L, const GradSrc& src, const float* mask, DzRing::Slot& s, bool training, bool thin_wg, hipStream_t st) {
     int rows = 0;
     const int64_t P = (int64_t)L.N * L.H * L.W;
-    // algorithmic bytes of the source per pixel and channel (z and dz are counted below): the pooled gradient is a quarter
-    // of the image, the head's logits / labels a few floats per pixel
-    const double src_b = src.kind == GS_POOL ? (1.0 + (src.skip ? 4.0 : 0.0)) : src.kind == GS_HEAD ? 0.5 : 4.0;
-    int pr = prof_begin(MIMO_PROF_BN_BWD_REDUCE, st);
+    const int pr = prof_begin(MIMO_PROF_BN_BWD_REDUCE, st);
     MIMO_TRY(bnrelu_bwd_reduce_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd,
                                       mask, L.Cout, L.cout_p, L.N, L.H, L.W, s_partial, &rows, st));
-    prof_end(pr, 0.0, (4.0 + src_b) * (double)P * L.cout_p, st);
+    prof_end(pr, 0.0, (4.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     if (src.kind == GS_HEAD) head_rows = rows;
-    MIMO_TRY(bn_bwd_stats_launch(s_partial, rows, L.Cout, L.cout_p, P, fwd_training ? 1 : 0, L.c1, L.c2,
-                                 grads + L.off_gamma, grads + L.off_beta, fwd_training ? grads + L.off_b : nullptr, colsum(), st));
-    // (with the profiler armed everything runs on the caller's stream: per-kernel times, not overlapped times)
-    const bool async = wg_async && !prof_on;
-    const int b = dz_idx;
-    float* dz = s_dz2[b];
-    if (async) {
-      dz_idx = (dz_idx + 1) % wg_bufs;
-      // last reader of this dz buffer (and, released in pairs, of the one after it)
-      if (kDzBufs >= 4 && (kDzBufs & 1) == 0) {
-        if ((b & 1) == 0) {
-          const int w = wg_pending[b + 1] ? b + 1 : b;
-          if (wg_pending[w]) MIMO_HIP_CHECK(hipStreamWaitEvent(st, ev_wg[w], 0));
-          wg_pending[b] = wg_pending[b + 1] = false;  // (their last readers are behind this wait)
-        } else if (wg_pending[b]) {  // not covered by the pair's wait: cannot happen in cyclic order, kept as the safe path
-          MIMO_HIP_CHECK(hipStreamWaitEvent(st, ev_wg[b], 0));
-        }
-      } else if (wg_pending[b]) {
-        MIMO_HIP_CHECK(hipStreamWaitEvent(st, ev_wg[b], 0));
-      }
-    }
-    // the image convolution's weight gradient on the plain-FMA kernel reads dz as fp32 (no data gradient wanted: nothing
-    // else reads this dz)
-    const bool thin_wg = L.thin && !mixed && !need_dgrad && wgrad_thin_ok(L.Cin, L.cout_p, L.N, L.H, L.W);
-    pr = prof_begin(MIMO_PROF_BN_BWD_APPLY, st);
-    int dzmax_n = 0;  // per-workgroup maxima of |dz| that launch leaves (two-MFMA weight gradient)
-    // "dz exists" travels with the launch that writes it (a stop event on the kernel, no hipEventRecord behind it) whenever that
-    // launch is the last writer — not when a split copy of dz follows — and not under stream capture
-    const bool needs_split_copy = L.wg_split && !L.dg_split && !thin_wg;
-    const bool ev_on_launch = async && !capturing && !needs_split_copy;
-    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask,
-                                 L.Cout, L.c1, L.c2, L.cout_p, L.N, L.H, L.W, dz, (L.dg_split && !mixed && !thin_wg) ? 1 : 0,
-                                 fwd_training ? nullptr : s_partial, &rows, st, (L.wg_np2 && !thin_wg) ? s_dzmax2[b] : nullptr,
-                                 &dzmax_n, ev_on_launch ? ev_dz[b] : nullptr));
-    prof_end(pr, 0.0, (8.0 + src_b) * (double)P * L.cout_p, st);
+    MIMO_TRY(bn_bwd_stats_launch(s_partial, rows, L.Cout, L.cout_p, P, training ? 1 : 0, L.c1, L.c2, grads + L.off_gamma,
+                                 grads + L.off_beta, training ? grads + L.off_b : nullptr, d_status, st));
+    MIMO_TRY(ring.wait_free(s, st));
+    float* dz = ring.dz[s.b];
     // dz storage: bf16 hi|lo pairs when the data-gradient kernel is the bf16-pair one (then the weight
     // gradient is too); fp32 otherwise, with a split copy for a bf16-pair weight gradient
-    const float* dz_wg = dz;
+    const bool needs_split_copy = L.wg_split && !L.dg_split && !thin_wg;
+    if (L.wg_np2 && !thin_wg) s.absmax = ring.dzmax[s.b];  // (travels with the dz buffer it describes: same slot, same events)
+    MIMO_TRY(bn_apply(L, src, mask, L.c1, L.c2, dz, L.dg_split && !mixed && !thin_wg, training ? nullptr : s_partial, &rows, st,
+                      s.absmax, &s.absmax_n, ring.dz_event_on_launch(s, capturing, needs_split_copy)));
+    s.dz_wg = dz;
     if (needs_split_copy) {
-      float* dzs = s_dzs2[b];
-      MIMO_TRY(split_pairs_launch(dz, dzs, P, L.cout_p, st));
-      dz_wg = dzs;
+      MIMO_TRY(split_pairs_launch(dz, ring.dzs[s.b], P, L.cout_p, st));
+      s.dz_wg = ring.dzs[s.b];
     }
-    // wgrad(L) may start as soon as dz exists, next to dgrad(L)
-    if (async && !ev_on_launch) MIMO_HIP_CHECK(hipEventRecord(ev_dz[b], st));
+    MIMO_TRY(ring.dz_written(s, st));
     // conv bias gradient: exactly zero in front of a training-mode BatchNorm (written by bn_bwd_stats above);
     // a real column sum of dz only after an eval-mode forward (running statistics: dz = scale * dy)
-    if (!fwd_training) MIMO_TRY(colsum_vec_launch(s_partial, rows, L.cout_p, L.Cout, grads + L.off_b, colsum(), st));
-    if (need_dgrad) MIMO_TRY(dgrad_conv(L, dz, dxpad_out, st));
-    hipStream_t ws = st;
-    if (async) {
-      MIMO_HIP_CHECK(hipStreamWaitEvent(wg_stream, ev_dz[b], 0));  // (a wait refers to the record made just above)
-      ws = wg_stream;
-    }
+    if (!training) MIMO_TRY(colsum_vec_launch(s_partial, rows, L.cout_p, L.Cout, grads + L.off_b, st));
+    return MIMO_OK;
+  }
+
+  // weight gradient of layer L and its reduction on `ws`; release != nullptr: recorded when the reduction completes
+  int wgrad_issue(ConvBN& L, const DzRing::Slot& o, bool thin_wg, hipStream_t ws, hipEvent_t release) {
+    const int64_t P = (int64_t)L.N * L.H * L.W;
     WgradLaunch wg;
     wg.x = L.fuse_in ? L.in_z : L.in;
     if (L.fuse_in) {
       wg.in_scale = L.in_scale;
       wg.in_shift = L.in_shift;
     }
-    wg.dz = dz_wg;
+    wg.dz = o.dz_wg;
     wg.partial = s_wslab;
     wg.N = L.N;
     wg.H = L.H;
@@ -1500,56 +1551,53 @@ struct mimo_plan {
     wg.cout_pad = L.wg_cout_pad;
     wg.splits = L.wg_splits;
     wg.np = (cfg.precision == MIMO_PREC_BF16 || mixed) ? 1 : 3;
-    if (L.wg_np2 && wg.np == 3 && !thin_wg) {  // two fp16 MFMAs per product (wgrad_split.hip NP == 2)
+    if (o.absmax && wg.np == 3) {  // two fp16 MFMAs per product (wgrad_split.hip NP == 2)
       wg.np = 2;
-      wg.dz_absmax = s_dzmax2[b];  // (travels with the dz buffer it describes: same ping-pong index, same events)
-      wg.dz_absmax_n = dzmax_n;
+      wg.dz_absmax = o.absmax;
+      wg.dz_absmax_n = o.absmax_n;
     }
     // 16-bit storage: activations and dz plain NHWC 16-bit; the image convolution's input stays fp32
     wg.store = !mixed ? 0 : (L.fwd_split ? (f16 ? 2 : 1) : (f16 ? 4 : 3));
     if (wg_delay_us > 0) MIMO_TRY(debug_delay_launch(wg_delay_us, ws));  // test hook: a late consumer
-    pr = prof_begin(MIMO_PROF_CONV_WGRAD, ws);
-    if (thin_wg)
-      MIMO_TRY(wgrad_thin_launch(L.in, L.ld_in, dz, L.cout_p, L.N, L.H, L.W, L.Cin, L.Cout, L.cout_p, s_wslab, grads + L.off_w, ws));
+    const int pr = prof_begin(MIMO_PROF_CONV_WGRAD, ws);
+    if (thin_wg)  // (dz as fp32, straight from the BatchNorm backward)
+      MIMO_TRY(wgrad_thin_launch(L.in, L.ld_in, o.dz_wg, L.cout_p, L.N, L.H, L.W, L.Cin, L.Cout, L.cout_p, s_wslab, grads + L.off_w, ws));
     else if (L.wg_split)
       MIMO_TRY(wgrad_split_launch(wg, ws));
     else
       MIMO_TRY(wgrad_launch(wg, ws));
     prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), ws);
-    const bool wg_ev_on_launch = async && !capturing && !thin_wg;
     if (!thin_wg)  // (the plain-FMA kernel's launch reduces its own partials)
       MIMO_TRY(wgrad_reduce_launch(s_wslab, L.wg_splits, L.wg_cin_pad, L.wg_cout_pad, L.cin_map, L.cin_p, L.Cin, L.Cout,
-                                   grads + L.off_w, ws, wg.dz_absmax, wg.dz_absmax_n, wg_ev_on_launch ? ev_wg[b] : nullptr));
-    if (async) {
-      // dz buffer b AND its max |dz| slots are free again — recorded behind the REDUCTION: it reads the slots too (to take the
-      // two-MFMA kernel's scale out again), and the BatchNorm backward of the layer after next overwrites them.  (Until the
-      // end of round 5 the event sat in front of the reduction: a race that showed as a weight gradient off by > 1e-4 of
-      // its scale in one small-geometry test when that test ran alone.)
-      if (!wg_ev_on_launch) MIMO_HIP_CHECK(hipEventRecord(ev_wg[b], wg_stream));
-      wg_pending[b] = true;
-    }
+                                   grads + L.off_w, ws, wg.dz_absmax, wg.dz_absmax_n, release));
     return MIMO_OK;
   }
 
-  // the caller's stream waits for every weight gradient issued so far
-  int wg_join(hipStream_t st) {
-    bool any = false;
-    for (bool p : wg_pending) any |= p;
-    if (!wg_async || !any) return MIMO_OK;
-    MIMO_HIP_CHECK(hipEventRecord(ev_join, wg_stream));
-    MIMO_HIP_CHECK(hipStreamWaitEvent(st, ev_join, 0));
-    for (bool& p : wg_pending) p = false;
-    return MIMO_OK;
+  int convbn_backward(ConvBN& L, const GradSrc& src, const float* mask, bool need_dgrad, float* dxpad_out, const BwdCall& call,
+                      hipStream_t st) {
+    if (call.ig) return need_dgrad ? convbn_input_grad(L, src, mask, dxpad_out, st) : MIMO_OK;
+    // the image convolution's weight gradient on the plain-FMA kernel reads dz as fp32 (no data gradient wanted: nothing
+    // else reads this dz)
+    const bool thin_wg = L.thin && !mixed && !need_dgrad && wgrad_thin_ok(L.Cin, L.cout_p, L.N, L.H, L.W);
+    // (with the profiler armed everything runs on the caller's stream: per-kernel times, not overlapped times)
+    DzRing::Slot s = ring.acquire(wg_async && !prof_on);
+    MIMO_TRY(bn_backward(L, src, mask, s, fwd_training, thin_wg, st));
+    if (need_dgrad) MIMO_TRY(dgrad_conv(L, ring.dz[s.b], dxpad_out, st));
+    hipStream_t ws = st;
+    MIMO_TRY(ring.reader_stream(s, st, &ws));
+    const hipEvent_t release = ring.release_on_launch(s, capturing, thin_wg);
+    MIMO_TRY(wgrad_issue(L, s, thin_wg, ws, release));
+    return ring.released(s, release != nullptr);
   }
 
-  int dc_backward(DoubleConv* dc, bool need_input_grad, hipStream_t st, const GradSrc* head_src = nullptr) {
+  int dc_backward(DoubleConv* dc, bool need_input_grad, const BwdCall& call, hipStream_t st, const GradSrc* head_src = nullptr) {
     const int blk = prof_begin(kProfTierBase + 2 * tier_of(dc->c1.H) + 1, st);
-    const int rc = dc_backward_impl(dc, need_input_grad, st, head_src);
+    const int rc = dc_backward_impl(dc, need_input_grad, call, st, head_src);
     prof_end(blk, 0.0, 0.0, st);
     return rc;
   }
 
-  int dc_backward_impl(DoubleConv* dc, bool need_input_grad, hipStream_t st, const GradSrc* head_src = nullptr) {
+  int dc_backward_impl(DoubleConv* dc, bool need_input_grad, const BwdCall& call, hipStream_t st, const GradSrc* head_src) {
     GradSrc src = GradSrc::plain(dc->out.da, dc->out.ldda);
     {
       const Act* root = dc->out.parent ? dc->out.parent : &dc->out;
@@ -1564,9 +1612,9 @@ struct mimo_plan {
         src.choff = src.skoff = dc->out.parent ? dc->out.parent_choff : 0;
       }
     }
-    MIMO_TRY(convbn_backward(dc->c2, src, dc->mask, true, s_dxpadA, st));
+    MIMO_TRY(convbn_backward(dc->c2, src, dc->mask, true, s_dxpadA, call, st));
     float* dxB = dc->dxpad_own ? dc->dxpad_own : s_dxpadB;
-    MIMO_TRY(convbn_backward(dc->c1, GradSrc::fold(s_dxpadA, dc->c1.cout_p), nullptr, need_input_grad, dxB, st));
+    MIMO_TRY(convbn_backward(dc->c1, GradSrc::fold(s_dxpadA, dc->c1.cout_p), nullptr, need_input_grad, dxB, call, st));
     if (!need_input_grad) return MIMO_OK;
     const int h = dc->c1.H, w = dc->c1.W, ldp = dc->c1.cin_p;
     if (dc->kind == IN_POOL && fuse_bwd_pool && dc->dxpad_own && dc->src0->grad_writes == 0) {
@@ -1669,8 +1717,8 @@ struct mimo_plan {
       if (train_graph && !ready && fwd_graphed && loss_staged && fwd_training && !prof_on && !dout && !dx && dloss && (whole || single) &&
           tg_captures < kMaxTrainCaptures) {
         const uint64_t key = (tg_fwd_key << 3) | (lmask ? 4 : 0) | (lperm ? 2 : 0) | (whole ? 1 : 0);
-        bool ready = tg_bwd_key == key && (whole ? tg_bwd[kBwdStages] != nullptr : tg_bwd[0] != nullptr);
-        if (!ready && tg_bwd_seen == key) {
+        bool have_graphs = tg_bwd_key == key && (whole ? tg_bwd[kBwdStages] != nullptr : tg_bwd[0] != nullptr);
+        if (!have_graphs && tg_bwd_seen == key) {
           for (auto& e : tg_bwd) {
             if (e) (void)hipGraphExecDestroy(e);
             e = nullptr;
@@ -1678,27 +1726,28 @@ struct mimo_plan {
           tg_bwd_key = 0;
           // (a capture executes nothing: the stages can be captured one after the other, each on the host state — gradient
           // routing of the activation tensors — the stage before it left)
+          const BwdCall staged{nullptr, g_dloss};
           if (whole) {
             MIMO_TRY(capture([&](hipStream_t cs) {
-              dz_idx = 0;
-              for (int stage = 0; stage < kBwdStages; ++stage) MIMO_TRY(backward_stage(stage, nullptr, g_dloss, nullptr, cs));
-              return wg_join(cs);
+              ring.policy.rewind();
+              for (int stage = 0; stage < kBwdStages; ++stage) MIMO_TRY(backward_stage(stage, staged, cs));
+              return ring.join(cs);
             }, &tg_bwd[kBwdStages]));
           } else {
             for (int stage = 0; stage < kBwdStages; ++stage)
               MIMO_TRY(capture([&](hipStream_t cs) {
-                dz_idx = 0;
-                MIMO_TRY(backward_stage(stage, nullptr, g_dloss, nullptr, cs));
-                return wg_join(cs);
+                ring.policy.rewind();
+                MIMO_TRY(backward_stage(stage, staged, cs));
+                return ring.join(cs);
               }, &tg_bwd[stage]));
           }
           tg_bwd_key = key;
           ++tg_captures;
-          ready = true;
+          have_graphs = true;
         }
         tg_bwd_seen = key;
-        tg_bwd_live = ready;
-        if (ready) MIMO_HIP_CHECK(hipMemcpyAsync(g_dloss, dloss, (size_t)S * sizeof(float), hipMemcpyDeviceToDevice, st));
+        tg_bwd_live = have_graphs;
+        if (have_graphs) MIMO_HIP_CHECK(hipMemcpyAsync(g_dloss, dloss, (size_t)S * sizeof(float), hipMemcpyDeviceToDevice, st));
       }
     }
     if (tg_bwd_live && !dout && !dx && (whole || stage_first == stage_last)) {
@@ -1715,18 +1764,19 @@ struct mimo_plan {
       set_error("mimo_backward: stage %d..%d differs from what stage 0 of this backward was called with", stage_first, stage_last);
       return MIMO_ERR_STATE;
     }
-    for (int stage = stage_first; stage <= stage_last; ++stage) MIMO_TRY(backward_stage(stage, dout, dloss, dx, st));
+    const BwdCall call{dout, dloss, dx};
+    for (int stage = stage_first; stage <= stage_last; ++stage) MIMO_TRY(backward_stage(stage, call, st));
     bwd_next_stage = stage_last + 1 < kBwdStages ? stage_last + 1 : 0;
     if (ready && wg_async && !prof_on && stage_last < kBwdStages - 1) {
       MIMO_HIP_CHECK(hipEventRecord(ev_stage, st));
-      MIMO_HIP_CHECK(hipStreamWaitEvent(wg_stream, ev_stage, 0));
-      *ready = wg_stream;
+      MIMO_HIP_CHECK(hipStreamWaitEvent(ring.side, ev_stage, 0));
+      *ready = ring.side;
       return MIMO_OK;
     }
-    return wg_join(st);  // the gradients of the stages run so far are final for the caller (all-reduce)
+    return ring.join(st);  // the gradients of the stages run so far are final for the caller (all-reduce)
   }
 
-  int backward_stage(int stage, const float* dout, const float* dloss, float* dx, hipStream_t st) {
+  int backward_stage(int stage, const BwdCall& call, hipStream_t st) {
     switch (stage) {
       case 0: {
         for (auto& dc : dcs) {
@@ -1737,7 +1787,7 @@ struct mimo_plan {
         x2cat.grad_writes = 0;
         x2cat.skipgrad = nullptr;
         x2cat.poolgrad = nullptr;
-        if (!fwd_training && !ig_only) {  // eval-mode forward skipped the dgrad weight packing
+        if (!fwd_training && !call.ig) {  // eval-mode forward skipped the dgrad weight packing
           MIMO_TRY(pack_all(true, st));
         }
         const int fp = pad_channels(f);
@@ -1750,12 +1800,12 @@ struct mimo_plan {
             // head_bwd is not launched, the gradient of the decoder output is never written
             GradSrc hs;
             hs.kind = GS_HEAD;
-            hs.head = HeadGrad{params + heads[s].off_w, f, Co, N, S, s, H * W, out, dout, dloss, label, lmask, lperm, cfg.loss_kind,
+            hs.head = HeadGrad{params + heads[s].off_w, f, Co, N, S, s, H * W, out, call.dout, call.dloss, label, lmask, lperm, cfg.loss_kind,
                                cfg.eps_min, cfg.eps_max, 1.f / (float)((double)N * (Co / 2) * H * W), s_headpart};
-            MIMO_TRY(dc_backward(dc, true, st, &hs));
-            if (ig_only) continue;  // (no head weight / bias gradient)
+            MIMO_TRY(dc_backward(dc, true, call, st, &hs));
+            if (call.ig) continue;  // (no head weight / bias gradient)
             // (the head's partial rows: one per workgroup of that reduction)
-            MIMO_TRY(head_bwd_stats_launch(s_headpart, head_rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, colsum(), st));
+            MIMO_TRY(head_bwd_stats_launch(s_headpart, head_rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, st));
             continue;
           }
           const int blk = prof_begin(kProfTierBase + 1, st);
@@ -1764,24 +1814,24 @@ struct mimo_plan {
           const Act& o = dc->out;
           const bool oz = o.z_live;
           MIMO_TRY(head_bwd_launch(oz ? o.z : o.a, this->st, oz ? o.z_ld : o.ld, params + heads[s].off_w, f, fp, Co, N, S, s, H * W,
-                                   out, dout, dloss, label, lmask, lperm, cfg.loss_kind, cfg.eps_min, cfg.eps_max, dc->out.da,
+                                   out, call.dout, call.dloss, label, lmask, lperm, cfg.loss_kind, cfg.eps_min, cfg.eps_max, dc->out.da,
                                    s_partial, &rows, st, oz ? o.z_scale : nullptr, oz ? o.z_shift : nullptr));
           prof_end(pr, 0.0, 4.0 * (double)N * H * W * (2.0 * fp + Co + Co / 2), st);
-          if (!ig_only)
-            MIMO_TRY(head_bwd_stats_launch(s_partial, rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, colsum(), st));
+          if (!call.ig)
+            MIMO_TRY(head_bwd_stats_launch(s_partial, rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, st));
           if (em || elem_rng_on[1 + s]) {
             const ElemRng g = elem_rng(1 + s);
             MIMO_TRY(elem_mask_mul_launch(dc->out.da, this->st, dc->out.ldda, em, N, dc->out.C, dc->out.Cp, H * W, st,
                                           em ? nullptr : &g));
           }
           prof_end(blk, 0.0, 0.0, st);
-          MIMO_TRY(dc_backward(dc, true, st));
+          MIMO_TRY(dc_backward(dc, true, call, st));
         }
         return MIMO_OK;
       }
-      case 1: return dc_backward(up3, true, st);
-      case 2: return dc_backward(up2, true, st);
-      case 3: return dc_backward(up1, true, st);
+      case 1: return dc_backward(up3, true, call, st);
+      case 2: return dc_backward(up2, true, call, st);
+      case 3: return dc_backward(up1, true, call, st);
       case 4:
         {
           const float* em = elem_masks.empty() ? nullptr : elem_masks[0];
@@ -1791,10 +1841,10 @@ struct mimo_plan {
                                           down4->out.H * down4->out.W, st, em ? nullptr : &g));
           }
         }
-        return dc_backward(down4, true, st);
-      case 5: return dc_backward(down3, true, st);
-      case 6: return dc_backward(down2, true, st);
-      default: return backward_encoders(dx, st);
+        return dc_backward(down4, true, call, st);
+      case 5: return dc_backward(down3, true, call, st);
+      case 6: return dc_backward(down2, true, call, st);
+      default: return backward_encoders(call, st);
     }
   }
 
@@ -1834,24 +1884,19 @@ struct mimo_plan {
       MIMO_TRY(pack_jobs_launch(pack_jobs + n_fwd_jobs, n_all_jobs - n_fwd_jobs, pack_max_total, params, st));
       dgrad_version = derived_version;
     }
-    ig_only = true;
-    ig_dimage = dimage;
-    ig_accumulate = accumulate != 0;
-    int rc = MIMO_OK;
-    for (int stage = 0; stage < kBwdStages && rc == MIMO_OK; ++stage) rc = backward_stage(stage, dout, dloss, nullptr, st);
-    ig_only = false;
-    ig_dimage = nullptr;
-    return rc;
+    const BwdCall call{dout, dloss, nullptr, true, dimage, accumulate != 0};
+    for (int stage = 0; stage < kBwdStages; ++stage) MIMO_TRY(backward_stage(stage, call, st));
+    return MIMO_OK;
   }
 
-  int backward_encoders(float* dx, hipStream_t st) {
-    for (int s = S - 1; s >= 0; --s) MIMO_TRY(dc_backward(down1[s], true, st));
+  int backward_encoders(const BwdCall& call, hipStream_t st) {
+    for (int s = S - 1; s >= 0; --s) MIMO_TRY(dc_backward(down1[s], true, call, st));
     for (int s = S - 1; s >= 0; --s) {
-      MIMO_TRY(dc_backward(enc_in[s], dx != nullptr || ig_only, st));
-      if (ig_only)  // s = S-1 assigns (or adds to the caller's values), S-2 ... 0 add: s_dxpadB is reused per encoder
-        MIMO_TRY(fold_image_grad_launch(s_dxpadB, Ci_p, N, Ci, H, W, ig_dimage, (s < S - 1 || ig_accumulate) ? 1 : 0, st));
-      else if (dx)
-        MIMO_TRY(unpack_dx_launch(s_dxpadB, this->st, Ci_p, N, S, s, Ci, H, W, dx, st));
+      MIMO_TRY(dc_backward(enc_in[s], call.dx != nullptr || call.ig, call, st));
+      if (call.ig)  // s = S-1 assigns (or adds to the caller's values), S-2 ... 0 add: s_dxpadB is reused per encoder
+        MIMO_TRY(fold_image_grad_launch(s_dxpadB, Ci_p, N, Ci, H, W, call.dimage, (s < S - 1 || call.accumulate) ? 1 : 0, st));
+      else if (call.dx)
+        MIMO_TRY(unpack_dx_launch(s_dxpadB, this->st, Ci_p, N, S, s, Ci, H, W, call.dx, st));
     }
     return MIMO_OK;
   }

@@ -7,9 +7,9 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_schedulers_under_asan_ubsan(tmp_path):
-    exe = str(tmp_path / "sched_test")
-    src = os.path.join(ROOT, "tests", "host", "sched_test.cpp")
+def _run_host_test(tmp_path, name):
+    exe = str(tmp_path / name)
+    src = os.path.join(ROOT, "tests", "host", name + ".cpp")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-Wall", "-Werror", src, "-o", exe], check=True, capture_output=True, text=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
@@ -18,11 +18,22 @@ def test_schedulers_under_asan_ubsan(tmp_path):
     assert "all checks passed" in r.stdout
 
 
+def test_schedulers_under_asan_ubsan(tmp_path):
+    _run_host_test(tmp_path, "sched_test")
+
+
+def test_dz_ring_policy_under_asan_ubsan(tmp_path):
+    """mimo_unet_amd/csrc/dz_ring.h: every sequence of layers, joins and rewinds of three trips round the ring, from a clean
+    ring and from what an abandoned staged backward leaves — no dz buffer is handed out under a weight gradient that still
+    reads it, and the waits are those of the logic the policy replaced (tests/host/dz_ring_test.cpp)."""
+    _run_host_test(tmp_path, "dz_ring_test")
+
+
 def test_kernels_use_the_tested_header():
     """No private copy of a scheduler is left in the .hip sources."""
     csrc = os.path.join(ROOT, "mimo_unet_amd", "csrc")
     for fn, needles in (("conv_bf16x3.hip", ["using sched::pick_tile_n"]), ("conv3x3.hip", ["sched::pick_tile_n", "sched::conv_cout_pad"]),
-                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus"]), ("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
+                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy"]), ("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
                         ("conv_wide.hip", ["sched::wide_config", "sched::wide_grid_x"])):
         text = open(os.path.join(csrc, fn)).read()
         for n in needles:
