@@ -19,6 +19,7 @@
 
 #include "dz_ring.h"
 #include "elementwise.h"
+#include "graph_replay.h"
 
 namespace mimo {
 
@@ -137,6 +138,31 @@ struct Head {
   int64_t off_w = 0, off_b = 0;
 };
 
+// What one forward was called with and what was decided for it (mimo_forward): built once by mimo_plan::forward, handed down by
+// const reference to the issuing functions, to prepare_forward in front of them and to record_forward behind them.  The
+// pointers are the caller's on the eager route, the plan's staging copies on the graph routes (staged_call).
+struct FwdCall {
+  static constexpr int kMaxSites = 56;  // Dropout2d sites (one per DoubleConv) + 1 + S element-wise ones: checked by build()
+  const float* x = nullptr;
+  int64_t stride_n = 0, stride_s = 0;
+  const int64_t* perm = nullptr;
+  int64_t rows = 0;  // rows of x (= rows of the label / mask tensors of that batch)
+  bool x5 = false, x4 = false;  // x is a dense [rows,S,Ci,H,W] / a dense [rows,Ci,H,W] shared by the subnetworks (stride_s = 0)
+  float* out = nullptr;
+  const float* masks[kMaxSites] = {};       // per DoubleConv: the Dropout2d multipliers in effect (the caller's or drawn in the engine)
+  const float* elem_masks[kMaxSites] = {};  // [1 + S] the caller's element-wise multipliers (center, final[s])
+  bool elem_rng_on[kMaxSites] = {};         // [1 + S] ... or drawn in the engine from (rng_seed, rng_offset)
+  // element-wise dropout in this call, the caller's or the engine's: off the hipGraph routes (the caller's array may hold
+  // nothing but null pointers and still counts; the generator state changes per call)
+  bool elem_dropout = false;
+  uint64_t rng_seed = 0, rng_offset = 0;
+  bool training = false;
+  bool no_grad = false;      // BN / ReLU folded into the conv epilogues, nothing saved for a backward (eval mode only)
+  bool need_derive = true;   // (re)pack the weights and the eval BN constants in this forward
+  int64_t version_after = -1;  // derived_version once the call has succeeded
+  bool elem_on(int j) const { return elem_masks[j] || elem_rng_on[j]; }
+};
+
 // What one walk of the backward stages was called with (mimo_backward*, mimo_input_gradient): handed down by reference from
 // backward_stage to the layer functions, nothing of it is kept on the plan.
 struct BwdCall {
@@ -235,6 +261,90 @@ struct DzRing {
   }
 };
 
+// Optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline, mimo_plan_profile*).
+struct Profiler {
+  struct Rec {
+    hipEvent_t a, b;
+    int kind, tier;
+  };
+  // tier records: kind = kTierBase + 2 * tier + (backward ? 1 : 0); tier = resolution level of a DoubleConv
+  // (0 = full resolution ... 4 = 1/16): the whole block (every launch between the two events), so that a tier's
+  // summed device time can be priced against its algorithmic HBM bytes (SURVEY 8d)
+  static constexpr int kTierBase = 100, kTiers = 5;
+  bool on = false;
+  int cur_tier = 0;  // resolution tier of the block being issued (kernel-class records inherit it)
+  std::vector<Rec> recs;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+  double ms[MIMO_PROF_KINDS] = {}, flops[MIMO_PROF_KINDS] = {}, bytes[MIMO_PROF_KINDS] = {};
+  int64_t launches[MIMO_PROF_KINDS] = {};
+  double kind_tier_ms[MIMO_PROF_KINDS][kTiers] = {};
+  double tier_ms[2 * kTiers] = {};
+  // (runs behind ~mimo_plan's body — buffers freed, graphs, cap_stream and ev_stage destroyed — and in front of ~DzRing;
+  // these events are recorded on the caller's streams only and destroying them needs none of those)
+  ~Profiler() {
+    for (auto& r : recs) {
+      (void)hipEventDestroy(r.a);
+      (void)hipEventDestroy(r.b);
+    }
+    for (auto& e : pool) {
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+  }
+  int begin(int kind, hipStream_t st) {
+    if (!on) return -1;
+    Rec r;
+    if (!pool.empty()) {
+      r.a = pool.back().first;
+      r.b = pool.back().second;
+      pool.pop_back();
+    } else {
+      (void)hipEventCreate(&r.a);
+      (void)hipEventCreate(&r.b);
+    }
+    r.kind = kind;
+    if (kind >= kTierBase) cur_tier = (kind - kTierBase) / 2;
+    r.tier = cur_tier;
+    (void)hipEventRecord(r.a, st);
+    recs.push_back(r);
+    return (int)recs.size() - 1;
+  }
+  void end(int idx, double fl, double by, hipStream_t st) {
+    if (idx < 0 || !on) return;
+    (void)hipEventRecord(recs[idx].b, st);
+    const int kind = recs[idx].kind;
+    if (kind >= kTierBase) return;
+    flops[kind] += fl;
+    bytes[kind] += by;
+    launches[kind] += 1;
+  }
+  int collect() {
+    for (auto& r : recs) {
+      MIMO_HIP_CHECK(hipEventSynchronize(r.b));
+      float t = 0.f;
+      MIMO_HIP_CHECK(hipEventElapsedTime(&t, r.a, r.b));
+      if (r.kind >= kTierBase)
+        tier_ms[r.kind - kTierBase] += t;
+      else {
+        ms[r.kind] += t;
+        kind_tier_ms[r.kind][r.tier] += t;
+      }
+      pool.emplace_back(r.a, r.b);
+    }
+    recs.clear();
+    return MIMO_OK;
+  }
+  void clear_totals() {
+    for (int k = 0; k < MIMO_PROF_KINDS; ++k) {
+      ms[k] = flops[k] = bytes[k] = 0.0;
+      launches[k] = 0;
+    }
+    for (double& v : tier_ms) v = 0.0;
+    for (auto& row : kind_tier_ms)
+      for (double& v : row) v = 0.0;
+  }
+};
+
 }  // namespace
 }  // namespace mimo
 
@@ -294,141 +404,76 @@ struct mimo_plan {
   // BatchNorm backward forms the gradient arriving at a pooled tensor / at the head's input itself (GS_POOL / GS_HEAD):
   // fp32 storage, MIMO_FUSE_BWD_SRC=0 switches it off (read per plan)
   bool fuse_bwd_src = false;
+  // BatchNorm + ReLU applied by the readers of a tensor instead of a pass of its own (ConvBN::fuse_in, Act::z):
+  // MIMO_FUSE_BN_IN=0 materialises every activated tensor (read per plan: A/B, tests)
+  bool fuse_bn_in = true;
   bool fuse_bwd_pool = false, fuse_bwd_head = false;  // (MIMO_FUSE_BWD_SRC=2: pooled tensors only, 3: head only — A/B)
   DzRing ring;  // dz buffers, their events and the side stream (ring.side)
   hipEvent_t ev_stage = nullptr;
   bool any_mixed_dz = false;
 
-  // optional per-kernel-class timing with HIP events on the launch stream (bench.py roofline)
-  struct ProfRec {
-    hipEvent_t a, b;
-    int kind, tier;
-  };
-  int cur_tier = 0;  // resolution tier of the block being issued (kernel-class records inherit it)
-  double prof_kind_tier_ms[MIMO_PROF_KINDS][5] = {};
-  bool prof_on = false;
-  std::vector<ProfRec> prof_recs;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
-  double prof_ms[MIMO_PROF_KINDS] = {}, prof_flops[MIMO_PROF_KINDS] = {}, prof_bytes[MIMO_PROF_KINDS] = {};
-  int64_t prof_launches[MIMO_PROF_KINDS] = {};
-
-  // tier records: kind = kProfTierBase + 2 * tier + (backward ? 1 : 0); tier = resolution level of a DoubleConv
-  // (0 = full resolution ... 4 = 1/16): the whole block (every launch between the two events), so that a tier's
-  // summed device time can be priced against its algorithmic HBM bytes (SURVEY 8d)
-  static constexpr int kProfTierBase = 100, kProfTiers = 5;
-  double prof_tier_ms[2 * kProfTiers] = {};
-  int tier_of(int h) const {
+  Profiler prof;
+  int tier_of(int h) const {  // resolution tier of a block at height h (Profiler::kTierBase records)
     int t = 0, hh = H;
-    while (t < kProfTiers - 1 && hh > h) {
+    while (t < Profiler::kTiers - 1 && hh > h) {
       hh /= 2;
       ++t;
     }
     return t;
   }
-  int prof_begin(int kind, hipStream_t st) {
-    if (!prof_on) return -1;
-    ProfRec r;
-    if (!prof_pool.empty()) {
-      r.a = prof_pool.back().first;
-      r.b = prof_pool.back().second;
-      prof_pool.pop_back();
-    } else {
-      (void)hipEventCreate(&r.a);
-      (void)hipEventCreate(&r.b);
-    }
-    r.kind = kind;
-    if (kind >= kProfTierBase) cur_tier = (kind - kProfTierBase) / 2;
-    r.tier = cur_tier;
-    (void)hipEventRecord(r.a, st);
-    prof_recs.push_back(r);
-    return (int)prof_recs.size() - 1;
-  }
-  void prof_end(int idx, double flops, double bytes, hipStream_t st) {
-    if (idx < 0 || !prof_on) return;
-    (void)hipEventRecord(prof_recs[idx].b, st);
-    const int kind = prof_recs[idx].kind;
-    if (kind >= kProfTierBase) return;
-    prof_flops[kind] += flops;
-    prof_bytes[kind] += bytes;
-    prof_launches[kind] += 1;
-  }
-  int prof_collect() {
-    for (auto& r : prof_recs) {
-      MIMO_HIP_CHECK(hipEventSynchronize(r.b));
-      float ms = 0.f;
-      MIMO_HIP_CHECK(hipEventElapsedTime(&ms, r.a, r.b));
-      if (r.kind >= kProfTierBase)
-        prof_tier_ms[r.kind - kProfTierBase] += ms;
-      else {
-        prof_ms[r.kind] += ms;
-        prof_kind_tier_ms[r.kind][r.tier] += ms;
-      }
-      prof_pool.emplace_back(r.a, r.b);
-    }
-    prof_recs.clear();
-    return MIMO_OK;
-  }
 
   // hipGraph replay of the eval-mode forward (launch-bound at small batch: ~100+ kernel launches).
   // The captured kernels read plan-owned staging copies of x / perm / masks and write a plan-owned
   // logits buffer, so the graph stays valid when the caller's tensors move.
+  // Whether a graphable call runs eagerly, is captured or replays what is live is decided by sched::GraphReplayPolicy
+  // (graph_replay.h, walked by tests/host/graph_replay_test.cpp), one per route; the handles, capture(), the staging copies and
+  // the "is this call graphable" predicates are here.  The eval-mode route captures a call shape at first sight.
   bool graph_enabled = true;
   hipStream_t cap_stream = nullptr;
   hipGraphExec_t graph_exec = nullptr;
-  uint64_t graph_key = 0;
+  sched::GraphReplayPolicy eval_replay = sched::GraphReplayPolicy::eval_forward();
   // hipGraph replay of the TRAINING step (round 6, MIMO_TRAIN_GRAPH=1, opt-in; mimo_unet.py:115-144 at its per-GPU shard is ~290
   // launches of which ~200 run < 20 us): the training forward is one graph, the backward one graph (mimo_backward) or one
   // per stage (mimo_backward_stage: the data-parallel caller starts a stage's all-reduce between two graphs).  Captured
   // kernels only see plan-owned memory: x / perm / Dropout2d multipliers are staged in front of the forward graph, label /
   // mask / perm by mimo_loss_forward, dloss in front of the first backward graph, the logits leave through g_out.  A call
   // shape (key) is captured the SECOND time it is seen — one-off shapes stay eager, and every kernel has run eagerly once
-  // before it is captured.  The side stream's weight gradients are a fork / join inside each backward graph.
+  // before it is captured (tg_fwd_replay / tg_bwd_replay) — out of one budget of captures per plan: a caller that keeps
+  // alternating call shapes on one plan would otherwise re-capture (milliseconds of host time) every other step.  The side
+  // stream's weight gradients are a fork / join inside each backward graph.
   bool train_graph = false;
   hipGraphExec_t tg_fwd = nullptr;
-  uint64_t tg_fwd_key = 0, tg_fwd_seen = 0;
   static constexpr int kBwdGraphs = 9;  // [0, 8): the single stages; [8]: the whole backward
   hipGraphExec_t tg_bwd[kBwdGraphs] = {};
-  uint64_t tg_bwd_key = 0, tg_bwd_seen = 0;
+  sched::CaptureBudget tg_budget{/*max=*/24};
+  sched::GraphReplayPolicy tg_fwd_replay = sched::GraphReplayPolicy::training_forward(&tg_budget);
+  sched::GraphReplayPolicy tg_bwd_replay = sched::GraphReplayPolicy::training_backward(&tg_budget);
   bool tg_bwd_live = false;    // the backward in progress replays graphs (decided at its stage 0)
-  // captures this plan may still make: a caller that keeps alternating call shapes on one plan would otherwise re-capture
-  // (milliseconds of host time) every other step
-  static constexpr int kMaxTrainCaptures = 24;
-  int tg_captures = 0;
-  bool fwd_graphed = false;    // the last forward was a training-graph replay: logits in g_out, masks staged
-  bool loss_staged = false;    // ... and mimo_loss_forward staged label / mask / perm
-  int64_t last_x_rows = 0;     // rows of the last forward's x (= rows of the label / mask tensors of that batch)
-  const int64_t* last_perm_arg = nullptr;  // the caller's perm tensor of the last graphed forward (staged in g_perm)
   float *g_label = nullptr, *g_lmask = nullptr, *g_dloss = nullptr;
   int64_t* g_lperm = nullptr;
-  void drop_train_graphs() {
-    if (tg_fwd) (void)hipGraphExecDestroy(tg_fwd);
-    tg_fwd = nullptr;
-    tg_fwd_key = tg_fwd_seen = 0;
-    for (auto& e : tg_bwd) {
-      if (e) (void)hipGraphExecDestroy(e);
-      e = nullptr;
-    }
-    tg_bwd_key = tg_bwd_seen = 0;
+  static void destroy_exec(hipGraphExec_t* e) {
+    if (*e) (void)hipGraphExecDestroy(*e);
+    *e = nullptr;
   }
-  void drop_graphs() {
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    graph_exec = nullptr;
-    drop_train_graphs();
+  void drop_graphs() {  // (spent captures are not refunded)
+    destroy_exec(&graph_exec);
+    eval_replay.reset();
+    destroy_exec(&tg_fwd);
+    tg_fwd_replay.reset();
+    for (auto& e : tg_bwd) destroy_exec(&e);
+    tg_bwd_replay.reset();
   }
   float *g_x = nullptr, *g_out = nullptr;
   int64_t* g_perm = nullptr;
   std::vector<float*> g_masks;
-  std::vector<const float*> g_mask_ptrs;
   // in-engine dropout (mimo_forward_args.rng_sites): Dropout2d multipliers are drawn into g_masks by one Philox
   // launch per forward; the element-wise sites (center / final nn.Dropout) regenerate theirs on the fly in the
   // forward and in the backward from the (seed, offset) of the last forward
   Dropout2dSite* d_sites = nullptr;
   int max_site_count = 0;
-  uint64_t rng_seed = 0, rng_offset = 0;
-  std::vector<char> elem_rng_on;  // [1 + S]
-  std::vector<const float*> eff_masks;
   float elem_rate(int j) const { return j == 0 ? cfg.center_dropout_rate : cfg.final_dropout_rate; }
-  ElemRng elem_rng(int j) const { return ElemRng{rng_seed, rng_offset, (int)dcs.size() + j, elem_rate(j)}; }
+  ElemRng elem_rng(int j, uint64_t seed, uint64_t offset) const { return ElemRng{seed, offset, (int)dcs.size() + j, elem_rate(j)}; }
+  ElemRng elem_rng(int j) const { return elem_rng(j, rng_seed, rng_offset); }  // of the last forward
 
   bool capturing = false;
 
@@ -441,32 +486,31 @@ struct mimo_plan {
   PackJob* pack_jobs = nullptr;
   int n_fwd_jobs = 0, n_all_jobs = 0, pack_max_total = 0;
 
-  // per-call state
+  // What the last forward left for the loss and the backward: assigned by record_forward.  (Besides: forward() ends
+  // fwd_graphed / loss_staged at once, mimo_loss_forward sets loss_done / loss_staged, a failed forward and mimo_plan_bind reset
+  // derived_version.)  dcs[i]->mask and Act::z_live belong to it and are set by prepare_forward.
   bool fwd_done = false, fwd_training = false, had_perm = false, loss_done = false;
-  int bwd_next_stage = 0;  // staged backward: the stage that may run next (0 = a fresh backward)
   bool fwd_no_grad = false;       // last forward folded BN/ReLU into the conv epilogue: nothing saved for a backward
+  float* out = nullptr;
+  std::vector<const float*> elem_masks;  // [1 + S] element-wise dropout multipliers of the last forward
+  std::vector<char> elem_rng_on;         // [1 + S] ... drawn in the engine, from:
+  uint64_t rng_seed = 0, rng_offset = 0;
+  bool fwd_graphed = false;    // the last forward was a training-graph replay: logits in g_out, masks staged
+  bool loss_staged = false;    // ... and mimo_loss_forward staged label / mask / perm
+  int64_t last_x_rows = 0;     // rows of the last forward's x (= rows of the label / mask tensors of that batch)
+  const int64_t* last_perm_arg = nullptr;  // the caller's perm tensor of the last graphed forward (staged in g_perm)
   int64_t derived_version = -1;   // param_version the packed weights / eval scale+shift were derived from (-1: none)
-  bool derived_dgrad = false;     // ... including the data-gradient weight copies
-  bool need_derive = true;        // per-call: (re)pack weights and eval BN constants in this forward
+
+  int bwd_next_stage = 0;  // staged backward: the stage that may run next (0 = a fresh backward)
   int64_t encoder_param_floats = 0;
   float* s_zero = nullptr;        // max cout_p zeros, never written: c1 / c2 of the apply pass after an eval-mode forward
   size_t cap_cout = 0;
   int64_t dgrad_version = -1;     // derived_version the data-gradient weight images were packed at by mimo_input_gradient (-1: none)
-  float* out = nullptr;
-  const float *label = nullptr, *lmask = nullptr;
-  std::vector<const float*> elem_masks;  // [1 + S] element-wise dropout multipliers of the last forward (or empty)
+  const float *label = nullptr, *lmask = nullptr;  // of the last mimo_loss_forward
   const int64_t* lperm = nullptr;
 
   ~mimo_plan() {
     for (void* p : allocs) (void)hipFree(p);
-    for (auto& r : prof_recs) {
-      (void)hipEventDestroy(r.a);
-      (void)hipEventDestroy(r.b);
-    }
-    for (auto& e : prof_pool) {
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
     drop_graphs();
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     if (ev_stage) (void)hipEventDestroy(ev_stage);
@@ -662,9 +706,8 @@ struct mimo_plan {
       // BatchNorm + ReLU of the first convolution applied by the second one's loaders: split16, when BOTH readers of the
       // activated tensor — the second convolution's forward and its weight gradient — run on kernels that can (the
       // wide / 256-pixel wave-specialised forward, the wave-specialised weight gradient).  MIMO_FUSE_BN_IN=0: materialise.
-      const bool on = !(getenv("MIMO_FUSE_BN_IN") && atoi(getenv("MIMO_FUSE_BN_IN")) == 0);  // read per plan (A/B, tests)
       ConvBN& c2 = dc->c2;
-      if (on && cfg.precision == MIMO_PREC_SPLIT16 && !cfg.inference_only && c2.fwd_split && c2.wg_split && dc->c1.dtz == ST_F32 &&
+      if (fuse_bn_in && cfg.precision == MIMO_PREC_SPLIT16 && !cfg.inference_only && c2.fwd_split && c2.wg_split && dc->c1.dtz == ST_F32 &&
           conv3x3_split_fuses_input(fwd_mode(), c2.fwd_wide, h, w) && wgrad_split_fuses_input(c2.cin_p, c2.cout_p, 0, 3)) {
         c2.fuse_in = true;
         c2.in_z = dc->c1.z;
@@ -737,6 +780,7 @@ struct mimo_plan {
       fuse_bwd_src = !mixed && cfg.inference_only != 1 && v != 0;
       fuse_bwd_pool = fuse_bwd_src && v != 3;
       fuse_bwd_head = fuse_bwd_src && v != 2;
+      fuse_bn_in = !(getenv("MIMO_FUSE_BN_IN") && atoi(getenv("MIMO_FUSE_BN_IN")) == 0);
     }
     if (cfg.precision < MIMO_PREC_FP32 || cfg.precision > MIMO_PREC_FP16_MIXED) {
       set_error("unknown precision %d", cfg.precision);
@@ -881,8 +925,6 @@ struct mimo_plan {
       h.off_b = add_tensor(p + ".bias", {Co}, 0);
       heads.push_back(h);
     }
-    // reorder dcs into the oracle's forward-spec order: enc_in[*], down1[*], core..., up4[*]
-    // (make_dc pushed them in exactly that order already).
 
     // ---- scratch ----
     const int fp = pad_channels(f);
@@ -1021,10 +1063,9 @@ struct mimo_plan {
       }
     }
     g_masks.resize(dcs.size());
-    g_mask_ptrs.assign(dcs.size(), nullptr);
     for (size_t i = 0; i < dcs.size(); ++i) MIMO_TRY(dalloc(&g_masks[i], (size_t)N * dcs[i]->c2.Cout));
     {
-      if (dcs.size() + 1 + S > 56) {
+      if ((int)dcs.size() + 1 + S > FwdCall::kMaxSites) {
         set_error("too many dropout sites (%d) for the in-engine generator", (int)dcs.size() + 1 + S);
         return MIMO_ERR_INVALID;
       }
@@ -1036,7 +1077,6 @@ struct mimo_plan {
       MIMO_TRY(dalloc(&d_sites, sites.size()));
       MIMO_HIP_CHECK(hipMemcpy(d_sites, sites.data(), sites.size() * sizeof(Dropout2dSite), hipMemcpyHostToDevice));
       elem_rng_on.assign(1 + S, 0);
-      eff_masks.assign(dcs.size(), nullptr);
     }
     MIMO_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
     return MIMO_OK;
@@ -1055,17 +1095,18 @@ struct mimo_plan {
   }
 
   // elide: the activated tensor of this layer is not written in this call (its readers apply BatchNorm + ReLU to z)
-  int convbn_forward(ConvBN& L, bool training, const float* mask, bool elide, hipStream_t st) {
+  int convbn_forward(ConvBN& L, const FwdCall& call, const float* mask, bool elide, hipStream_t st) {
+    const bool training = call.training;
     // inference: BN(eval) + ReLU (+ channel-dropout) in the conv epilogue — not for the fp32-kernel image convolution
     // of the 16-bit storage modes, whose output type differs from the activation type
-    const bool fused = fwd_no_grad && !(mixed && !L.fwd_split);
-    if (!training && need_derive)
+    const bool fused = call.no_grad && !(mixed && !L.fwd_split);
+    if (!training && call.need_derive)
       MIMO_TRY(bn_eval_prepare_launch(L.Cout, L.cout_p, params + L.off_gamma, params + L.off_beta, bnbuf + L.off_rm,
                                       bnbuf + L.off_rv, cfg.bn_eps, L.mean, L.invstd, L.scale, L.shift, st, d_status));
     // Training forward only.  (A forward without a graph folds BatchNorm + ReLU into every convolution's epilogue, and an
     // eval-mode forward WITH a graph — FGSM — keeps the separate pass, whose finiteness test feeds the numerics status word:
     // the activated tensors exist in both.  The weight gradient applies scale / shift to z either way: identical values.)
-    const bool fin = L.fuse_in && training && !fwd_no_grad;
+    const bool fin = L.fuse_in && training && !call.no_grad;
     ConvLaunch a;
     a.x = fin ? L.in_z : L.in;
     if (fin) {
@@ -1098,14 +1139,14 @@ struct mimo_plan {
     a.wmax = L.fwd_split ? L.wmax : nullptr;
     a.pair = (L.fwd_split && !L.fwd_wide) ? conv3x3_pair_tail(fwd_mode(), L.cin_p, L.H, L.W) : 0;
     a.wide = L.fwd_wide;
-    int pr = prof_begin(MIMO_PROF_CONV_FWD, st);
+    int pr = prof.begin(MIMO_PROF_CONV_FWD, st);
     if (L.fwd_split)  // (training forward: with the K split of conv3x3_ksplit where that pays — few tiles, a long K walk)
       MIMO_TRY(conv3x3_bf16x3_launch_k(a, fwd_mode(), &rows, st, (training && !fused) ? s_kpart : nullptr, cap_kpart));
     else if (L.thin)
       MIMO_TRY(conv3x3_thin_launch(a, L.Cin, &rows, st));
     else
       MIMO_TRY(conv3x3_launch(a, &rows, st));
-    prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
+    prof.end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
     if (training) {
       if (rows <= kColsumMaxRows) {
         MIMO_TRY(bn_fwd_stats_launch(s_partial, rows, L.cout_pad, L.Cout, L.cout_p, P, params + L.off_gamma,
@@ -1120,14 +1161,14 @@ struct mimo_plan {
       }
     }
     if (!fused && !elide) {
-      pr = prof_begin(MIMO_PROF_BN_RELU_FWD, st);
+      pr = prof.begin(MIMO_PROF_BN_RELU_FWD, st);
       if (L.pool_out)
         MIMO_TRY(bn_relu_pool_fwd_launch(L.z, L.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, L.N,
                                          L.H, L.W, L.pool_out, L.pool_ld, st, training ? nullptr : d_status));
       else
         MIMO_TRY(bn_relu_fwd_launch(L.z, L.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, P,
                                     L.H * L.W, st, training ? nullptr : d_status));
-      prof_end(pr, 0.0, (L.pool_out ? 9.0 : 8.0) * (double)P * L.cout_p, st);
+      prof.end(pr, 0.0, (L.pool_out ? 9.0 : 8.0) * (double)P * L.cout_p, st);
     }
     return MIMO_OK;
   }
@@ -1136,8 +1177,7 @@ struct mimo_plan {
   // Dropout2d on the block (its multipliers act on the activated tensor), MIMO_FUSE_BN_IN != 0.  The decoders' blocks
   // additionally need the element-wise final dropout off (checked where they are built).
   void elide_output(DoubleConv* dc) {
-    const bool on = !(getenv("MIMO_FUSE_BN_IN") && atoi(getenv("MIMO_FUSE_BN_IN")) == 0);
-    if (!on || cfg.precision != MIMO_PREC_SPLIT16 || cfg.inference_only || dc->drop_p > 0.f || dc->c2.pool_out ||
+    if (!fuse_bn_in || cfg.precision != MIMO_PREC_SPLIT16 || cfg.inference_only || dc->drop_p > 0.f || dc->c2.pool_out ||
         dc->c2.dtz != ST_F32)
       return;
     dc->c2.act_elided = true;
@@ -1148,36 +1188,35 @@ struct mimo_plan {
   }
 
   // the readers of this block's output go through z in this call (Act::z_live); dc->mask must be this call's
-  bool z_live_rule(const DoubleConv* dc, bool training, bool elem_mask_on_output) const {
-    return dc->c2.act_elided && dc->out.z && training && !fwd_no_grad && !dc->mask && !elem_mask_on_output;
+  bool z_live_rule(const DoubleConv* dc, const FwdCall& call, bool elem_mask_on_output) const {
+    return dc->c2.act_elided && dc->out.z && call.training && !call.no_grad && !dc->mask && !elem_mask_on_output;
   }
 
-  int dc_forward(DoubleConv* dc, bool training, hipStream_t st, bool elem_mask_on_output = false) {
+  int dc_forward(DoubleConv* dc, const FwdCall& call, hipStream_t st) {
     const int h = dc->c1.H, w = dc->c1.W;
-    dc->out.z_live = z_live_rule(dc, training, elem_mask_on_output);
-    const int blk = prof_begin(kProfTierBase + 2 * tier_of(h), st);
+    const int blk = prof.begin(Profiler::kTierBase + 2 * tier_of(h), st);
     if (dc->kind == IN_POOL) {
       Act* s = dc->src0;
-      if (!(dc->pool_fused && !fwd_no_grad))  // else: already written by the producers' BatchNorm + ReLU pass
+      if (!(dc->pool_fused && !call.no_grad))  // else: already written by the producers' BatchNorm + ReLU pass
         MIMO_TRY(maxpool_fwd_launch(s->a, this->st, s->ld, N, s->H, s->W, s->Cp, dc->in_buf, dc->in_ld, st));
     } else if (dc->kind == IN_UPCAT) {
       Act *sk = dc->src0, *lo = dc->src1;
-      const int pr = prof_begin(MIMO_PROF_UPCAT_FWD, st);
+      const int pr = prof.begin(MIMO_PROF_UPCAT_FWD, st);
       const bool lz = lo->z_live;  // the low-resolution tensor through its BatchNorm + ReLU
       MIMO_TRY(upcat_fwd_launch(nullptr, this->st, sk->ld, sk->Cp, lz ? lo->z : lo->a,
                                 lz ? lo->z_ld : lo->ld, lo->Cp, N, h, w, lo->H, lo->W, dc->in_buf, st, lz ? lo->z_scale : nullptr,
                                 lz ? lo->z_shift : nullptr));
       // writes the up-sampled channels at (h, w), reads the low-resolution tensor once
-      prof_end(pr, 0.0, 4.0 * lo->Cp * ((double)N * h * w + (double)N * lo->H * lo->W), st);
+      prof.end(pr, 0.0, 4.0 * lo->Cp * ((double)N * h * w + (double)N * lo->H * lo->W), st);
     }
 
-    MIMO_TRY(convbn_forward(dc->c1, training, nullptr, dc->c1.act_elided && training, st));
-    MIMO_TRY(convbn_forward(dc->c2, training, dc->mask, dc->out.z_live, st));
-    prof_end(blk, 0.0, 0.0, st);
+    MIMO_TRY(convbn_forward(dc->c1, call, nullptr, dc->c1.act_elided && call.training, st));
+    MIMO_TRY(convbn_forward(dc->c2, call, dc->mask, dc->out.z_live, st));
+    prof.end(blk, 0.0, 0.0, st);
     return MIMO_OK;
   }
 
-  int forward(const mimo_forward_args* args, hipStream_t st) {
+  int check_forward(const mimo_forward_args* args) const {
     if (!params || !bnbuf) {
       set_error("mimo_forward: parameters not bound (mimo_plan_bind)");
       return MIMO_ERR_STATE;
@@ -1194,120 +1233,145 @@ struct mimo_plan {
       set_error("mimo_forward: input-gradient-only plan (mimo_config.inference_only = 2) needs training = 0");
       return MIMO_ERR_STATE;
     }
-    // ---- in-engine dropout: draw the Dropout2d multipliers of the flagged sites, note the element-wise ones ----
-    mimo_forward_args a2 = *args;
-    const int64_t* const orig_perm = args->perm;
-    {
-      const int ndc = (int)dcs.size();
-      uint64_t active = 0;
-      bool any_mask = false;
-      for (int i = 0; i < ndc; ++i) {
-        eff_masks[i] = args->drop_masks ? args->drop_masks[i] : nullptr;
-        if (args->rng_sites && args->rng_sites[i] && dcs[i]->drop_p > 0.f) {
-          active |= 1ull << i;
-          eff_masks[i] = g_masks[i];
-        }
-        any_mask |= eff_masks[i] != nullptr;
+    return MIMO_OK;
+  }
+
+  // the call as the issuing functions see it; *active: the Dropout2d sites whose multipliers the engine draws (into g_masks)
+  FwdCall make_call(const mimo_forward_args& a, uint64_t* active) const {
+    FwdCall c;
+    const int ndc = (int)dcs.size();
+    c.x = a.x;
+    c.stride_n = a.stride_n;
+    c.stride_s = a.stride_s;
+    c.perm = a.perm;
+    c.out = a.out;
+    c.rows = a.x_rows > 0 ? a.x_rows : N;
+    const int64_t img = (int64_t)Ci * H * W;
+    c.x5 = a.stride_s == img && a.stride_n == (int64_t)S * img;
+    c.x4 = a.stride_s == 0 && a.stride_n == img;
+    *active = 0;
+    for (int i = 0; i < ndc; ++i) {
+      c.masks[i] = a.drop_masks ? a.drop_masks[i] : nullptr;
+      if (a.rng_sites && a.rng_sites[i] && dcs[i]->drop_p > 0.f) {
+        *active |= 1ull << i;
+        c.masks[i] = g_masks[i];
       }
-      rng_seed = args->rng_seed;
-      rng_offset = args->rng_offset;
-      bool any_elem = false;
-      for (int j = 0; j <= S; ++j) {
-        elem_rng_on[j] = args->rng_sites && args->rng_sites[ndc + j] && elem_rate(j) > 0.f &&
-                         !(args->elem_masks && args->elem_masks[j]);
-        any_elem |= elem_rng_on[j] != 0;
-      }
-      MIMO_TRY(dropout2d_masks_launch(d_sites, ndc, max_site_count, active, rng_seed, rng_offset, (hipStream_t)st));
-      a2.drop_masks = any_mask ? eff_masks.data() : nullptr;
-      a2.rng_sites = nullptr;
-      if (any_elem && !a2.elem_masks) {  // keeps the call off the hipGraph paths (the generator state changes per call)
-        static const float* const kNoElemMasks[64] = {};
-        a2.elem_masks = kNoElemMasks;
-      }
-      args = &a2;
+    }
+    c.rng_seed = a.rng_seed;
+    c.rng_offset = a.rng_offset;
+    c.elem_dropout = a.elem_masks != nullptr;
+    for (int j = 0; j <= S; ++j) {
+      c.elem_masks[j] = a.elem_masks ? a.elem_masks[j] : nullptr;
+      c.elem_rng_on[j] = a.rng_sites && a.rng_sites[ndc + j] && elem_rate(j) > 0.f && !c.elem_masks[j];
+      c.elem_dropout |= c.elem_rng_on[j];
     }
     // what has to be (re)derived from the parameters in this call, and whether anything is kept for a backward
-    const bool training_call = args->training != 0;
-    fwd_no_grad = !training_call && args->no_grad != 0;
-    need_derive = training_call || args->param_version == 0 || args->param_version != derived_version;
-    const int64_t version_after = training_call ? -1 : (args->param_version != 0 ? args->param_version : -1);
-    const int64_t img = (int64_t)Ci * H * W;
-    const bool x5 = args->stride_s == img && args->stride_n == (int64_t)S * img;
-    const bool x4 = args->stride_s == 0 && args->stride_n == img;
-    const int64_t rows = args->x_rows > 0 ? args->x_rows : N;
-    last_x_rows = rows;
-    last_perm_arg = nullptr;
-    fwd_graphed = loss_staged = false;
+    c.training = a.training != 0;
+    c.no_grad = !c.training && a.no_grad != 0;
+    c.need_derive = c.training || a.param_version == 0 || a.param_version != derived_version;
+    // (-1 after a training forward: the optimiser step invalidates the packed weights)
+    c.version_after = c.training ? -1 : (a.param_version != 0 ? a.param_version : -1);
+    return c;
+  }
+
+  // the same call on the plan's staging copies: what a captured forward reads and writes
+  FwdCall staged_call(const FwdCall& call) const {
+    FwdCall g = call;
+    g.x = g_x;
+    g.perm = call.perm ? g_perm : nullptr;
+    g.out = g_out;
+    for (size_t i = 0; i < dcs.size(); ++i) g.masks[i] = call.masks[i] ? g_masks[i] : nullptr;
+    return g;
+  }
+
+  // the caller's x / perm / Dropout2d multipliers into the staging copies
+  int stage_inputs(const FwdCall& call, hipStream_t st) {
+    MIMO_HIP_CHECK(hipMemcpyAsync(g_x, call.x, (size_t)call.rows * (call.x5 ? S : 1) * Ci * H * W * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (call.perm)
+      MIMO_HIP_CHECK(hipMemcpyAsync(g_perm, call.perm, (size_t)S * N * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    for (size_t i = 0; i < dcs.size(); ++i)
+      if (call.masks[i] && call.masks[i] != g_masks[i])  // (an in-engine site was drawn straight into the staging buffer)
+        MIMO_HIP_CHECK(hipMemcpyAsync(g_masks[i], call.masks[i], (size_t)N * dcs[i]->c2.Cout * sizeof(float),
+                                      hipMemcpyDeviceToDevice, st));
+    return MIMO_OK;
+  }
+
+  // In front of issuing or replaying a forward: what of the call's state lives on the blocks — this call's Dropout2d
+  // multipliers and which activated tensors are read through z (every input of that rule is known before the first launch).
+  void prepare_forward(const FwdCall& call) {
+    for (size_t i = 0; i < dcs.size(); ++i) {
+      dcs[i]->mask = call.masks[i];
+      dcs[i]->out.z_live = z_live_rule(dcs[i].get(), call, false);
+    }
+    // (an element-wise final dropout on a block whose output is elided by construction: this call materialises it)
+    for (int s = 0; s < S; ++s) up4[s]->out.z_live = z_live_rule(up4[s], call, call.elem_on(1 + s));
+  }
+
+  // Behind a forward that was issued or replayed: what the loss and the backward read later.  `call` carries the pointers they
+  // are to see — the caller's after an eager forward and after an eval-mode replay, the staged ones after a training replay
+  // (graphed: a backward graph must not see the caller's pointers).
+  void record_forward(const FwdCall& call, bool graphed, const int64_t* perm_arg) {
+    out = call.out;
+    fwd_done = true;
+    fwd_training = call.training;
+    fwd_no_grad = call.no_grad;
+    had_perm = call.perm != nullptr;
+    loss_done = false;
+    elem_masks.assign(call.elem_masks, call.elem_masks + 1 + S);
+    elem_rng_on.assign(call.elem_rng_on, call.elem_rng_on + 1 + S);
+    rng_seed = call.rng_seed;
+    rng_offset = call.rng_offset;
+    fwd_graphed = graphed;
+    last_x_rows = call.rows;
+    last_perm_arg = graphed ? perm_arg : nullptr;
+    derived_version = call.version_after;
+  }
+
+  int forward(const mimo_forward_args* args, hipStream_t st) {
+    MIMO_TRY(check_forward(args));
+    // ---- in-engine dropout: draw the Dropout2d multipliers of the flagged sites, note the element-wise ones ----
+    uint64_t active = 0;
+    const FwdCall call = make_call(*args, &active);
+    MIMO_TRY(dropout2d_masks_launch(d_sites, (int)dcs.size(), max_site_count, active, call.rng_seed, call.rng_offset, st));
+    fwd_graphed = loss_staged = false;  // whatever the previous forward staged for a backward graph ends here, also if this call fails
     // eval mode replays a graph while the packed weights stand (need_derive: the repack is not part of that graph); a
     // training forward always repacks — inside its graph
-    const bool graphable = graph_enabled && !prof_on && (x5 || x4) && !args->elem_masks && rows <= N &&
-                           (training_call ? (train_graph && tg_captures < kMaxTrainCaptures) : !need_derive);
-    uint64_t key = 1 | (x5 ? 2 : 0) | (args->perm ? 4 : 0) | (fwd_no_grad ? 8 : 0) | (training_call ? 16 : 0);
+    const bool graphable = graph_enabled && !prof.on && (call.x5 || call.x4) && !call.elem_dropout && call.rows <= N &&
+                           (call.training ? train_graph : !call.need_derive);
+    uint64_t key = 1 | (call.x5 ? 2 : 0) | (call.perm ? 4 : 0) | (call.no_grad ? 8 : 0) | (call.training ? 16 : 0);
     for (size_t i = 0; i < dcs.size(); ++i)
-      if (args->drop_masks && args->drop_masks[i]) key |= 1ull << (8 + i);
-    bool eager = !graphable;
-    if (graphable && training_call && !(tg_fwd && key == tg_fwd_key) && key != tg_fwd_seen) {
-      tg_fwd_seen = key;  // first sighting of this call shape: eager (captured when it comes again)
-      eager = true;
-    }
-    if (eager) {
-      const int rc = forward_impl(args, st);
-      derived_version = rc == MIMO_OK ? version_after : -1;
-      return rc;
+      if (call.masks[i]) key |= 1ull << (8 + i);
+    sched::GraphReplayPolicy& replay = call.training ? tg_fwd_replay : eval_replay;
+    const auto route = graphable ? replay.decide(key) : sched::GraphReplayPolicy::Eager;
+    if (route == sched::GraphReplayPolicy::Eager) {
+      prepare_forward(call);
+      if (const int rc = forward_impl(call, st)) {
+        derived_version = -1;
+        return rc;
+      }
+      record_forward(call, false, nullptr);
+      return MIMO_OK;
     }
     // ---- stage the caller's tensors, (re)capture if the call shape changed, replay ----
-    MIMO_HIP_CHECK(hipMemcpyAsync(g_x, args->x, (size_t)rows * (x5 ? S : 1) * img * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (args->perm)
-      MIMO_HIP_CHECK(hipMemcpyAsync(g_perm, args->perm, (size_t)S * N * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    for (size_t i = 0; i < dcs.size(); ++i) {
-      const bool on = args->drop_masks && args->drop_masks[i];
-      g_mask_ptrs[i] = on ? g_masks[i] : nullptr;
-      if (on && args->drop_masks[i] != g_masks[i])  // (an in-engine site was drawn straight into the staging buffer)
-        MIMO_HIP_CHECK(hipMemcpyAsync(g_masks[i], args->drop_masks[i], (size_t)N * dcs[i]->c2.Cout * sizeof(float),
-                                      hipMemcpyDeviceToDevice, st));
+    const FwdCall staged = staged_call(call);
+    hipGraphExec_t* exec = call.training ? &tg_fwd : &graph_exec;
+    int rc = stage_inputs(call, st);
+    if (rc == MIMO_OK && route == sched::GraphReplayPolicy::Capture) {
+      destroy_exec(exec);
+      prepare_forward(staged);  // (the issuing functions read the blocks' masks and z_live)
+      rc = capture([&](hipStream_t cs) { return forward_impl(staged, cs); }, exec);
     }
-    hipGraphExec_t* exec = training_call ? &tg_fwd : &graph_exec;
-    uint64_t* ekey = training_call ? &tg_fwd_key : &graph_key;
-    if (!*exec || key != *ekey) {
-      if (*exec) {
-        (void)hipGraphExecDestroy(*exec);
-        *exec = nullptr;
-      }
-      mimo_forward_args ga = *args;
-      ga.x = g_x;
-      ga.perm = args->perm ? g_perm : nullptr;
-      ga.drop_masks = args->drop_masks ? g_mask_ptrs.data() : nullptr;
-      ga.out = g_out;
-      MIMO_TRY(capture([&](hipStream_t cs) { return forward_impl(&ga, cs); }, exec));
-      *ekey = key;
-      if (training_call) ++tg_captures;
+    if (rc != MIMO_OK) {
+      if (route == sched::GraphReplayPolicy::Capture) replay.capture_failed();
+      return rc;
     }
-    elem_masks.clear();
+    // the loss and the backward after a training replay stay on the staged tensors; an eval-mode forward writes every
+    // activated tensor, and its backward (FGSM) reads the caller's masks and logits
+    const FwdCall& left = call.training ? staged : call;
+    prepare_forward(left);
     MIMO_HIP_CHECK(hipGraphLaunch(*exec, st));
-    MIMO_HIP_CHECK(hipMemcpyAsync(args->out, g_out, (size_t)N * S * Co * H * W * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (training_call) {
-      // the per-call state forward_impl / dc_forward leave behind for the loss and the backward, on the STAGED tensors (a
-      // backward graph must not see the caller's pointers): masks, which activated tensors were elided, the logits
-      elem_masks.assign(1 + S, nullptr);
-      for (size_t i = 0; i < dcs.size(); ++i) {
-        dcs[i]->mask = g_mask_ptrs[i];
-        dcs[i]->out.z_live = z_live_rule(dcs[i].get(), true, false);
-      }
-      out = g_out;
-      fwd_graphed = true;
-      last_perm_arg = orig_perm;
-    } else {
-      for (size_t i = 0; i < dcs.size(); ++i) {
-        dcs[i]->mask = args->drop_masks ? args->drop_masks[i] : nullptr;
-        dcs[i]->out.z_live = false;  // (an eval-mode forward writes every activated tensor)
-      }
-      out = args->out;
-    }
-    fwd_done = true;
-    fwd_training = training_call;
-    had_perm = args->perm != nullptr;
-    loss_done = false;
-    derived_version = version_after;  // -1 after a training forward: the optimiser step invalidates the packed weights
+    MIMO_HIP_CHECK(hipMemcpyAsync(call.out, g_out, (size_t)N * S * Co * H * W * sizeof(float), hipMemcpyDeviceToDevice, st));
+    record_forward(left, call.training, call.perm);
     return MIMO_OK;
   }
 
@@ -1331,64 +1395,46 @@ struct mimo_plan {
     return MIMO_OK;
   }
 
-  int forward_impl(const mimo_forward_args* args, hipStream_t st) {
-    if (!params || !bnbuf) {
-      set_error("mimo_forward: parameters not bound (mimo_plan_bind)");
-      return MIMO_ERR_STATE;
-    }
-    if (!args || !args->x || !args->out) {
-      set_error("mimo_forward: null argument");
-      return MIMO_ERR_INVALID;
-    }
-    const bool training = args->training != 0;
-    for (size_t i = 0; i < dcs.size(); ++i) dcs[i]->mask = args->drop_masks ? args->drop_masks[i] : nullptr;
-    elem_masks.assign(1 + S, nullptr);
-    if (args->elem_masks)
-      for (int i = 0; i <= S; ++i) elem_masks[i] = args->elem_masks[i];
-    if (need_derive) MIMO_TRY(pack_all(training, st));
+  // issues one forward on `st` (eagerly or under capture); prepare_forward(call) has run
+  int forward_impl(const FwdCall& call, hipStream_t st) {
+    if (call.need_derive) MIMO_TRY(pack_all(call.training, st));
     for (int s = 0; s < S; ++s)
-      MIMO_TRY(pack_input_launch(args->x, args->stride_n, args->stride_s, args->perm, s, N, Ci, H, W, enc_in[s]->in_buf,
+      MIMO_TRY(pack_input_launch(call.x, call.stride_n, call.stride_s, call.perm, s, N, Ci, H, W, enc_in[s]->in_buf,
                                  Ci_p, st));
     for (int s = 0; s < S; ++s) {  // chain by chain
-      MIMO_TRY(dc_forward(enc_in[s], training, st));
-      MIMO_TRY(dc_forward(down1[s], training, st));
+      MIMO_TRY(dc_forward(enc_in[s], call, st));
+      MIMO_TRY(dc_forward(down1[s], call, st));
     }
-    MIMO_TRY(dc_forward(down2, training, st));
-    MIMO_TRY(dc_forward(down3, training, st));
-    MIMO_TRY(dc_forward(down4, training, st));
+    MIMO_TRY(dc_forward(down2, call, st));
+    MIMO_TRY(dc_forward(down3, call, st));
+    MIMO_TRY(dc_forward(down4, call, st));
     // center_dropout: in place on down4's output, whose only reader is up1's upsample (the BN/ReLU
     // backward recomputes its mask from z, not from a)
-    if (elem_masks[0] || elem_rng_on[0]) {
-      const ElemRng g = elem_rng(0);
-      MIMO_TRY(elem_mask_mul_launch(down4->out.a, this->st, down4->out.ld, elem_masks[0], N, down4->out.C, down4->out.Cp,
-                                    down4->out.H * down4->out.W, st, elem_masks[0] ? nullptr : &g));
+    if (call.elem_on(0)) {
+      const ElemRng g = elem_rng(0, call.rng_seed, call.rng_offset);
+      MIMO_TRY(elem_mask_mul_launch(down4->out.a, this->st, down4->out.ld, call.elem_masks[0], N, down4->out.C, down4->out.Cp,
+                                    down4->out.H * down4->out.W, st, call.elem_masks[0] ? nullptr : &g));
     }
-    MIMO_TRY(dc_forward(up1, training, st));
-    MIMO_TRY(dc_forward(up2, training, st));
-    MIMO_TRY(dc_forward(up3, training, st));
+    MIMO_TRY(dc_forward(up1, call, st));
+    MIMO_TRY(dc_forward(up2, call, st));
+    MIMO_TRY(dc_forward(up3, call, st));
     for (int s = 0; s < S; ++s) {
-      // (an element-wise final dropout on a block whose output is elided by construction: this call materialises it)
-      MIMO_TRY(dc_forward(up4[s], training, st, elem_masks[1 + s] || elem_rng_on[1 + s]));
+      MIMO_TRY(dc_forward(up4[s], call, st));
       const Act& o = up4[s]->out;
       // final_dropouts[s]: in place, the head (forward and weight gradient) is the only reader
-      if (elem_masks[1 + s] || elem_rng_on[1 + s]) {
-        const ElemRng g = elem_rng(1 + s);
-        MIMO_TRY(elem_mask_mul_launch(o.a, this->st, o.ld, elem_masks[1 + s], N, o.C, o.Cp, H * W, st,
-                                      elem_masks[1 + s] ? nullptr : &g));
+      if (call.elem_on(1 + s)) {
+        const ElemRng g = elem_rng(1 + s, call.rng_seed, call.rng_offset);
+        MIMO_TRY(elem_mask_mul_launch(o.a, this->st, o.ld, call.elem_masks[1 + s], N, o.C, o.Cp, H * W, st,
+                                      call.elem_masks[1 + s] ? nullptr : &g));
       }
-      const int blk = prof_begin(kProfTierBase, st);
-      const int pr = prof_begin(MIMO_PROF_HEAD_FWD, st);
+      const int blk = prof.begin(Profiler::kTierBase, st);
+      const int pr = prof.begin(MIMO_PROF_HEAD_FWD, st);
       const bool oz = o.z_live;
       MIMO_TRY(head_fwd_launch(oz ? o.z : o.a, this->st, oz ? o.z_ld : o.ld, params + heads[s].off_w, params + heads[s].off_b, f, Co,
-                               N, S, s, H * W, args->out, st, d_status, oz ? o.z_scale : nullptr, oz ? o.z_shift : nullptr));
-      prof_end(pr, 0.0, 4.0 * (double)N * H * W * (pad_channels(f) + Co), st);
-      prof_end(blk, 0.0, 0.0, st);
+                               N, S, s, H * W, call.out, st, d_status, oz ? o.z_scale : nullptr, oz ? o.z_shift : nullptr));
+      prof.end(pr, 0.0, 4.0 * (double)N * H * W * (pad_channels(f) + Co), st);
+      prof.end(blk, 0.0, 0.0, st);
     }
-    out = args->out;
-    fwd_done = true;
-    fwd_training = training;
-    had_perm = args->perm != nullptr;
-    loss_done = false;
     return MIMO_OK;
   }
 
@@ -1457,12 +1503,12 @@ struct mimo_plan {
     a.wpk = L.wd16;
     a.pair = (L.dg_split && !L.dg_wide) ? conv3x3_pair_tail(dgrad_mode(), L.cout_p, L.H + 2, L.W + 2) : 0;
     a.wide = L.dg_wide;
-    int pr = prof_begin(MIMO_PROF_CONV_DGRAD, st);
+    int pr = prof.begin(MIMO_PROF_CONV_DGRAD, st);
     if (L.dg_split)
       MIMO_TRY(conv3x3_bf16x3_launch_k(a, dgrad_mode(), nullptr, st, s_kpart, cap_kpart));
     else
       MIMO_TRY(conv3x3_launch(a, nullptr, st));
-    prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
+    prof.end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
     return MIMO_OK;
   }
 
@@ -1477,10 +1523,10 @@ struct mimo_plan {
   int bn_apply(ConvBN& L, const GradSrc& src, const float* mask, const float* c1, const float* c2, float* dz, bool split_out,
                float* partial, int* rows, hipStream_t st, float* absmax = nullptr, int* absmax_n = nullptr, hipEvent_t done = nullptr) {
     const int64_t P = (int64_t)L.N * L.H * L.W;
-    const int pr = prof_begin(MIMO_PROF_BN_BWD_APPLY, st);
+    const int pr = prof.begin(MIMO_PROF_BN_BWD_APPLY, st);
     MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, c1, c2,
                                  L.cout_p, L.N, L.H, L.W, dz, split_out ? 1 : 0, partial, rows, st, absmax, absmax_n, done));
-    prof_end(pr, 0.0, (8.0 + src_bytes(src)) * (double)P * L.cout_p, st);
+    prof.end(pr, 0.0, (8.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     return MIMO_OK;
   }
 
@@ -1502,10 +1548,10 @@ struct mimo_plan {
   int bn_backward(ConvBN& L, const GradSrc& src, const float* mask, DzRing::Slot& s, bool training, bool thin_wg, hipStream_t st) {
     int rows = 0;
     const int64_t P = (int64_t)L.N * L.H * L.W;
-    const int pr = prof_begin(MIMO_PROF_BN_BWD_REDUCE, st);
+    const int pr = prof.begin(MIMO_PROF_BN_BWD_REDUCE, st);
     MIMO_TRY(bnrelu_bwd_reduce_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd,
                                       mask, L.Cout, L.cout_p, L.N, L.H, L.W, s_partial, &rows, st));
-    prof_end(pr, 0.0, (4.0 + src_bytes(src)) * (double)P * L.cout_p, st);
+    prof.end(pr, 0.0, (4.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     if (src.kind == GS_HEAD) head_rows = rows;
     MIMO_TRY(bn_bwd_stats_launch(s_partial, rows, L.Cout, L.cout_p, P, training ? 1 : 0, L.c1, L.c2, grads + L.off_gamma,
                                  grads + L.off_beta, training ? grads + L.off_b : nullptr, d_status, st));
@@ -1559,14 +1605,14 @@ struct mimo_plan {
     // 16-bit storage: activations and dz plain NHWC 16-bit; the image convolution's input stays fp32
     wg.store = !mixed ? 0 : (L.fwd_split ? (f16 ? 2 : 1) : (f16 ? 4 : 3));
     if (wg_delay_us > 0) MIMO_TRY(debug_delay_launch(wg_delay_us, ws));  // test hook: a late consumer
-    const int pr = prof_begin(MIMO_PROF_CONV_WGRAD, ws);
+    const int pr = prof.begin(MIMO_PROF_CONV_WGRAD, ws);
     if (thin_wg)  // (dz as fp32, straight from the BatchNorm backward)
       MIMO_TRY(wgrad_thin_launch(L.in, L.ld_in, o.dz_wg, L.cout_p, L.N, L.H, L.W, L.Cin, L.Cout, L.cout_p, s_wslab, grads + L.off_w, ws));
     else if (L.wg_split)
       MIMO_TRY(wgrad_split_launch(wg, ws));
     else
       MIMO_TRY(wgrad_launch(wg, ws));
-    prof_end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), ws);
+    prof.end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), ws);
     if (!thin_wg)  // (the plain-FMA kernel's launch reduces its own partials)
       MIMO_TRY(wgrad_reduce_launch(s_wslab, L.wg_splits, L.wg_cin_pad, L.wg_cout_pad, L.cin_map, L.cin_p, L.Cin, L.Cout,
                                    grads + L.off_w, ws, wg.dz_absmax, wg.dz_absmax_n, release));
@@ -1580,7 +1626,7 @@ struct mimo_plan {
     // else reads this dz)
     const bool thin_wg = L.thin && !mixed && !need_dgrad && wgrad_thin_ok(L.Cin, L.cout_p, L.N, L.H, L.W);
     // (with the profiler armed everything runs on the caller's stream: per-kernel times, not overlapped times)
-    DzRing::Slot s = ring.acquire(wg_async && !prof_on);
+    DzRing::Slot s = ring.acquire(wg_async && !prof.on);
     MIMO_TRY(bn_backward(L, src, mask, s, fwd_training, thin_wg, st));
     if (need_dgrad) MIMO_TRY(dgrad_conv(L, ring.dz[s.b], dxpad_out, st));
     hipStream_t ws = st;
@@ -1591,9 +1637,9 @@ struct mimo_plan {
   }
 
   int dc_backward(DoubleConv* dc, bool need_input_grad, const BwdCall& call, hipStream_t st, const GradSrc* head_src = nullptr) {
-    const int blk = prof_begin(kProfTierBase + 2 * tier_of(dc->c1.H) + 1, st);
+    const int blk = prof.begin(Profiler::kTierBase + 2 * tier_of(dc->c1.H) + 1, st);
     const int rc = dc_backward_impl(dc, need_input_grad, call, st, head_src);
-    prof_end(blk, 0.0, 0.0, st);
+    prof.end(blk, 0.0, 0.0, st);
     return rc;
   }
 
@@ -1625,22 +1671,22 @@ struct mimo_plan {
       s->poolgrad_ld = ldp;
     } else if (dc->kind == IN_POOL) {
       Act* s = dc->src0;
-      const int pr = prof_begin(MIMO_PROF_POOL_BWD, st);
+      const int pr = prof.begin(MIMO_PROF_POOL_BWD, st);
       const bool acc = acc_flag(s) != 0;
       MIMO_TRY(pool_bwd_launch(dxB, this->st, ldp, 0, s->a, s->ld, s->da, s->ldda, N, s->H, s->W, s->Cp, acc ? 1 : 0, st, s->skipgrad,
                                s->skipgrad_ld));
       // reads the pooled gradient (1/4), the activation, [the skip gradient], [the old gradient]; writes the gradient
-      prof_end(pr, 0.0, 4.0 * s->Cp * (double)N * s->H * s->W * (2.25 + (s->skipgrad ? 1.0 : 0.0) + (acc ? 1.0 : 0.0)), st);
+      prof.end(pr, 0.0, 4.0 * s->Cp * (double)N * s->H * s->W * (2.25 + (s->skipgrad ? 1.0 : 0.0) + (acc ? 1.0 : 0.0)), st);
       s->skipgrad = nullptr;
     } else if (dc->kind == IN_UPCAT) {
       Act *sk = dc->src0, *lo = dc->src1;
       // the skip slice stays where the data gradient wrote it (dxpad_own); the pool backward of sk folds it in
       sk->skipgrad = dxB;
       sk->skipgrad_ld = ldp;
-      const int pr = prof_begin(MIMO_PROF_UP_BWD, st);
+      const int pr = prof.begin(MIMO_PROF_UP_BWD, st);
       MIMO_TRY(up_bwd_launch(dxB, this->st, ldp, sk->Cp, lo->da, lo->ldda, N, h, w, lo->H, lo->W, lo->Cp, acc_flag(lo), st));
       // reads the up-sampled slice of the padded-domain gradient once, writes the low-resolution gradient
-      prof_end(pr, 0.0, 4.0 * lo->Cp * ((double)N * (h + 2) * (w + 2) + (double)N * lo->H * lo->W), st);
+      prof.end(pr, 0.0, 4.0 * lo->Cp * ((double)N * (h + 2) * (w + 2) + (double)N * lo->H * lo->W), st);
     }
     return MIMO_OK;
   }
@@ -1671,6 +1717,15 @@ struct mimo_plan {
   int backward(const float* dout, const float* dloss, float* dx, int stage_first, int stage_last, hipStream_t st,
                hipStream_t* ready = nullptr) {
     if (ready) *ready = st;
+    MIMO_TRY(check_backward(dout, dloss, dx, stage_first, stage_last));
+    const bool whole = stage_first == 0 && stage_last == kBwdStages - 1;
+    const bool graph_shaped = !dout && !dx && (whole || stage_first == stage_last);  // what a backward graph can stand for
+    if (stage_first == 0) MIMO_TRY(backward_graphs(dloss, whole, graph_shaped && dloss && !ready, st));
+    if (tg_bwd_live) return backward_replay(stage_first, stage_last, whole, graph_shaped, st);
+    return backward_eager(BwdCall{dout, dloss, dx}, stage_first, stage_last, ready, st);
+  }
+
+  int check_backward(const float* dout, const float* dloss, const float* dx, int stage_first, int stage_last) const {
     if (!fwd_done) {
       set_error("mimo_backward: call mimo_forward first");
       return MIMO_ERR_STATE;
@@ -1707,67 +1762,71 @@ struct mimo_plan {
       set_error("mimo_backward: stage %d requested, stage %d is next", stage_first, bwd_next_stage);
       return MIMO_ERR_STATE;
     }
-    const bool whole = stage_first == 0 && stage_last == kBwdStages - 1;
-    if (stage_first == 0) {
-      // ---- training-step graphs: decide for this backward, stage dloss, capture on the second sighting of the shape ----
-      tg_bwd_live = false;
-      const bool single = stage_first == stage_last;
-      // (the asynchronous stages — `ready` — are eager launches: a per-stage graph has to close its fork to the side stream
-      // before it ends, which is the join that route exists to avoid)
-      if (train_graph && !ready && fwd_graphed && loss_staged && fwd_training && !prof_on && !dout && !dx && dloss && (whole || single) &&
-          tg_captures < kMaxTrainCaptures) {
-        const uint64_t key = (tg_fwd_key << 3) | (lmask ? 4 : 0) | (lperm ? 2 : 0) | (whole ? 1 : 0);
-        bool have_graphs = tg_bwd_key == key && (whole ? tg_bwd[kBwdStages] != nullptr : tg_bwd[0] != nullptr);
-        if (!have_graphs && tg_bwd_seen == key) {
-          for (auto& e : tg_bwd) {
-            if (e) (void)hipGraphExecDestroy(e);
-            e = nullptr;
-          }
-          tg_bwd_key = 0;
-          // (a capture executes nothing: the stages can be captured one after the other, each on the host state — gradient
-          // routing of the activation tensors — the stage before it left)
-          const BwdCall staged{nullptr, g_dloss};
-          if (whole) {
-            MIMO_TRY(capture([&](hipStream_t cs) {
-              ring.policy.rewind();
-              for (int stage = 0; stage < kBwdStages; ++stage) MIMO_TRY(backward_stage(stage, staged, cs));
-              return ring.join(cs);
-            }, &tg_bwd[kBwdStages]));
-          } else {
-            for (int stage = 0; stage < kBwdStages; ++stage)
-              MIMO_TRY(capture([&](hipStream_t cs) {
-                ring.policy.rewind();
-                MIMO_TRY(backward_stage(stage, staged, cs));
-                return ring.join(cs);
-              }, &tg_bwd[stage]));
-          }
-          tg_bwd_key = key;
-          ++tg_captures;
-          have_graphs = true;
-        }
-        tg_bwd_seen = key;
-        tg_bwd_live = have_graphs;
-        if (have_graphs) MIMO_HIP_CHECK(hipMemcpyAsync(g_dloss, dloss, (size_t)S * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return MIMO_OK;
+  }
+
+  // Stage 0 of a backward: decides whether this backward replays training-step graphs (tg_bwd_live), captures them on the
+  // second sighting of the call shape — the whole backward as one graph or each of the eight stages as its own — and stages dloss.
+  // shape_ok: the call is one a graph can stand for (dloss only, whole or a single stage, not the asynchronous stages —
+  // `ready` — which are eager launches: a per-stage graph has to close its fork to the side stream before it ends, which is
+  // the join that route exists to avoid).
+  int backward_graphs(const float* dloss, bool whole, bool shape_ok, hipStream_t st) {
+    tg_bwd_live = false;
+    if (!(train_graph && shape_ok && fwd_graphed && loss_staged && fwd_training && !prof.on)) return MIMO_OK;
+    const uint64_t key = (tg_fwd_replay.live << 3) | (lmask ? 4 : 0) | (lperm ? 2 : 0) | (whole ? 1 : 0);
+    const auto route = tg_bwd_replay.decide(key);
+    if (route == sched::GraphReplayPolicy::Eager) return MIMO_OK;
+    if (route == sched::GraphReplayPolicy::Capture) {
+      for (auto& e : tg_bwd) destroy_exec(&e);
+      // (a capture executes nothing: the stages can be captured one after the other, each on the host state — gradient
+      // routing of the activation tensors — the stage before it left)
+      const BwdCall staged{nullptr, g_dloss};
+      int rc = MIMO_OK;
+      if (whole) {
+        rc = capture([&](hipStream_t cs) {
+          ring.policy.rewind();
+          for (int stage = 0; stage < kBwdStages; ++stage) MIMO_TRY(backward_stage(stage, staged, cs));
+          return ring.join(cs);
+        }, &tg_bwd[kBwdStages]);
+      } else {
+        for (int stage = 0; stage < kBwdStages && rc == MIMO_OK; ++stage)
+          rc = capture([&](hipStream_t cs) {
+            ring.policy.rewind();
+            MIMO_TRY(backward_stage(stage, staged, cs));
+            return ring.join(cs);
+          }, &tg_bwd[stage]);
+      }
+      if (rc != MIMO_OK) {
+        tg_bwd_replay.capture_failed();
+        return rc;
       }
     }
-    if (tg_bwd_live && !dout && !dx && (whole || stage_first == stage_last)) {
-      hipGraphExec_t e = whole ? tg_bwd[kBwdStages] : tg_bwd[stage_first];
-      if (!e) {
-        set_error("mimo_backward: no graph for stage range %d..%d of the backward in progress", stage_first, stage_last);
-        return MIMO_ERR_STATE;
-      }
-      MIMO_HIP_CHECK(hipGraphLaunch(e, st));
-      bwd_next_stage = stage_last + 1 < kBwdStages ? stage_last + 1 : 0;
-      return MIMO_OK;  // (every backward graph ends with the join of the side stream)
-    }
-    if (tg_bwd_live) {
+    tg_bwd_live = true;
+    MIMO_HIP_CHECK(hipMemcpyAsync(g_dloss, dloss, (size_t)S * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return MIMO_OK;
+  }
+
+  // the backward in progress replays graphs: the one of this stage range (every backward graph ends with the join of the side stream)
+  int backward_replay(int stage_first, int stage_last, bool whole, bool graph_shaped, hipStream_t st) {
+    if (!graph_shaped) {
       set_error("mimo_backward: stage %d..%d differs from what stage 0 of this backward was called with", stage_first, stage_last);
       return MIMO_ERR_STATE;
     }
-    const BwdCall call{dout, dloss, dx};
+    hipGraphExec_t e = whole ? tg_bwd[kBwdStages] : tg_bwd[stage_first];
+    if (!e) {
+      set_error("mimo_backward: no graph for stage range %d..%d of the backward in progress", stage_first, stage_last);
+      return MIMO_ERR_STATE;
+    }
+    MIMO_HIP_CHECK(hipGraphLaunch(e, st));
+    bwd_next_stage = stage_last + 1 < kBwdStages ? stage_last + 1 : 0;
+    return MIMO_OK;
+  }
+
+  // the eager walk of the stages, then the hand-off: `ready` / ev_stage (see above), or the join
+  int backward_eager(const BwdCall& call, int stage_first, int stage_last, hipStream_t* ready, hipStream_t st) {
     for (int stage = stage_first; stage <= stage_last; ++stage) MIMO_TRY(backward_stage(stage, call, st));
     bwd_next_stage = stage_last + 1 < kBwdStages ? stage_last + 1 : 0;
-    if (ready && wg_async && !prof_on && stage_last < kBwdStages - 1) {
+    if (ready && wg_async && !prof.on && stage_last < kBwdStages - 1) {
       MIMO_HIP_CHECK(hipEventRecord(ev_stage, st));
       MIMO_HIP_CHECK(hipStreamWaitEvent(ring.side, ev_stage, 0));
       *ready = ring.side;
@@ -1794,7 +1853,7 @@ struct mimo_plan {
         for (int s = S - 1; s >= 0; --s) {
           DoubleConv* dc = up4[s];
           int rows = 0;
-          const float* em = elem_masks.empty() ? nullptr : elem_masks[1 + s];
+          const float* em = elem_masks[1 + s];
           if (fuse_bwd_head && Co == 2 && !dc->mask && !em && !elem_rng_on[1 + s]) {
             // the head's input gradient is formed by the BatchNorm backward of the decoder's last convolution itself (GS_HEAD):
             // head_bwd is not launched, the gradient of the decoder output is never written
@@ -1808,15 +1867,15 @@ struct mimo_plan {
             MIMO_TRY(head_bwd_stats_launch(s_headpart, head_rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, st));
             continue;
           }
-          const int blk = prof_begin(kProfTierBase + 1, st);
-          const int pr = prof_begin(MIMO_PROF_HEAD_BWD, st);
+          const int blk = prof.begin(Profiler::kTierBase + 1, st);
+          const int pr = prof.begin(MIMO_PROF_HEAD_BWD, st);
           // (the tensor the forward's head read: z through scale / shift + ReLU, or the materialised — possibly masked — one)
           const Act& o = dc->out;
           const bool oz = o.z_live;
           MIMO_TRY(head_bwd_launch(oz ? o.z : o.a, this->st, oz ? o.z_ld : o.ld, params + heads[s].off_w, f, fp, Co, N, S, s, H * W,
                                    out, call.dout, call.dloss, label, lmask, lperm, cfg.loss_kind, cfg.eps_min, cfg.eps_max, dc->out.da,
                                    s_partial, &rows, st, oz ? o.z_scale : nullptr, oz ? o.z_shift : nullptr));
-          prof_end(pr, 0.0, 4.0 * (double)N * H * W * (2.0 * fp + Co + Co / 2), st);
+          prof.end(pr, 0.0, 4.0 * (double)N * H * W * (2.0 * fp + Co + Co / 2), st);
           if (!call.ig)
             MIMO_TRY(head_bwd_stats_launch(s_partial, rows, f, fp, Co, grads + heads[s].off_w, grads + heads[s].off_b, st));
           if (em || elem_rng_on[1 + s]) {
@@ -1824,7 +1883,7 @@ struct mimo_plan {
             MIMO_TRY(elem_mask_mul_launch(dc->out.da, this->st, dc->out.ldda, em, N, dc->out.C, dc->out.Cp, H * W, st,
                                           em ? nullptr : &g));
           }
-          prof_end(blk, 0.0, 0.0, st);
+          prof.end(blk, 0.0, 0.0, st);
           MIMO_TRY(dc_backward(dc, true, call, st));
         }
         return MIMO_OK;
@@ -1834,7 +1893,7 @@ struct mimo_plan {
       case 3: return dc_backward(up1, true, call, st);
       case 4:
         {
-          const float* em = elem_masks.empty() ? nullptr : elem_masks[0];
+          const float* em = elem_masks[0];
           if (em || elem_rng_on[0]) {
             const ElemRng g = elem_rng(0);
             MIMO_TRY(elem_mask_mul_launch(down4->out.da, this->st, down4->out.ldda, em, N, down4->out.C, down4->out.Cp,
@@ -2015,17 +2074,9 @@ int mimo_plan_profile(mimo_plan* plan, int enable) {
     set_error("mimo_plan_profile: null plan");
     return MIMO_ERR_INVALID;
   }
-  MIMO_TRY(plan->prof_collect());
-  plan->prof_on = enable != 0;
-  if (enable) {
-    for (int k = 0; k < MIMO_PROF_KINDS; ++k) {
-      plan->prof_ms[k] = plan->prof_flops[k] = plan->prof_bytes[k] = 0.0;
-      plan->prof_launches[k] = 0;
-    }
-    for (double& v : plan->prof_tier_ms) v = 0.0;
-    for (auto& row : plan->prof_kind_tier_ms)
-      for (double& v : row) v = 0.0;
-  }
+  MIMO_TRY(plan->prof.collect());
+  plan->prof.on = enable != 0;
+  if (enable) plan->prof.clear_totals();
   return MIMO_OK;
 }
 
@@ -2034,32 +2085,32 @@ int mimo_plan_profile_read(mimo_plan* plan, int kind, double* total_ms, int64_t*
     set_error("mimo_plan_profile_read: bad argument");
     return MIMO_ERR_INVALID;
   }
-  MIMO_TRY(plan->prof_collect());
-  if (total_ms) *total_ms = plan->prof_ms[kind];
-  if (launches) *launches = plan->prof_launches[kind];
-  if (flops) *flops = plan->prof_flops[kind];
-  if (bytes) *bytes = plan->prof_bytes[kind];
+  MIMO_TRY(plan->prof.collect());
+  if (total_ms) *total_ms = plan->prof.ms[kind];
+  if (launches) *launches = plan->prof.launches[kind];
+  if (flops) *flops = plan->prof.flops[kind];
+  if (bytes) *bytes = plan->prof.bytes[kind];
   return MIMO_OK;
 }
 
 int mimo_plan_profile_read_tier(mimo_plan* plan, int tier, double* forward_ms, double* backward_ms) {
-  if (!plan || tier < 0 || tier >= mimo_plan::kProfTiers) {
+  if (!plan || tier < 0 || tier >= Profiler::kTiers) {
     set_error("mimo_plan_profile_read_tier: bad argument");
     return MIMO_ERR_INVALID;
   }
-  MIMO_TRY(plan->prof_collect());
-  if (forward_ms) *forward_ms = plan->prof_tier_ms[2 * tier];
-  if (backward_ms) *backward_ms = plan->prof_tier_ms[2 * tier + 1];
+  MIMO_TRY(plan->prof.collect());
+  if (forward_ms) *forward_ms = plan->prof.tier_ms[2 * tier];
+  if (backward_ms) *backward_ms = plan->prof.tier_ms[2 * tier + 1];
   return MIMO_OK;
 }
 
 int mimo_plan_profile_read_kind_tier(mimo_plan* plan, int kind, int tier, double* ms) {
-  if (!plan || kind < 0 || kind >= MIMO_PROF_KINDS || tier < 0 || tier >= mimo_plan::kProfTiers || !ms) {
+  if (!plan || kind < 0 || kind >= MIMO_PROF_KINDS || tier < 0 || tier >= Profiler::kTiers || !ms) {
     set_error("mimo_plan_profile_read_kind_tier: bad argument");
     return MIMO_ERR_INVALID;
   }
-  MIMO_TRY(plan->prof_collect());
-  *ms = plan->prof_kind_tier_ms[kind][tier];
+  MIMO_TRY(plan->prof.collect());
+  *ms = plan->prof.kind_tier_ms[kind][tier];
   return MIMO_OK;
 }
 

@@ -29,11 +29,20 @@ def test_dz_ring_policy_under_asan_ubsan(tmp_path):
     _run_host_test(tmp_path, "dz_ring_test")
 
 
+def test_graph_replay_policy_under_asan_ubsan(tmp_path):
+    """mimo_unet_amd/csrc/graph_replay.h: every sequence of nine training forwards and backwards of two call shapes each,
+    calls that are not graphable and drops of the graphs, on a budget of three captures, from a clean plan and from what a drop
+    leaves — eager / capture / replay and the captures spent are those of the in-line logic the policy replaced, nothing is
+    captured at first sight or replayed under another key, and nothing is graphed once the budget is spent; the eval-mode
+    form (capture at first sight, no budget) likewise (tests/host/graph_replay_test.cpp)."""
+    _run_host_test(tmp_path, "graph_replay_test")
+
+
 def test_kernels_use_the_tested_header():
     """No private copy of a scheduler is left in the .hip sources."""
     csrc = os.path.join(ROOT, "mimo_unet_amd", "csrc")
     for fn, needles in (("conv_bf16x3.hip", ["using sched::pick_tile_n"]), ("conv3x3.hip", ["sched::pick_tile_n", "sched::conv_cout_pad"]),
-                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy"]), ("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
+                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy", "sched::GraphReplayPolicy"]), ("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
                         ("conv_wide.hip", ["sched::wide_config", "sched::wide_grid_x"])):
         text = open(os.path.join(csrc, fn)).read()
         for n in needles:
