@@ -313,6 +313,23 @@ int mimo_evidential_forward(const float* logits, const float* label, const float
 int mimo_evidential_backward(const float* logits, const float* label, const float* mask, const float* d_ev,
                              const float* d_loss, int32_t n, int64_t hw, float* dlogits, mimo_stream stream);
 
+/* ---- evidential model, evaluation: replaces the per-batch tail of make_predictions in the reference's
+ * scripts/test/test_nyuv2_depth_evidential.py:42-65 (test_ndvi_evidential.py has the same lines).
+ * mimo_evidential_uncertainties: EvidentialLoss.mode / aleatoric_var / epistemic_var (mimo/losses.py:258-271) straight from
+ *   the backbone logits [N,4,HW]: mean = l0, aleatoric_var = beta / (alpha - 1), epistemic_var = beta / (v (alpha - 1)),
+ *   each [N,HW], with the head arithmetic of mimo_evidential_forward (alpha = softplus(l2) + 1 rounded, then alpha - 1) in
+ *   fp32.  One pass, 16 B read + 12 B written per pixel; 16-byte accesses when hw % 4 == 0 and the pointers are aligned.
+ *   Infinities and NaNs (alpha - 1 == 0, v == 0) are written as they come.
+ * mimo_evidential_loss_gradient: dlogits [N,4,HW] = d(scale * sum over pixels of loss_map) / d logits — with scale =
+ *   1 / (N HW) the backward of `model.loss_fn(out, labels).mean()` (test_nyuv2_depth_evidential.py:44-50) down to the logits.
+ *   Bit-identical to mimo_evidential_backward(d_ev = NULL, d_loss = a tensor filled with scale): the same device function,
+ *   no weight tensor, no fill launch.  label [N,HW]; mask [N,HW] or NULL as in mimo_evidential_forward.
+ * Both are asynchronous on the stream. */
+int mimo_evidential_uncertainties(const float* logits, int32_t n, int64_t hw, float* mean, float* aleatoric_var,
+                                  float* epistemic_var, mimo_stream stream);
+int mimo_evidential_loss_gradient(const float* logits, const float* label, const float* mask, int32_t n, int64_t hw,
+                                  float scale, float* dlogits, mimo_stream stream);
+
 /* ---- validation epilogue: replaces, after the forward, the tail of MimoUnetModel.validation_step
  * (mimo_unet.py:153-183): compute_uncertainties, sqrt of the variances, calculate_dist_param(log=True) +
  * the combined NLL on the ensemble mean, the error map, compute_regression_metrics (metrics.py:22-34:

@@ -18,6 +18,11 @@ image and does not depend on eps, so here ONE gradient serves the whole sweep:
         rob.update_from(ensemble, batch["image"].cuda(), batch["label"].cuda())
     rob.write_csv(result_dir, "nyuv2")
 
+A bare `EvidentialUnetModel` is accepted wherever an ensemble is (the reference's scripts/test/test_nyuv2_depth_evidential.py
+and test_ndvi_evidential.py drive the model itself, :42-65): `EvidentialUnetModel.image_gradient` — the eval-mode forward, the
+logit gradient of `loss_fn(out, labels).mean()` in one kernel, `mimo_input_gradient` with that `dout` — then the same one
+`mimo_fgsm_perturb` launch and `predict_uncertainties` per eps.
+
 MC-dropout ensembles are rejected: the reference draws fresh dropout masks in each of its three forwards (clean, backward,
 perturbed), so there is no gradient "at the same network" to be in parity with.
 """
@@ -33,19 +38,12 @@ from .evaluation import UncertaintyEvaluator, write_tables_csv
 DEFAULT_EPSILONS = (0.0, 0.02, 0.04)  # test_nyuv2_depth.py:192
 
 
-def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
-    """Everything that can be refused is refused here, before anything touches the GPU."""
-    if getattr(ensemble, "monte_carlo_steps", 0) > 0:
-        raise NotImplementedError("fgsm_sweep: MC-dropout ensembles (monte_carlo_steps > 0) are not supported: the reference "
-                                  "draws fresh dropout masks in each of its forwards, there is nothing to be in parity with")
-    from .models.mimo_unet import MimoUnetModel
-    models = list(getattr(ensemble, "models", []))
-    if not models:
-        raise ValueError("fgsm_sweep: the ensemble has no members")
-    for m in models:
-        if not isinstance(m, MimoUnetModel):
-            raise NotImplementedError(f"fgsm_sweep: members must be MimoUnetModel (Laplace / Gaussian NLL heads), not "
-                                      f"{type(m).__name__}: the evidential model is not supported")
+def _is_evidential(model) -> bool:
+    from .models.evidential_unet import EvidentialUnetModel
+    return isinstance(model, EvidentialUnetModel)
+
+
+def _validate_epsilons(epsilons: Sequence[float]) -> Tuple[float, ...]:
     eps = tuple(float(e) for e in epsilons)
     if not eps:
         raise ValueError("fgsm_sweep: no epsilons")
@@ -56,11 +54,37 @@ def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
     return eps
 
 
+def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
+    """Everything that can be refused is refused here, before anything touches the GPU."""
+    if _is_evidential(ensemble):  # the model itself, not an ensemble of it
+        ensemble.require_eval("fgsm_sweep")
+        if ensemble.model._geom.precision not in ("fp32", "split16"):
+            raise NotImplementedError(f"fgsm_sweep: the input gradient is implemented for the fp32 and split16 precisions, not "
+                                      f"{ensemble.model._geom.precision!r}")
+        return _validate_epsilons(epsilons)
+    if getattr(ensemble, "monte_carlo_steps", 0) > 0:
+        raise NotImplementedError("fgsm_sweep: MC-dropout ensembles (monte_carlo_steps > 0) are not supported: the reference "
+                                  "draws fresh dropout masks in each of its forwards, there is nothing to be in parity with")
+    from .models.mimo_unet import MimoUnetModel
+    models = list(getattr(ensemble, "models", []))
+    if not models:
+        raise ValueError("fgsm_sweep: the ensemble has no members")
+    for m in models:
+        if not isinstance(m, MimoUnetModel):
+            raise NotImplementedError(f"fgsm_sweep: members must be MimoUnetModel (Laplace / Gaussian NLL heads), not "
+                                      f"{type(m).__name__}: an evidential model is not supported as a member, pass the "
+                                      f"EvidentialUnetModel itself")
+    return _validate_epsilons(epsilons)
+
+
 def image_gradient(ensemble, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """d loss / d image [B,C,H,W] of `loss_fn(y_pred, log_param, labels)` as the reference's script forms it
     (test_nyuv2_depth.py:44-55): the mean NLL over the concatenated subnetwork axis of ALL members, i.e. a weight of
-    1 / S_total on every subnetwork's mean loss.  Members are summed in list order (member 0 assigns, the others add)."""
+    1 / S_total on every subnetwork's mean loss.  Members are summed in list order (member 0 assigns, the others add).
+    A bare `EvidentialUnetModel`: the gradient of `loss_fn(out, labels).mean()` (`EvidentialUnetModel.image_gradient`)."""
     _validate(ensemble, (0.0,))
+    if _is_evidential(ensemble):
+        return ensemble.image_gradient(image, label, mask)[0]
     if not image.is_cuda:
         from . import _lib as L
         raise L.MimoHipError("fgsm_sweep runs on an AMD GPU through libmimo_hip.so; move the ensemble and its inputs to cuda")
@@ -80,7 +104,7 @@ def fgsm_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Seq
                mask: Optional[torch.Tensor] = None, clip: Optional[Tuple[float, float]] = (0.0, 1.0),
                return_perturbed: bool = False) -> Dict[float, tuple]:
     """{eps: (mean, aleatoric_var, epistemic_var)} [B,Ct,H,W] on the device, for the image attacked with each eps
-    (eps = 0 is the clamped clean image, as in the reference).  image [B,C,H,W], label [B,Ct,H,W], mask [B,1,H,W] or None
+    (eps = 0 is the clamped clean image, as in the reference).  `ensemble`: an `EnsembleModule` or a bare `EvidentialUnetModel`.  image [B,C,H,W], label [B,Ct,H,W], mask [B,1,H,W] or None
     (weights the loss the gradient is taken of).  clip: the range the perturbed image is clamped to; None = no clamp.
     return_perturbed: the tuples get the perturbed image [B,C,H,W] as a fourth entry.
     The members' `.grad`, BatchNorm buffers and train / eval flags are left as they were."""
@@ -89,6 +113,12 @@ def fgsm_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Seq
     dimage = image_gradient(ensemble, image, label, mask)
     lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
     perturbed = fgsm_perturb(image.detach(), dimage, eps, lo, hi)
+    if _is_evidential(ensemble):
+        out = {}
+        for k, e in enumerate(eps):
+            res = ensemble.predict_uncertainties(perturbed[k])
+            out[e] = res + (perturbed[k],) if return_perturbed else res
+        return out
     keep, raw = ensemble.keep_on_device, ensemble.return_raw_predictions
     ensemble.keep_on_device, ensemble.return_raw_predictions = True, False
     out = {}

@@ -355,6 +355,39 @@ def evidential_head_loss(logits: torch.Tensor, label: Optional[torch.Tensor] = N
     return ev, (loss if label is not None else None)
 
 
+def evidential_uncertainties(logits: torch.Tensor):
+    """Backbone logits [B,4,H,W] -> (mean, aleatoric_var, epistemic_var), each [B,1,H,W], in one pass
+    (mimo_evidential_uncertainties; EvidentialLoss.mode / aleatoric_var / epistemic_var of the reference's mimo/losses.py:258-271
+    on the softplus heads).  Non-finite values (alpha - 1 == 0, v == 0) pass through."""
+    lib = L.load()
+    assert logits.is_cuda and logits.dim() == 4 and logits.shape[1] == 4, tuple(logits.shape)
+    logits = logits.detach().contiguous().float()
+    b, _, h, w = logits.shape
+    outs = [torch.empty(b, 1, h, w, device=logits.device, dtype=torch.float32) for _ in range(3)]
+    with torch.cuda.device(logits.device):
+        L.check(lib.mimo_evidential_uncertainties(logits.data_ptr(), b, h * w, outs[0].data_ptr(), outs[1].data_ptr(),
+                                                  outs[2].data_ptr(), L.current_stream()), "mimo_evidential_uncertainties")
+    return tuple(outs)
+
+
+def evidential_loss_gradient(logits: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor], scale: float) -> torch.Tensor:
+    """d(scale * sum of the per-pixel evidential loss (x mask)) / d logits, [B,4,H,W] (mimo_evidential_loss_gradient): what
+    `mimo_evidential_backward` gives for a d_loss tensor filled with `scale`, bit for bit, without that tensor.
+    label [B,1,H,W] (or [B,H,W]), mask [B,H,W] (or [B,1,H,W]) or None."""
+    lib = L.load()
+    assert logits.is_cuda and logits.dim() == 4 and logits.shape[1] == 4, tuple(logits.shape)
+    logits = logits.detach().contiguous().float()
+    b, _, h, w = logits.shape
+    assert label.numel() == b * h * w and (mask is None or mask.numel() == b * h * w)
+    label_c = label.detach().reshape(b, h * w).contiguous().float()
+    mask_c = None if mask is None else mask.detach().reshape(b, h * w).contiguous().float()
+    out = torch.empty_like(logits)
+    with torch.cuda.device(logits.device):
+        L.check(lib.mimo_evidential_loss_gradient(logits.data_ptr(), label_c.data_ptr(), L.ptr(mask_c) or None, b, h * w,
+                                                  float(scale), out.data_ptr(), L.current_stream()), "mimo_evidential_loss_gradient")
+    return out
+
+
 class _LossBufferStep(torch.autograd.Function):
     """(mean(loss * weights), weights, mean(loss)) with `loss` written into row `index` of the ring — one launch
     (include/mimo_hip.h mimo_loss_buffer_step).  d mean(loss * weights) / d loss = weights / S: the weights carry no

@@ -167,7 +167,13 @@ class UncertaintyEvaluator:
 
     def update_from(self, ensemble, image, label, mask=None) -> None:
         """Run an `EnsembleModule` on `image` and feed its `(mean, aleatoric_var, epistemic_var)` without leaving the
-        device (the module's `keep_on_device` is switched on for the call)."""
+        device (the module's `keep_on_device` is switched on for the call).  A bare `EvidentialUnetModel` is fed through its
+        `predict_uncertainties` (the reference's scripts/test/test_nyuv2_depth_evidential.py drives the model itself)."""
+        from .models.evidential_unet import EvidentialUnetModel
+        if isinstance(ensemble, EvidentialUnetModel):
+            mean, av, ev = ensemble.predict_uncertainties(image)
+            self.update(mean, av, ev, label.to(mean.device), None if mask is None else mask.to(mean.device))
+            return
         keep, raw = ensemble.keep_on_device, ensemble.return_raw_predictions
         ensemble.keep_on_device, ensemble.return_raw_predictions = True, False
         try:

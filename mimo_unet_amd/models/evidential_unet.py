@@ -6,12 +6,12 @@ softplus heads and the loss are one fused HIP kernel over the [B,4,H,W] logits (
 from __future__ import annotations
 
 from argparse import ArgumentParser
-from typing import Any, Dict, Literal
+from typing import Any, Dict, Literal, Optional
 
 import torch
 import torch.nn.functional as F
 
-from ..engine import evidential_head_loss
+from ..engine import evidential_head_loss, evidential_loss_gradient, evidential_uncertainties
 from ..lightning_compat import LightningModule
 from ..losses import EvidentialLoss
 from ..metrics import compute_regression_metrics
@@ -65,6 +65,59 @@ class EvidentialUnetModel(LightningModule):
             return evidential_head_loss(self._logits(image), label, mask)
         out = self(image)
         return out, self.loss_fn(out, label, mask=mask)
+
+    def require_eval(self, what: str) -> None:
+        """Evaluation entry points run the network as `model.eval()` leaves it: BatchNorm on running statistics, dropout off."""
+        net = self.model
+        if self.training or net._bn_training() or any(d.p > 0.0 and d.training for d in net._dropout_modules()):
+            raise NotImplementedError(f"{what}: eval mode only (call model.eval(): BatchNorm on running statistics, dropout off)")
+
+    def predict_uncertainties(self, image: torch.Tensor):
+        """image [B,C,H,W] -> (mean, aleatoric_var, epistemic_var), each [B,1,H,W], on the device: the no-grad forward on an
+        inference plan and one pass over the logits (mimo_evidential_uncertainties) instead of the head kernel plus
+        `loss_fn.mode / aleatoric_var / epistemic_var` (the reference's test_nyuv2_depth_evidential.py:59-65)."""
+        self.require_eval("EvidentialUnetModel.predict_uncertainties")
+        if image.dim() != 4 or image.shape[1] != self.in_channels:
+            raise ValueError("channel dimension must match in_channels")
+        with torch.no_grad():
+            return evidential_uncertainties(self._logits(image.detach()))
+
+    def image_gradient(self, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                       dimage: Optional[torch.Tensor] = None):
+        """(d loss / d image [B,C,H,W], logits [B,4,H,W]) of `loss_fn(out, labels).mean()` as the reference's test script
+        takes it (test_nyuv2_depth_evidential.py:42-53): the mean over all B*H*W pixels, masked ones included.  The eval-mode
+        forward with its graph kept, the logit gradient in one kernel (mimo_evidential_loss_gradient, scale = 1 / (B H W)) and
+        the data-gradient chain (mimo_input_gradient): no weight gradient, no `.grad`, no BatchNorm buffer written.
+        label [B,1,H,W]; mask [B,H,W] (or the evaluators' [B,1,H,W], of which the [B,H,W] view is taken) or None."""
+        self.require_eval("EvidentialUnetModel.image_gradient")
+        net = self.model
+        if net._geom.precision not in ("fp32", "split16"):
+            raise NotImplementedError(f"EvidentialUnetModel.image_gradient: implemented for the fp32 and split16 precisions, "
+                                      f"not {net._geom.precision!r}")
+        if image.dim() != 4 or image.shape[1] != self.in_channels:
+            raise ValueError("channel dimension must match in_channels")
+        b, _, h, w = image.shape
+        if tuple(label.shape) != (b, 1, h, w):
+            raise ValueError(f"label: expected {(b, 1, h, w)}, got {tuple(label.shape)}")
+        if mask is not None:
+            if tuple(mask.shape) not in ((b, h, w), (b, 1, h, w)):
+                raise ValueError(f"mask: expected {(b, h, w)} or {(b, 1, h, w)}, got {tuple(mask.shape)}")
+            mask = mask.reshape(b, h, w)
+        if not image.is_cuda:
+            from .. import _lib as L
+            raise L.MimoHipError("EvidentialUnetModel.image_gradient runs on an AMD GPU through libmimo_hip.so; move the model "
+                                 "and its inputs to cuda")
+        image = image.detach().contiguous().float()
+        label = label.detach().to(image.device)
+        mask = None if mask is None else mask.detach().to(image.device)
+        if dimage is None:
+            dimage = torch.empty_like(image)
+        # 1 / (B H W) as torch's mean backward forms it: one fp32 division
+        scale = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(b * h * w), dtype=torch.float32))
+        with torch.no_grad():
+            out = net.image_gradient_from_dout(
+                image, lambda logits: evidential_loss_gradient(logits[:, 0], label, mask, scale).unsqueeze(1), dimage)
+        return dimage, out[:, 0]
 
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int) -> Dict[str, torch.Tensor]:
         image, label = batch["image"], batch["label"]

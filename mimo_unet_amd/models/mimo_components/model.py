@@ -551,6 +551,31 @@ class MimoUNet(nn.Module):
         self._inference_keep = (image, label, mask, dloss, out)  # the plan still points at these
         return out, loss
 
+    def image_gradient_from_dout(self, image: torch.Tensor, dout_fn, dimage: torch.Tensor, accumulate: bool = False):
+        """The half of `image_gradient` for a loss the engine does not know (the evidential head): the eval-mode forward of
+        `image` [B,C,H,W] with its graph kept, `dout_fn(logits [B,S,Co,H,W]) -> dout` of the same shape made by the caller,
+        and `mimo_input_gradient(dout, dloss = NULL)` written (accumulate: added) into `dimage` [B,C,H,W] — no
+        `mimo_loss_forward`, no `.grad`, no BatchNorm buffer, no autograd graph.  Returns the logits."""
+        if self._bn_training() or any(d.p > 0.0 and d.training for d in self._dropout_modules()):
+            raise NotImplementedError("MimoUNet.image_gradient_from_dout: eval mode only (BatchNorm on running statistics, dropout off)")
+        if self._geom.precision not in ("fp32", "split16"):
+            raise NotImplementedError(f"MimoUNet.image_gradient_from_dout: implemented for the fp32 and split16 precisions, not "
+                                      f"{self._geom.precision!r} (mimo_input_gradient)")
+        image = image.contiguous().float()
+        if image.dim() != 4 or image.shape[1] != self.in_channels:
+            raise ValueError(f"expected [B,{self.in_channels},H,W], got {tuple(image.shape)}")
+        plan = self._plan_for(image, None, grad_only=True)
+        out = torch.empty(image.shape[0], self.num_subnetworks, self.out_channels, plan.height, plan.width, device=image.device,
+                          dtype=torch.float32)
+        plan.bind(self._flat_params, None, self._flat_buffers)
+        plan.forward(image, out, training=False, broadcast_subnetworks=True, no_grad=False, param_version=self._param_version())
+        dout = dout_fn(out).contiguous().float()
+        assert dout.shape == out.shape and dout.is_cuda, (tuple(dout.shape), tuple(out.shape))
+        plan.input_gradient(dout, None, dimage, accumulate)
+        plan.generation += 1
+        self._inference_keep = (image, out, dout)  # the plan still points at these
+        return out
+
     def _run_backward(self, plan: Plan, dout, dloss, dx) -> None:
         g = self._flat_grads
         views = self._param_views

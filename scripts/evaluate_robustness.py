@@ -6,6 +6,11 @@ loss, `x.grad`, the torch expression of the attack, then the ensemble forward.
     python scripts/evaluate_robustness.py --synthetic 4 --result_dir out                      # seeded model and batches
     python scripts/evaluate_robustness.py --synthetic 4 --compare --result_dir out            # + the older route, alternating
     python scripts/evaluate_robustness.py --model_checkpoint_paths a.ckpt b.ckpt --batch_dir batches/ --result_dir out
+    python scripts/evaluate_robustness.py --evidential --synthetic 4 --compare --result_dir out   # a bare EvidentialUnetModel
+    python scripts/evaluate_robustness.py --evidential --model_checkpoint_paths ev.ckpt --batch_dir batches/ --result_dir out
+
+--evidential: the reference's scripts/test/test_nyuv2_depth_evidential.py — ONE `EvidentialUnetModel` (one checkpoint, or a
+seeded fbc = --fbc network) instead of an ensemble; the older route is then autograd through the model, `.mean()` of its loss.
 
 --batch_dir: `*.npy` files holding one dict each ({"image": [B,C,H,W], "label": [B,1,H,W], optional "mask"}), saved with
 np.save(..., allow_pickle=True).  --synthetic N: N seeded batches of --batch x --channels x --size x --size (defaults: the
@@ -44,6 +49,25 @@ def older_route(ensemble, image, label, epsilons, mask=None):
     return out
 
 
+def older_route_evidential(model, image, label, epsilons, mask=None):
+    """Per eps (the reference's loop, test_nyuv2_depth_evidential.py:39-65): autograd through the model to the image (the whole
+    training backward runs for it), the torch expression of the attack, the model again, the head kernel's parameters through
+    `loss_fn.mode / aleatoric_var / epistemic_var` as three torch launches."""
+    out = {}
+    m3 = None if mask is None else mask.reshape(mask.shape[0], *mask.shape[-2:])
+    for eps in epsilons:
+        x = image.clone().requires_grad_(True)
+        _, loss = model._forward_with_loss(x, label, m3)
+        model.zero_grad()
+        loss.mean().backward()
+        perturbed = torch.clamp(image + eps * x.grad.sign(), 0, 1)
+        with torch.no_grad():
+            ev = model(perturbed)
+            out[eps] = tuple(f(ev).unsqueeze(1) for f in (model.loss_fn.mode, model.loss_fn.aleatoric_var, model.loss_fn.epistemic_var))
+    model.zero_grad()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model_checkpoint_paths", nargs="*", default=[])
@@ -56,6 +80,7 @@ def main():
     ap.add_argument("--members", type=int, default=1, help="seeded members of the synthetic ensemble")
     ap.add_argument("--epsilons", type=float, nargs="+", default=[0.0, 0.02, 0.04])
     ap.add_argument("--name", default="synthetic")
+    ap.add_argument("--evidential", action="store_true", help="one EvidentialUnetModel instead of an ensemble")
     ap.add_argument("--compare", action="store_true", help="also time the autograd route, in alternating pairs")
     ap.add_argument("--result_dir", required=True)
     args = ap.parse_args()
@@ -63,7 +88,22 @@ def main():
     torch.cuda.set_device(dev)
     from mimo.models.ensemble import EnsembleModule
     models = None
-    if not args.model_checkpoint_paths:
+    if args.evidential:
+        from mimo.models.evidential_unet import EvidentialUnetModel
+        if len(args.model_checkpoint_paths) > 1:
+            ap.error("--evidential takes one checkpoint")
+        if args.model_checkpoint_paths:
+            ensemble = EvidentialUnetModel.load_from_checkpoint(args.model_checkpoint_paths[0])
+        else:
+            if args.synthetic < 1:
+                ap.error("give a checkpoint or --synthetic N")
+            torch.manual_seed(0)
+            ensemble = EvidentialUnetModel(in_channels=args.channels, out_channels=4, filter_base_count=args.fbc,
+                                           center_dropout_rate=0.0, final_dropout_rate=0.0, encoder_dropout_rate=0.0,
+                                           core_dropout_rate=0.0, decoder_dropout_rate=0.0, weight_decay=0.0, learning_rate=1e-3,
+                                           seed=0)
+        ensemble = ensemble.to(dev).eval()
+    elif not args.model_checkpoint_paths:
         if args.synthetic < 1:
             ap.error("give checkpoints or --synthetic N")
         from mimo.models.mimo_unet import MimoUnetModel
@@ -74,7 +114,9 @@ def main():
                                         center_dropout_rate=0.0, final_dropout_rate=0.0, encoder_dropout_rate=0.0,
                                         core_dropout_rate=0.0, decoder_dropout_rate=0.0, loss="laplace_nll", weight_decay=0.0,
                                         learning_rate=1e-3, seed=i, loss_buffer_size=10, loss_buffer_temperature=0.3).cuda())
-    ensemble = EnsembleModule(args.model_checkpoint_paths, models=models, keep_on_device=True).to(dev)
+    if not args.evidential:
+        ensemble = EnsembleModule(args.model_checkpoint_paths, models=models, keep_on_device=True).to(dev)
+    older = older_route_evidential if args.evidential else older_route
     if args.batch_dir:
         batches = [np.load(f, allow_pickle=True).item() for f in sorted(glob.glob(os.path.join(args.batch_dir, "*.npy")))]
     else:
@@ -96,7 +138,7 @@ def main():
     first = {k: torch.as_tensor(batches[0][k]).to(dev) for k in ("image", "label")}
     fgsm_sweep(ensemble, first["image"], first["label"], eps)  # first calls: plans, code load
     if args.compare:
-        older_route(ensemble, first["image"], first["label"], eps)
+        older(ensemble, first["image"], first["label"], eps)
     new_ms, old_ms, agree = [], [], []
     for i, b in enumerate(batches):
         image, label = (torch.as_tensor(b[k]).to(dev) for k in ("image", "label"))
@@ -108,7 +150,7 @@ def main():
                 res["new"], ms = timed(lambda: fgsm_sweep(ensemble, image, label, eps, mask=mask))
                 new_ms.append(ms)
             else:
-                res["old"], ms = timed(lambda: older_route(ensemble, image, label, eps, mask=mask))
+                res["old"], ms = timed(lambda: older(ensemble, image, label, eps, mask=mask))
                 old_ms.append(ms)
         if args.compare:  # the two routes' predictions differ only where a gradient's sign is within rounding of zero
             e = eps[-1]
@@ -122,7 +164,7 @@ def main():
             rob.evaluators[e].update(mean, av, ev, label, mask)
     tables = rob.compute()
     rob.write_csv(args.result_dir, args.name, tables)
-    out = {"epsilons": list(eps), "batches": len(batches), "pixels_per_batch": int(batches[0]["image"].shape[0]) * args.size * args.size
+    out = {"model": "evidential" if args.evidential else "ensemble", "epsilons": list(eps), "batches": len(batches), "pixels_per_batch": int(batches[0]["image"].shape[0]) * args.size * args.size
            if not args.batch_dir else None, "sweep_ms_median": float(np.median(new_ms)), "sweep_ms_min": float(np.min(new_ms)),
            "mae_per_eps": {str(e): tables[e]["mae"] for e in eps}}
     if old_ms:

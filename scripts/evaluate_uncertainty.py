@@ -5,6 +5,11 @@ of the host route (the same tables from `.cpu()` copies: numpy argsort + 41 quan
     python scripts/evaluate_uncertainty.py --synthetic 8 --result_dir out            # seeded maps, no network
     python scripts/evaluate_uncertainty.py --synthetic_model --synthetic 2 --monte_carlo_steps 4 --result_dir out
     python scripts/evaluate_uncertainty.py --model_checkpoint_paths a.ckpt b.ckpt --batch_dir batches/ --result_dir out
+    python scripts/evaluate_uncertainty.py --evidential --synthetic 2 --result_dir out   # a seeded EvidentialUnetModel
+    python scripts/evaluate_uncertainty.py --evidential --model_checkpoint_paths ev.ckpt --batch_dir batches/ --result_dir out
+
+--evidential: ONE `EvidentialUnetModel` (one checkpoint, or a seeded network) fed through `predict_uncertainties`, as the
+reference's scripts/test/test_nyuv2_depth_evidential.py / test_ndvi_evidential.py drive the model itself.
 
 --batch_dir: `*.npy` files holding one dict each ({"image": [B,C,H,W], "label": [B,1,H,W], optional "mask"}), saved with
 np.save(..., allow_pickle=True).  --synthetic N without a model feeds N seeded batches of (mean, aleatoric_var,
@@ -56,6 +61,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model_checkpoint_paths", nargs="*", default=[])
     ap.add_argument("--synthetic_model", action="store_true", help="a seeded MIMO U-Net instead of checkpoints")
+    ap.add_argument("--evidential", action="store_true", help="one EvidentialUnetModel instead of an ensemble")
     ap.add_argument("--monte_carlo_steps", type=int, default=0)
     ap.add_argument("--batch_dir")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
@@ -69,7 +75,19 @@ def main():
     torch.cuda.set_device(dev)
 
     ensemble = None
-    if args.model_checkpoint_paths or args.synthetic_model:
+    if args.evidential:
+        from mimo.models.evidential_unet import EvidentialUnetModel
+        if len(args.model_checkpoint_paths) > 1 or args.monte_carlo_steps:
+            ap.error("--evidential takes one checkpoint and no --monte_carlo_steps")
+        if args.model_checkpoint_paths:
+            ensemble = EvidentialUnetModel.load_from_checkpoint(args.model_checkpoint_paths[0])
+        else:
+            torch.manual_seed(0)
+            ensemble = EvidentialUnetModel(in_channels=3, out_channels=4, filter_base_count=8, center_dropout_rate=0.0,
+                                           final_dropout_rate=0.0, encoder_dropout_rate=0.0, core_dropout_rate=0.0,
+                                           decoder_dropout_rate=0.0, weight_decay=0.0, learning_rate=1e-3, seed=0)
+        ensemble = ensemble.to(dev).eval()
+    elif args.model_checkpoint_paths or args.synthetic_model:
         from mimo.models.ensemble import EnsembleModule
         models = None
         if args.synthetic_model:
@@ -109,7 +127,8 @@ def main():
             if args.no_host_route:
                 ev.update_from(ensemble, image, label, mask)  # the three-line form of INTEGRATION.md
             else:  # the same two steps apart, to time the update alone and to keep the maps for the host route
-                timed_update(ensemble(image) + (label,), mask)
+                maps = ensemble.predict_uncertainties(image) if args.evidential else ensemble(image)
+                timed_update(tuple(maps) + (label,), mask)
     else:
         if args.synthetic < 1:
             ap.error("give checkpoints, --synthetic_model or --synthetic N")
