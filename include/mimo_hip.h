@@ -194,6 +194,21 @@ int mimo_plan_num_double_convs(const mimo_plan* plan);
 int mimo_plan_double_conv_channels(const mimo_plan* plan, int index); /* Cout of DoubleConv #index */
 int mimo_forward(mimo_plan* plan, const mimo_forward_args* args, mimo_stream stream);
 
+/* ---- subnetwork permutations: replaces the draws of apply_input_transform (mimo/models/utils.py:27-36:
+ * `torch.randperm(B).repeat(batch_repetitions)`, then per subnetwork `main[:k][torch.randperm(k)]` in front of the shared
+ * tail `main[k:]`) by one launch — the `perm` argument of mimo_forward / mimo_loss_forward / mimo_training_epilogue.
+ * perm int64 [S][M], M = batch * reps; main_out int64 [M] or NULL; k = int(M * (1 - input_repetition_probability)) as the
+ * caller's Python computes it, 0 <= k <= M.  Same structure as the reference, the engine's own generator (so not the
+ * reference's values): with bits(stream, j) = 64 bits of philox4x32_10(ctr = (j >> 1, stream, offset_lo, offset_hi),
+ * key = seed) — words (x, y) for even j, (z, w) for odd j, the first word low — and key(stream, j) = (bits & ~0xFFF) | j,
+ *   base = argsort of key(0, 0 .. batch-1), main[i] = base[i mod batch], sigma_s = argsort of key(1 + s, 0 .. k-1),
+ *   perm[s][i] = main[sigma_s[i]] for i < k and main[i] for i >= k.
+ * (seed, offset): the caller's generator, which it advances by one counter block (4), as for rng_seed / rng_offset above.
+ * One workgroup per subnetwork, a bitonic sort of the 64-bit keys in LDS: M <= 4096 and S <= 64, MIMO_ERR_INVALID beyond
+ * (nothing is launched or written).  Asynchronous on the stream; no allocation, no atomics. */
+int mimo_draw_permutations(int64_t* perm, int64_t* main_out, int32_t batch, int32_t reps, int32_t k, int32_t s,
+                           uint64_t seed, uint64_t offset, mimo_stream stream);
+
 /* ---- loss: replaces UncertaintyLoss.forward(reduce_mean=False).mean((0,2,3,4))
  * (losses.py:132-164, mimo_unet.py:241-242) on the logits of the last mimo_forward.
  * label [N,Ct,H,W], mask [N,1,H,W] or NULL, both gathered through perm like x.

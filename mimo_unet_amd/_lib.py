@@ -68,6 +68,7 @@ _SIGNATURES = {
     "mimo_plan_num_double_convs": (C.c_int, [_P]),
     "mimo_plan_double_conv_channels": (C.c_int, [_P, C.c_int]),
     "mimo_forward": (C.c_int, [_P, C.POINTER(ForwardArgs), _P]),
+    "mimo_draw_permutations": (C.c_int, [_P, _P, _I, _I, _I, _I, C.c_uint64, C.c_uint64, _P]),
     "mimo_loss_forward": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "mimo_backward": (C.c_int, [_P, _P, _P, _P, _P]),
     "mimo_backward_stage": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),

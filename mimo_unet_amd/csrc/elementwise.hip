@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "elementwise.h"
+#include "philox.h"
 
 namespace mimo {
 
@@ -983,18 +984,7 @@ int fold_slice_launch(const void* dxpad, int dt, int ldp, int choff, void* da, i
 // offset, site, element index), so the backward regenerates exactly what the forward used and nothing is stored for
 // the element-wise sites.  Statistically equivalent to the reference's Bernoulli draws (keep with probability 1 - p,
 // scale by 1 / (1 - p)); bit-level parity with recorded masks stays available through the mask arguments.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-  constexpr unsigned int M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned int hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-    const unsigned int hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += W0;
-    key.y += W1;
-  }
-  return ctr;
-}
+// (philox4x32_10: philox.h, shared with the permutation draw of perm_draw.hip)
 __device__ __forceinline__ float4 philox_keep4(unsigned int i0, unsigned int i1, unsigned int site, uint64_t seed, uint64_t offset,
                                                float p, float inv_keep) {
   const uint4 r = philox4x32_10(make_uint4(i0, i1, (unsigned int)offset ^ (site << 24), (unsigned int)(offset >> 32)),

@@ -301,6 +301,26 @@ def fgsm_perturb(image: torch.Tensor, dimage: torch.Tensor, epsilons: Sequence[f
     return out
 
 
+def draw_permutations(batch: int, reps: int, k: int, s: int, seed: int, offset: int, device, want_main: bool = False):
+    """[s, batch * reps] int64 gather indices of apply_input_transform (the reference's mimo/models/utils.py:27-36) drawn by
+    one launch from the Philox stream keyed by (seed, offset) — mimo_draw_permutations, include/mimo_hip.h: a main
+    permutation of the batch repeated `reps` times, its first k entries re-shuffled independently per subnetwork.
+    want_main: also return that main permutation [batch * reps].  Sizes the kernel refuses (batch * reps > 4096, s > 64)
+    raise MimoHipError."""
+    device = torch.device(device if device is not None else "cpu")
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise L.MimoHipError(f"draw_permutations runs on an AMD GPU (mimo_draw_permutations; no CPU fallback); got {device}")
+    lib = L.load()
+    m = int(batch) * int(reps)
+    with torch.cuda.device(device):
+        perm = torch.empty(int(s), m, device=device, dtype=torch.int64)
+        main = torch.empty(m, device=device, dtype=torch.int64) if want_main else None
+        L.check(lib.mimo_draw_permutations(perm.data_ptr(), L.ptr(main) or None, int(batch), int(reps), int(k), int(s),
+                                           int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), L.current_stream()),
+                "mimo_draw_permutations")
+    return (perm, main) if want_main else perm
+
+
 def uncertainties(p1: torch.Tensor, p2: torch.Tensor, loss: str = "laplace_nll"):
     """[N,S,C,H,W] x2 -> (mean, aleatoric_var, epistemic_var) each [N,C,H,W], on device."""
     lib = L.load()

@@ -13,6 +13,7 @@ the batch — the permutation indices go to the engine, which gathers while load
 kernels (`mimo_loss_forward`, `mimo_backward` dloss argument)."""
 from __future__ import annotations
 
+import os
 from argparse import ArgumentParser
 from typing import Any, Dict, Literal, Optional, Tuple
 
@@ -28,6 +29,8 @@ from .mimo_components.loss_buffer import LossBuffer
 from .mimo_components.model import MimoUNet
 from .utils import (compute_uncertainties, draw_subnetwork_permutations, flatten_subnetwork_dimension,
                     gather_subnetworks)
+
+_ENGINE_PERM = os.environ.get("MIMO_ENGINE_PERM", "0") != "0"  # 1: training_step's permutations are drawn inside the engine
 
 
 class MimoUnetModel(LightningModule):
@@ -87,6 +90,9 @@ class MimoUnetModel(LightningModule):
         self.save_hyperparameters()
         self.save_hyperparameters({"loss": loss, "trainable_params": count_trainable_parameters(self.model)})
         self.use_fused_optimizer = True
+        # training_step's subnetwork permutations: False = torch.randperm on the device + S CPU randperms (the reference's
+        # generator streams, which the golden fixtures replay); True = one engine launch (models/utils.py, MIMO_ENGINE_PERM)
+        self.engine_perm = _ENGINE_PERM
 
     # The reference wraps the net in torch.compile (mimo_unet.py:89-91).  The engine is already a
     # fixed kernel schedule; nothing to trace.  Checkpoints written by a compiled reference model
@@ -112,7 +118,7 @@ class MimoUnetModel(LightningModule):
         image, label = batch["image"], batch["label"]
         mask = batch["mask"] if "mask" in batch else None
         perms = draw_subnetwork_permutations(image.shape[0], self.num_subnetworks, self.input_repetition_probability,
-                                             self.batch_repetitions, device=image.device)
+                                             self.batch_repetitions, device=image.device, engine=self.engine_perm)
         return self.training_step_with_perms(image, label, mask, perms)
 
     def training_step_with_perms(self, image, label, mask, perms) -> Dict[str, torch.Tensor]:

@@ -43,11 +43,34 @@ def _cpu_randperms_on_device(k: int, count: int, device) -> torch.Tensor:
     return dev
 
 
+def _engine_permutations(batch: int, num_subnetworks: int, k: int, batch_repetitions: int, device) -> torch.Tensor:
+    """The same structure from the engine's generator in ONE launch (engine.draw_permutations): Philox keyed by torch's CUDA
+    generator of `device`, whose offset advances by one counter block (4) exactly as MimoUNet._engine_rng_sites advances it
+    for dropout — a step with active dropout consumes two disjoint blocks, the permutations' first.  No CPU generator, no
+    pinned ring, no upload."""
+    from .._lib import MimoHipError
+    from ..engine import draw_permutations
+    dev = torch.device(device if device is not None else "cpu")
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise MimoHipError(f"draw_subnetwork_permutations(engine=True) draws on an AMD GPU (mimo_draw_permutations); got {dev}")
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    gen = torch.cuda.default_generators[index]
+    seed, offset = gen.initial_seed(), gen.get_offset()
+    perms = draw_permutations(batch, batch_repetitions, k, num_subnetworks, seed, offset, torch.device("cuda", index))
+    gen.set_offset(offset + 4)  # after the launch: a refused size leaves the generator where it was
+    return perms
+
+
 def draw_subnetwork_permutations(batch: int, num_subnetworks: int, input_repetition_probability: float = 0.0,
-                                 batch_repetitions: int = 1, device=None) -> torch.Tensor:
+                                 batch_repetitions: int = 1, device=None, engine: bool = False) -> torch.Tensor:
     """[S, batch*reps] int64 gather indices: a main permutation of the batch, of which the first
     (1 - irp) share is re-shuffled independently per subnetwork (utils.py:27-36).  One upload and one gather for all S
-    rows (round 4: S uploads, S gathers, S concatenations and a stack were ~8 five-microsecond launches per step)."""
+    rows (round 4: S uploads, S gathers, S concatenations and a stack were ~8 five-microsecond launches per step).
+    engine=True: drawn inside the engine instead (MIMO_ENGINE_PERM, `_engine_permutations`) — the same distribution, other
+    values than the reference's generator streams, which the default route replays for the golden fixtures."""
+    if engine:
+        k = int(batch * batch_repetitions * (1.0 - input_repetition_probability))
+        return _engine_permutations(batch, num_subnetworks, k, batch_repetitions, device)
     main = torch.randperm(batch, device=device)
     if batch_repetitions != 1:
         main = main.repeat(batch_repetitions)
@@ -66,9 +89,9 @@ def gather_subnetworks(t: Optional[torch.Tensor], perms: torch.Tensor) -> Option
 
 
 def apply_input_transform(image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor], num_subnetworks: int,
-                          input_repetition_probability: float = 0.0, batch_repetitions: int = 1):
+                          input_repetition_probability: float = 0.0, batch_repetitions: int = 1, engine: bool = False):
     perms = draw_subnetwork_permutations(image.shape[0], num_subnetworks, input_repetition_probability,
-                                         batch_repetitions, device=image.device)
+                                         batch_repetitions, device=image.device, engine=engine)
     return gather_subnetworks(image, perms), gather_subnetworks(label, perms), gather_subnetworks(mask, perms)
 
 
