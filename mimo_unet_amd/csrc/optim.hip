@@ -26,8 +26,10 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   if (found_inf && *found_inf != 0.f) return;  // the scaler saw an inf / nan gradient: skip this step
   if (step_dev) {
     const float t = *step_dev;
-    bc1 = 1.f - powf(beta1, t);
-    bc2_sqrt = sqrtf(1.f - powf(beta2, t));
+    // 1 - beta^t as -expm1(t log1p(beta - 1)) (beta - 1 is exact): 1 - powf(beta, t) keeps the rounding of a number near 1
+    // in a result of about t (1 - beta) — 6.7e-6 of the second-moment correction at t = 2, 1.7e-8 in this form
+    bc1 = -expm1f(t * log1pf(beta1 - 1.f));
+    bc2_sqrt = sqrtf(-expm1f(t * log1pf(beta2 - 1.f)));
   }
   if (amp_scale) grad_scale /= *amp_scale;
   const int64_t n4 = n / 4;
