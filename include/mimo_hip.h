@@ -345,6 +345,33 @@ int mimo_evidential_uncertainties(const float* logits, int32_t n, int64_t hw, fl
 int mimo_evidential_loss_gradient(const float* logits, const float* label, const float* mask, int32_t n, int64_t hw,
                                   float scale, float* dlogits, mimo_stream stream);
 
+/* ---- evidential model, training / validation step: replaces, after the backbone, the tail of
+ * EvidentialUnetModel.training_step / validation_step (mimo/models/evidential_unet.py:98-146): the head, EvidentialLoss.forward
+ * and `loss.mean()`, `aleatoric_var ** 0.5` / `epistemic_var ** 0.5` (mimo/losses.py:258-271), `y_pred - label`, the two
+ * `clip(0, 5).mean()` and compute_regression_metrics (mimo/metrics.py:22-34) — and the backward of that mean.
+ * mimo_evidential_step: one pass over logits [N,4,HW], label [N,HW], mask [N,HW] or NULL.  Per pixel, with the head arithmetic
+ *   of mimo_evidential_forward (alpha = softplus(l2) + 1 rounded, then alpha - 1): aleatoric_std = sqrt(beta / (alpha - 1)),
+ *   epistemic_std = sqrt(beta / (v (alpha - 1))) (NULL: not wanted, not computed), err = l0 - label, each [N,HW]; the
+ *   predictions are plane 0 of the logits and are not written.  Non-finite values are written as they come.
+ *   scalars: device [8] = mean of the loss map (x mask) over all N HW pixels, masked ones counted (`loss.mean()`), mae, mse,
+ *            rmse, r2 (= 1 - SSE / (sum y^2 - (sum y)^2 / n), in double; none of the four looks at the mask),
+ *            mean clip(aleatoric_std, 0, 5), mean clip(epistemic_std, 0, 5) (0 when not wanted), element count.  An infinite
+ *            std clips to 5; what a NaN does to a scalar is unspecified.
+ *   scratch: device doubles [scratch_blocks * 8], scratch_blocks >= 1 (2048 is enough for any size): one partial row per
+ *            workgroup, summed in a fixed order by a second one-workgroup kernel — no atomics, the same bits every run.
+ *   20 B read (24 with a mask) + 8 B written (12 with epistemic_std) per pixel; 16-byte accesses when hw % 4 == 0 and
+ *   every pointer is 16-byte aligned.  n, hw, scratch_blocks >= 1.
+ * mimo_evidential_loss_gradient_dev: dlogits [N,4,HW] = d(scale * upstream[0] * sum over pixels of loss_map) / d logits,
+ *   upstream: device [1] — the gradient arriving at the mean (1, or a loss scaler's factor), read by the kernel: no host
+ *   synchronisation and no [N,HW] tensor filled with it.  Each thread forms s = scale * upstream[0] in one fp32
+ *   multiplication: bit-identical to mimo_evidential_loss_gradient(scale = that product), the same device function.
+ * Both are asynchronous on the stream. */
+int mimo_evidential_step(const float* logits, const float* label, const float* mask, int32_t n, int64_t hw,
+                         float* aleatoric_std, float* epistemic_std, float* err, float* scalars, double* scratch,
+                         int32_t scratch_blocks, mimo_stream stream);
+int mimo_evidential_loss_gradient_dev(const float* logits, const float* label, const float* mask, int32_t n, int64_t hw,
+                                      float scale, const float* upstream, float* dlogits, mimo_stream stream);
+
 /* ---- validation epilogue: replaces, after the forward, the tail of MimoUnetModel.validation_step
  * (mimo_unet.py:153-183): compute_uncertainties, sqrt of the variances, calculate_dist_param(log=True) +
  * the combined NLL on the ensemble mean, the error map, compute_regression_metrics (metrics.py:22-34:

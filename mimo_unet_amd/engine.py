@@ -408,6 +408,83 @@ def evidential_loss_gradient(logits: torch.Tensor, label: torch.Tensor, mask: Op
     return out
 
 
+EVIDENTIAL_STEP_SCALARS = ("loss", "mae", "mse", "rmse", "r2", "aleatoric_std_mean", "epistemic_std_mean", "count")
+_STEP_SCRATCH_BLOCKS = 2048  # the largest grid of mimo_evidential_step: one partial row of 8 doubles per workgroup
+_step_scratch: Dict[Tuple[int, int], torch.Tensor] = {}
+
+
+def _evidential_step_scratch(device: torch.device, stream: int) -> torch.Tensor:
+    """The partial rows of mimo_evidential_step, kept per (device, stream): calls on one stream are ordered, so they can
+    share the rows; the allocator stays out of the step."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), stream)
+    buf = _step_scratch.get(key)
+    if buf is None:
+        buf = _step_scratch[key] = torch.empty(_STEP_SCRATCH_BLOCKS * 8, device=device, dtype=torch.float64)
+    return buf
+
+
+class _EvidentialStep(torch.autograd.Function):
+    """The tail of EvidentialUnetModel.training_step / validation_step after the backbone in one pass over the logits
+    (include/mimo_hip.h mimo_evidential_step): the mean of the masked loss map (differentiable), the standard-deviation and
+    error maps and the logged scalars.  The backward is one kernel (mimo_evidential_loss_gradient_dev) that reads the
+    incoming gradient from the device: no `[B,H,W]` gradient tensor and no `.item()`, also under a GradScaler."""
+
+    @staticmethod
+    def forward(ctx, logits, label, mask, want_epistemic):
+        lib = L.load()
+        logits = logits.contiguous().float()
+        b, four, h, w = logits.shape
+        assert four == 4 and logits.is_cuda
+        dev = logits.device
+        # (the kernel takes device pointers: a label or mask left on the host is moved, as image_gradient moves them)
+        label_c = label.detach().to(dev).reshape(b, h * w).contiguous().float()
+        mask_c = None if mask is None else mask.detach().to(dev).reshape(b, h * w).contiguous().float()
+        alea, err = (torch.empty(b, 1, h, w, device=dev, dtype=torch.float32) for _ in range(2))
+        epi = torch.empty(b, 1, h, w, device=dev, dtype=torch.float32) if want_epistemic else None
+        scalars = torch.empty(8, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            stream = L.current_stream()
+            scratch = _evidential_step_scratch(dev, stream)
+            L.check(lib.mimo_evidential_step(logits.data_ptr(), label_c.data_ptr(), L.ptr(mask_c) or None, b, h * w,
+                                             alea.data_ptr(), L.ptr(epi) or None, err.data_ptr(), scalars.data_ptr(),
+                                             scratch.data_ptr(), _STEP_SCRATCH_BLOCKS, stream), "mimo_evidential_step")
+        ctx.save_for_backward(logits, label_c, mask_c)
+        ctx.set_materialize_grads(False)  # no zero-filled gradients for the maps
+        # 1 / (B H W) as torch's mean backward forms it: one fp32 division (on the host: no synchronisation)
+        ctx.scale = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(b * h * w), dtype=torch.float32))
+        loss = scalars[0]
+        ctx.mark_non_differentiable(*(t for t in (alea, epi, err, scalars) if t is not None))
+        return loss, alea, epi, err, scalars
+
+    @staticmethod
+    def backward(ctx, grad, *_unused):
+        if grad is None:
+            return None, None, None, None
+        lib = L.load()
+        logits, label_c, mask_c = ctx.saved_tensors
+        b, _, h, w = logits.shape
+        upstream = grad.detach().to(device=logits.device, dtype=torch.float32).reshape(1).contiguous()
+        out = torch.empty_like(logits)
+        with torch.cuda.device(logits.device):
+            L.check(lib.mimo_evidential_loss_gradient_dev(logits.data_ptr(), label_c.data_ptr(), L.ptr(mask_c) or None, b, h * w,
+                                                          ctx.scale, upstream.data_ptr(), out.data_ptr(), L.current_stream()),
+                    "mimo_evidential_loss_gradient_dev")
+        return out, None, None, None
+
+
+def evidential_step(logits: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor], want_epistemic: bool):
+    """Backbone logits [B,4,H,W] + label [B,1,H,W] (+ mask [B,H,W]) -> (loss, aleatoric_std, epistemic_std or None, err,
+    scalars): the 0-dim mean of the masked per-pixel evidential loss over all B*H*W pixels (`loss_fn(out, label,
+    mask=mask).mean()`, differentiable w.r.t. the logits), the maps as [B,1,H,W] and a device tensor of the eight
+    EVIDENTIAL_STEP_SCALARS — one launch sequence (mimo_evidential_step), one more in the backward
+    (mimo_evidential_loss_gradient_dev), no host synchronisation in either.  Everything but the loss carries no graph; the
+    predictions are `logits[:, 0:1]`."""
+    assert logits.is_cuda and logits.dim() == 4 and logits.shape[1] == 4, tuple(logits.shape)
+    b, _, h, w = logits.shape
+    assert label.numel() == b * h * w and (mask is None or mask.numel() == b * h * w)
+    return _EvidentialStep.apply(logits, label, mask, bool(want_epistemic))
+
+
 class _LossBufferStep(torch.autograd.Function):
     """(mean(loss * weights), weights, mean(loss)) with `loss` written into row `index` of the ring — one launch
     (include/mimo_hip.h mimo_loss_buffer_step).  d mean(loss * weights) / d loss = weights / S: the weights carry no

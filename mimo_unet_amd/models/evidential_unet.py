@@ -2,22 +2,27 @@
 (``mimo/models/evidential_unet.py:13-209``): a single-subnetwork MIMO U-Net backbone with four output
 channels turned into Normal-Inverse-Gamma parameters (softplus heads) and trained with the evidential
 loss.  The backbone is the HIP engine (`MimoUNet`, S = 1, through its generic autograd bridge); the
-softplus heads and the loss are one fused HIP kernel over the [B,4,H,W] logits (one more for their gradient)."""
+softplus heads and the loss are one fused HIP kernel over the [B,4,H,W] logits (one more for their gradient); the training
+and validation steps take everything they return and log from one pass over the logits (engine.evidential_step)."""
 from __future__ import annotations
 
+import os
 from argparse import ArgumentParser
 from typing import Any, Dict, Literal, Optional
 
 import torch
 import torch.nn.functional as F
 
-from ..engine import evidential_head_loss, evidential_loss_gradient, evidential_uncertainties
+from ..engine import evidential_head_loss, evidential_loss_gradient, evidential_step, evidential_uncertainties
 from ..lightning_compat import LightningModule
 from ..losses import EvidentialLoss
 from ..metrics import compute_regression_metrics
 from ..optim import FlatAdam
 from ..utils import count_trainable_parameters
 from .mimo_components.model import MimoUNet
+
+# 0: the tensor operations on the NIG parameters and the loss map (A/B)
+_FUSED_STEP = os.environ.get("MIMO_EVIDENTIAL_STEP_FUSED", "1") != "0"
 
 
 class EvidentialUnetModel(LightningModule):
@@ -119,9 +124,37 @@ class EvidentialUnetModel(LightningModule):
                 image, lambda logits: evidential_loss_gradient(logits[:, 0], label, mask, scale).unsqueeze(1), dimage)
         return dimage, out[:, 0]
 
+    def _fused_step(self, image: torch.Tensor, label: torch.Tensor, mask, stage: Literal["train", "val"]):
+        """The step's dict from one pass over the logits (engine.evidential_step: loss mean, standard deviations, error map
+        and the logged scalars; the reference runs ~20 full-tensor torch ops here), or None where `_forward_with_loss`
+        would leave the loss to the loss class (and on the CPU, and with MIMO_EVIDENTIAL_STEP_FUSED=0)."""
+        on_gpu = image.is_cuda and label.is_cuda and (mask is None or mask.is_cuda)  # the whole batch, not the image alone
+        if not (_FUSED_STEP and on_gpu and image.dim() == 4):
+            return None
+        b, _, h, w = image.shape
+        if tuple(label.shape) != (b, 1, h, w) or not (mask is None or tuple(mask.shape) == (b, h, w)):
+            return None
+        val = stage == "val"
+        logits = self._logits(image)
+        loss, aleatoric_std, epistemic_std, err_map, sc = evidential_step(logits, label, mask, want_epistemic=val)
+        if val:
+            self._log("val_loss", sc[0])
+        for i, name in ((4, "r2"), (1, "mae"), (2, "mse"), (3, "rmse")):
+            self._log(f"metric_{stage}/{name}", sc[i], on_step=not val, on_epoch=True)
+        out = {"loss": loss, "label": label, "preds": logits.detach()[:, 0:1].float(), "aleatoric_std_map": aleatoric_std}
+        if val:
+            self._log("metric_val/aleatoric_std_mean", sc[5])
+            self._log("metric_val/epistemic_std_mean", sc[6])
+            out["epistemic_std_map"] = epistemic_std
+        out.update(err_map=err_map, mask=mask)
+        return out
+
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int) -> Dict[str, torch.Tensor]:
         image, label = batch["image"], batch["label"]
         mask = batch["mask"] if "mask" in batch else None
+        fused = self._fused_step(image, label, mask, "train")
+        if fused is not None:
+            return fused
         out, loss = self._forward_with_loss(image, label, mask)
         y_pred = self.loss_fn.mode(out).unsqueeze(dim=1)
         aleatoric_std = self.loss_fn.aleatoric_var(out).unsqueeze(dim=1) ** 0.5
@@ -133,6 +166,9 @@ class EvidentialUnetModel(LightningModule):
         image, label = batch["image"], batch["label"]
         mask = batch["mask"] if "mask" in batch else None
         with torch.no_grad():
+            fused = self._fused_step(image, label, mask, "val")
+            if fused is not None:
+                return fused
             out, loss = self._forward_with_loss(image, label, mask)
             y_pred = self.loss_fn.mode(out).unsqueeze(dim=1)
             aleatoric_std = self.loss_fn.aleatoric_var(out).unsqueeze(dim=1) ** 0.5
