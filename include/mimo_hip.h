@@ -456,6 +456,100 @@ int mimo_op_maxpool2x2(const float* x, float* y, int32_t n, int32_t h, int32_t w
 int mimo_op_upsample_cat(const float* skip, const float* low, float* out, int32_t n, int32_t hs, int32_t ws,
                          int32_t cs_p, int32_t hl, int32_t wl, int32_t cl_p, mimo_stream stream);
 
+/* ---- single-operator entry points of the backward element-wise kernels (elementwise.hip) -------
+ * NHWC fp32 tensors whose channel count c_p is a multiple of 8; "ld*" = elements per pixel of the buffer a pointer indexes
+ * (a tensor may be a channel slice of a wider buffer; pitches and channel offsets are multiples of 4).  "dxpad" is a
+ * gradient on the reflect-padded domain [n, h + 2, w + 2, ldp], as the data-gradient convolution leaves it; fold = the
+ * transpose of the 1-pixel reflect padding (utils.py / components.py:17 padding_mode="reflect").
+ * precision: MIMO_PREC_FP32 runs the fp32-storage kernels; MIMO_PREC_BF16_MIXED / MIMO_PREC_FP16_MIXED round every
+ * activation-like buffer (whole buffers, at their pitch) into bf16 / fp16 copies, run the 16-bit storage kernels on those and
+ * widen the outputs again; every other value is treated as fp32 storage.
+ * MIMO_ERR_INVALID, with nothing launched: h or w < 2 (no reflect fold), c_p % 8 != 0, a pitch that does not hold its slice,
+ * and what each function lists. */
+/* da[n,h,w] (ldda) (=|+=) fold(dxpad)[..., choff : choff + c_p] */
+int mimo_op_fold_slice(const float* dxpad, int32_t ldp, int32_t choff, float* da, int32_t ldda, int32_t n, int32_t h,
+                       int32_t w, int32_t c_p, int32_t accumulate, int32_t precision, mimo_stream stream);
+/* MaxPool2d(2) backward (components.py:48): da[n,h,w] (ldda) (=|+=) the gradient fold(dxpad [n, h/2 + 2, w/2 + 2])[...,
+ * choff : choff + c_p] routed to the first maximum, in scan order (0,0),(0,1),(1,0),(1,1), of each 2x2 window of a (lda);
+ * the last row / column of an odd size receives none.  skip != NULL: + fold(skip [n, h + 2, w + 2] (ldsk))[..., 0 : c_p].
+ * The pooled tensor is the folded one: h / 2 and w / 2 >= 2. */
+int mimo_op_pool_backward(const float* dxpad, int32_t ldp, int32_t choff, const float* a, int32_t lda, const float* skip,
+                          int32_t ldsk, float* da, int32_t ldda, int32_t n, int32_t h, int32_t w, int32_t c_p,
+                          int32_t accumulate, int32_t precision, mimo_stream stream);
+/* Upsample(x2, bilinear, align_corners=True) + F.pad backward (components.py:78,110-117): da[n,hl,wl] (ldda) (=|+=) the
+ * transposed interpolation of fold(dxpad [n, hs + 2, ws + 2])[..., choff : choff + c_p].  hs / 2 == hl and ws / 2 == wl. */
+int mimo_op_up_backward(const float* dxpad, int32_t ldp, int32_t choff, float* da, int32_t ldda, int32_t n, int32_t hs,
+                        int32_t ws, int32_t hl, int32_t wl, int32_t c_p, int32_t accumulate, int32_t precision,
+                        mimo_stream stream);
+
+/* BatchNorm2d + ReLU (+ Dropout2d) backward (components.py:24-29) of one layer, the chain the plan runs: the reduction pass,
+ * the column sums, the apply pass and, in eval mode, the column sums of dz.
+ *   dy = g * mask[n][c] * [z * scale + shift > 0];   s1 = sum dy;   s2 = sum dy * (z - mean) * invstd
+ *   training: dz = scale * (dy - s1 / count - xhat * s2 / count), dgamma = s2, dbeta = s1, dbias = 0 (exactly)
+ *   eval:     dz = scale * dy, dbias = sum dz
+ * g, the gradient arriving at the activation, comes from `kind`:
+ *   0  da [n,h,w] (ldda)
+ *   1  fold(dxpad [n, h + 2, w + 2] (ldp))[..., 0 : c_p]   (choff must be 0)
+ *   2  mimo_op_pool_backward's result for dxpad / choff / skip / ldsk (+ skoff) with the window's activations re-formed as
+ *      relu(fma(z, scale, shift)) * mask — never written
+ *   3  mimo_op_head_backward's da for head_* / loss_kind / eps_* with in_scale / in_shift = scale / shift — never written;
+ *      head_dw / head_db receive the head's parameter gradients
+ * Kinds 2 and 3 exist for fp32 storage and (3) head_co == 2 only: MIMO_ERR_INVALID otherwise. */
+typedef struct mimo_op_bn_relu_backward_args {
+  int32_t kind, n, h, w, c, c_p; /* c logical channels of c_p */
+  int32_t training, split_out, precision;
+  const float* da; /* kind 0 */
+  int32_t ldda;
+  const float* dxpad; /* kinds 1, 2 */
+  int32_t ldp, choff;
+  const float* skip; /* kind 2, or NULL */
+  int32_t ldsk, skoff;
+  /* kind 3: w [2][c]; logits out, dout [n][subnetworks][2][h*w]; dloss [subnetworks]; label, mask [n][h*w] (mask or
+   * NULL); perm [subnetworks][n] or NULL — the arguments of mimo_loss_forward / mimo_backward */
+  const float *head_w, *head_out, *head_dout, *head_dloss, *head_label, *head_mask;
+  const int64_t* head_perm;
+  int32_t head_co, head_subnetworks, head_s, loss_kind;
+  float eps_min, eps_max;
+  const float* z; /* the convolution output [n,h,w] (ldz) */
+  int32_t ldz;
+  const float *scale, *shift, *mean, *invstd; /* [c_p] */
+  const float* mask;                          /* Dropout2d multipliers [n][c], or NULL */
+  /* outputs (device).  dz [n,h,w,c_p]; split_out = 1 (fp32 storage): the same bytes hold, per pixel and 32-channel chunk,
+   * [hi: bf16 x 32 | lo: bf16 x 32] with dz ~= hi + lo (a last chunk of r channels: [hi r | lo r]) */
+  float* dz;
+  float *dgamma, *dbeta, *dbias; /* [c]; dbias is required in eval mode */
+  float *c1, *c2;                /* [c_p]: s1 / count, s2 / count (zeros in eval mode) */
+  float *head_dw, *head_db;      /* kind 3: [2][c], [2] */
+  float* absmax;                 /* NULL, or absmax_capacity >= 4096 floats: per-workgroup max |dz| */
+  int32_t absmax_capacity;
+  int32_t* absmax_n; /* host: slots written */
+  int32_t* status;   /* host, or NULL: numerics status word (mimo_plan_status bits) */
+} mimo_op_bn_relu_backward_args;
+int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* args, mimo_stream stream);
+
+/* 1x1 head + NLL backward (components.py:126, losses.py:151-160) of subnetwork s:
+ *   dlogit = dout + dloss[s] / count * mask * dNLL/dlogit   (count = n * (co / 2) * hw; the clamp of exp(log-scale) to
+ *            [eps_min, eps_max] acts on the value only, d/dlog keeps the unclamped exp)
+ *   da [n, hw, c_p] = W^T dlogit (padding channels zero), dw [co][c] = sum dlogit x a, db [co] = sum dlogit
+ * a [n, hw] (lda): the head's input; in_scale / in_shift != NULL: the pre-activation tensor, relu(fma(a, scale, shift)) is
+ * applied on the way in.  out, dout [n][subnetworks][co][hw]; label [n][co/2][hw]; mask [n][hw] or NULL; perm
+ * [subnetworks][n] or NULL.  dout and / or dloss (with out and label).  c_p <= 256, co even and <= 8. */
+typedef struct mimo_op_head_backward_args {
+  const float* a;
+  int32_t lda;
+  const float* w; /* [co][c] */
+  int32_t c, c_p, co, n, subnetworks, s;
+  int64_t hw;
+  const float *out, *dout, *dloss, *label, *mask;
+  const int64_t* perm;
+  int32_t loss_kind;
+  float eps_min, eps_max;
+  const float *in_scale, *in_shift;
+  int32_t precision;
+  float *da, *dw, *db;
+} mimo_op_head_backward_args;
+int mimo_op_head_backward(const mimo_op_head_backward_args* args, mimo_stream stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

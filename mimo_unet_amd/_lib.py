@@ -44,6 +44,40 @@ class ForwardArgs(C.Structure):
     ]
 
 
+class BnReluBackwardArgs(C.Structure):
+    """mimo_op_bn_relu_backward_args (include/mimo_hip.h)"""
+    _fields_ = [
+        ("kind", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("c_p", C.c_int32),
+        ("training", C.c_int32), ("split_out", C.c_int32), ("precision", C.c_int32),
+        ("da", C.c_void_p), ("ldda", C.c_int32),
+        ("dxpad", C.c_void_p), ("ldp", C.c_int32), ("choff", C.c_int32),
+        ("skip", C.c_void_p), ("ldsk", C.c_int32), ("skoff", C.c_int32),
+        ("head_w", C.c_void_p), ("head_out", C.c_void_p), ("head_dout", C.c_void_p), ("head_dloss", C.c_void_p),
+        ("head_label", C.c_void_p), ("head_mask", C.c_void_p), ("head_perm", C.c_void_p),
+        ("head_co", C.c_int32), ("head_subnetworks", C.c_int32), ("head_s", C.c_int32), ("loss_kind", C.c_int32),
+        ("eps_min", C.c_float), ("eps_max", C.c_float),
+        ("z", C.c_void_p), ("ldz", C.c_int32),
+        ("scale", C.c_void_p), ("shift", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p), ("mask", C.c_void_p),
+        ("dz", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dbias", C.c_void_p),
+        ("c1", C.c_void_p), ("c2", C.c_void_p), ("head_dw", C.c_void_p), ("head_db", C.c_void_p),
+        ("absmax", C.c_void_p), ("absmax_capacity", C.c_int32), ("absmax_n", C.POINTER(C.c_int32)),
+        ("status", C.POINTER(C.c_int32)),
+    ]
+
+
+class HeadBackwardArgs(C.Structure):
+    """mimo_op_head_backward_args (include/mimo_hip.h)"""
+    _fields_ = [
+        ("a", C.c_void_p), ("lda", C.c_int32), ("w", C.c_void_p),
+        ("c", C.c_int32), ("c_p", C.c_int32), ("co", C.c_int32), ("n", C.c_int32), ("subnetworks", C.c_int32), ("s", C.c_int32),
+        ("hw", C.c_int64),
+        ("out", C.c_void_p), ("dout", C.c_void_p), ("dloss", C.c_void_p), ("label", C.c_void_p), ("mask", C.c_void_p),
+        ("perm", C.c_void_p), ("loss_kind", C.c_int32), ("eps_min", C.c_float), ("eps_max", C.c_float),
+        ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("precision", C.c_int32),
+        ("da", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
+    ]
+
+
 LOSS_KINDS = {"laplace_nll": 0, "gaussian_nll": 1}
 # "bf16-mixed" / "16-mixed": Lightning's names for bf16 / fp16 autocast training — here 16-bit storage + operands
 PRECISIONS = {"fp32": 0, "split16": 1, "bf16": 2, "bf16-mixed": 3, "16-mixed": 4}
@@ -104,6 +138,11 @@ _SIGNATURES = {
     "mimo_op_conv3x3_wgrad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mimo_op_maxpool2x2": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     "mimo_op_upsample_cat": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_op_fold_slice": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_op_pool_backward": (C.c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_op_up_backward": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_op_bn_relu_backward": (C.c_int, [C.POINTER(BnReluBackwardArgs), _P]),
+    "mimo_op_head_backward": (C.c_int, [C.POINTER(HeadBackwardArgs), _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -374,3 +374,279 @@ int mimo_op_upsample_cat(const float* skip, const float* low, float* out, int32_
 }
 
 }  // extern "C"
+
+// ---- backward element-wise operators (tests/test_ew_bwd_kernels_gpu.py) --------------------------------------------------
+// fp32 tensors at the interface; in the 16-bit storage modes whole buffers (every pixel at its full pitch) are rounded into
+// 16-bit copies, the storage-mode kernels run on those, and the outputs are widened again (exact).
+
+namespace {
+
+bool bad_dims(const char* who, int n, int h, int w, int c_p) {
+  if (n < 1 || h < 2 || w < 2 || c_p < 8 || c_p % 8 != 0 || (int64_t)n * (h + 2) * (w + 2) >= (int64_t)1 << 31) {
+    set_error("%s: n %d, %d x %d, c_p %d unsupported (n >= 1, h and w >= 2 for the reflect fold, c_p a multiple of 8)", who, n, h, w, c_p);
+    return true;
+  }
+  return false;
+}
+// a channel slice [off, off + c_p) of a buffer with `ld` elements per pixel, float4-addressable
+bool bad_slice(const char* who, const char* what, int ld, int off, int c_p) {
+  if (off < 0 || off % 4 != 0 || ld % 4 != 0 || ld < off + c_p) {
+    set_error("%s: %s pitch %d / channel offset %d do not hold %d channels", who, what, ld, off, c_p);
+    return true;
+  }
+  return false;
+}
+int store_type(int precision) { return precision == MIMO_PREC_BF16_MIXED ? ST_BF16 : precision == MIMO_PREC_FP16_MIXED ? ST_F16 : ST_F32; }
+
+// `count` fp32 elements of `src` as the storage type of `precision`: src itself for fp32 storage, a rounded 16-bit copy otherwise
+struct Stored {
+  const void* in = nullptr;  // what the kernel reads
+  void* out = nullptr;       // what the kernel writes (out16 or dst)
+  uint16_t* b16 = nullptr;
+  float* dst = nullptr;
+  int64_t count = 0;
+};
+int stage_in(Temp& t, const float* src, int64_t count, int precision, hipStream_t st, Stored* s) {
+  s->count = count;
+  s->in = src;
+  if (!src || !is_mixed(precision)) return MIMO_OK;
+  s->b16 = t.get<uint16_t>(count);
+  if (!s->b16) {
+    set_error("mimo_op: allocation failed");
+    return MIMO_ERR_HIP;
+  }
+  MIMO_TRY(to16(src, s->b16, count, precision == MIMO_PREC_FP16_MIXED, st));
+  s->in = s->b16;
+  return MIMO_OK;
+}
+// an output (read as well when the operator accumulates into it)
+int stage_out(Temp& t, float* dst, int64_t count, int precision, hipStream_t st, Stored* s) {
+  MIMO_TRY(stage_in(t, dst, count, precision, st, s));
+  s->dst = dst;
+  s->out = s->b16 ? (void*)s->b16 : (void*)dst;
+  return MIMO_OK;
+}
+int stage_back(const Stored& s, int precision, hipStream_t st) {
+  if (s.b16) MIMO_TRY(from16(s.b16, s.dst, s.count, precision == MIMO_PREC_FP16_MIXED, st));
+  return MIMO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mimo_op_fold_slice(const float* dxpad, int32_t ldp, int32_t choff, float* da, int32_t ldda, int32_t n, int32_t h,
+                       int32_t w, int32_t c_p, int32_t accumulate, int32_t precision, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (bad_dims("mimo_op_fold_slice", n, h, w, c_p) || bad_slice("mimo_op_fold_slice", "dxpad", ldp, choff, c_p) ||
+      bad_slice("mimo_op_fold_slice", "da", ldda, 0, c_p))
+    return MIMO_ERR_INVALID;
+  Temp t;
+  Stored src, dst;
+  MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (h + 2) * (w + 2) * ldp, precision, st, &src));
+  MIMO_TRY(stage_out(t, da, (int64_t)n * h * w * ldda, precision, st, &dst));
+  MIMO_TRY(fold_slice_launch(src.in, store_type(precision), ldp, choff, dst.out, ldda, n, h, w, c_p, accumulate, st));
+  MIMO_TRY(stage_back(dst, precision, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_pool_backward(const float* dxpad, int32_t ldp, int32_t choff, const float* a, int32_t lda, const float* skip,
+                          int32_t ldsk, float* da, int32_t ldda, int32_t n, int32_t h, int32_t w, int32_t c_p,
+                          int32_t accumulate, int32_t precision, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_pool_backward";
+  // (the folded tensor is the pooled one: h / 2 x w / 2 needs two rows and columns)
+  if (bad_dims(who, n, h / 2, w / 2, c_p) || bad_dims(who, n, h, w, c_p) || bad_slice(who, "dxpad", ldp, choff, c_p) ||
+      bad_slice(who, "a", lda, 0, c_p) || bad_slice(who, "da", ldda, 0, c_p) || (skip && bad_slice(who, "skip", ldsk, 0, c_p)))
+    return MIMO_ERR_INVALID;
+  Temp t;
+  Stored src, act, sk, dst;
+  MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (h / 2 + 2) * (w / 2 + 2) * ldp, precision, st, &src));
+  MIMO_TRY(stage_in(t, a, (int64_t)n * h * w * lda, precision, st, &act));
+  MIMO_TRY(stage_in(t, skip, (int64_t)n * (h + 2) * (w + 2) * ldsk, precision, st, &sk));
+  MIMO_TRY(stage_out(t, da, (int64_t)n * h * w * ldda, precision, st, &dst));
+  MIMO_TRY(pool_bwd_launch(src.in, store_type(precision), ldp, choff, act.in, lda, dst.out, ldda, n, h, w, c_p, accumulate, st,
+                           sk.in, ldsk));
+  MIMO_TRY(stage_back(dst, precision, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_up_backward(const float* dxpad, int32_t ldp, int32_t choff, float* da, int32_t ldda, int32_t n, int32_t hs,
+                        int32_t ws, int32_t hl, int32_t wl, int32_t c_p, int32_t accumulate, int32_t precision,
+                        mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_up_backward";
+  if (bad_dims(who, n, hs, ws, c_p) || bad_slice(who, "dxpad", ldp, choff, c_p) || bad_slice(who, "da", ldda, 0, c_p))
+    return MIMO_ERR_INVALID;
+  if (hl < 1 || wl < 1 || hs / 2 != hl || ws / 2 != wl) {
+    set_error("%s: %d x %d is not the x2 up-sampling of %d x %d (floor(hs / 2) == hl)", who, hs, ws, hl, wl);
+    return MIMO_ERR_INVALID;
+  }
+  Temp t;
+  Stored src, dst;
+  MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (hs + 2) * (ws + 2) * ldp, precision, st, &src));
+  MIMO_TRY(stage_out(t, da, (int64_t)n * hl * wl * ldda, precision, st, &dst));
+  MIMO_TRY(up_bwd_launch(src.in, store_type(precision), ldp, choff, dst.out, ldda, n, hs, ws, hl, wl, c_p, accumulate, st));
+  MIMO_TRY(stage_back(dst, precision, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* p, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_bn_relu_backward";
+  if (!p) {
+    set_error("%s: null arguments", who);
+    return MIMO_ERR_INVALID;
+  }
+  const mimo_op_bn_relu_backward_args& a = *p;
+  const int prec = a.precision, Cp = a.c_p, N = a.n, H = a.h, W = a.w;
+  const bool fused = a.kind == GS_POOL || a.kind == GS_HEAD;
+  if (bad_dims(who, N, H, W, Cp) || bad_slice(who, "z", a.ldz, 0, Cp)) return MIMO_ERR_INVALID;
+  if (a.kind < GS_PLAIN || a.kind > GS_HEAD || a.c < 1 || a.c > Cp || !a.z || !a.scale || !a.shift || !a.mean || !a.invstd ||
+      !a.dz || !a.c1 || !a.c2 || a.absmax_capacity < 0 || (a.absmax && (!a.absmax_n || a.absmax_capacity < kDzMaxSlots))) {
+    set_error("%s: kind %d, c %d of %d, a missing tensor, or fewer than %d max |dz| slots", who, a.kind, a.c, Cp, kDzMaxSlots);
+    return MIMO_ERR_INVALID;
+  }
+  if (fused && is_mixed(prec)) {
+    set_error("%s: the pooled and head gradient sources exist for fp32 storage only", who);
+    return MIMO_ERR_INVALID;
+  }
+  if (a.split_out && is_mixed(prec)) {
+    set_error("%s: pair-split dz exists for fp32 storage only", who);
+    return MIMO_ERR_INVALID;
+  }
+  if (!a.training && !a.dbias) {
+    set_error("%s: eval mode returns the bias gradient", who);
+    return MIMO_ERR_INVALID;
+  }
+  GradSrc src;
+  src.kind = a.kind;
+  Temp t;
+  Stored gsrc, sk, zs, dzs;
+  float* head_partial = nullptr;
+  if (a.kind == GS_PLAIN) {
+    if (!a.da || bad_slice(who, "da", a.ldda, 0, Cp)) return MIMO_ERR_INVALID;
+    MIMO_TRY(stage_in(t, a.da, (int64_t)N * H * W * a.ldda, prec, st, &gsrc));
+    src.da = gsrc.in;
+    src.ldda = a.ldda;
+  } else if (a.kind == GS_FOLD) {  // (the folded source reads channels [0, c_p) of its buffer)
+    if (!a.dxpad || a.choff != 0 || bad_slice(who, "dxpad", a.ldp, 0, Cp)) {
+      set_error("%s: the folded source needs dxpad with choff 0 and a pitch of at least c_p", who);
+      return MIMO_ERR_INVALID;
+    }
+    MIMO_TRY(stage_in(t, a.dxpad, (int64_t)N * (H + 2) * (W + 2) * a.ldp, prec, st, &gsrc));
+    src.dxpad = gsrc.in;
+    src.ldp = a.ldp;
+  } else if (a.kind == GS_POOL) {
+    if (!a.dxpad || bad_dims(who, N, H / 2, W / 2, Cp) || bad_slice(who, "dxpad", a.ldp, a.choff, Cp) ||
+        (a.skip && bad_slice(who, "skip", a.ldsk, a.skoff, Cp)))
+      return MIMO_ERR_INVALID;
+    src.dxpad = a.dxpad;
+    src.ldp = a.ldp;
+    src.choff = a.choff;
+    src.skip = a.skip;
+    src.ldsk = a.ldsk;
+    src.skoff = a.skoff;
+  } else {
+    if (a.head_co != 2 || !a.head_w || a.head_subnetworks < 1 || a.head_s < 0 || a.head_s >= a.head_subnetworks ||
+        (!a.head_dout && !a.head_dloss) || (a.head_dloss && (!a.head_out || !a.head_label)) || !a.head_dw || !a.head_db ||
+        (a.loss_kind != MIMO_LOSS_LAPLACE_NLL && a.loss_kind != MIMO_LOSS_GAUSSIAN_NLL)) {
+      set_error("%s: the head source needs 2 logits per pixel, its weights, dout and / or dloss with logits and labels, dw and db", who);
+      return MIMO_ERR_INVALID;
+    }
+    head_partial = t.get<float>((size_t)kBnReduceMaxBlocks * (2 * Cp + 2));
+    if (!head_partial) {
+      set_error("%s: allocation failed", who);
+      return MIMO_ERR_HIP;
+    }
+    HeadGrad& hg = src.head;
+    hg.w = a.head_w;
+    hg.C = a.c;
+    hg.Co = 2;
+    hg.N = N;
+    hg.S = a.head_subnetworks;
+    hg.s = a.head_s;
+    hg.HW = H * W;
+    hg.out = a.head_out;
+    hg.dout = a.head_dout;
+    hg.dloss = a.head_dloss;
+    hg.label = a.head_label;
+    hg.mask = a.head_mask;
+    hg.perm = a.head_perm;
+    hg.kind = a.loss_kind;
+    hg.eps_min = a.eps_min;
+    hg.eps_max = a.eps_max;
+    hg.inv_count = 1.f / (float)((double)N * H * W);  // head_bwd_launch's: N * (Co / 2) * HW
+    hg.partial = head_partial;
+  }
+  MIMO_TRY(stage_in(t, a.z, (int64_t)N * H * W * a.ldz, prec, st, &zs));
+  MIMO_TRY(stage_out(t, a.dz, (int64_t)N * H * W * Cp, prec, st, &dzs));
+  // (partial rows: one per workgroup of a BatchNorm-backward grid, <= kBnReduceMaxBlocks = the column-sum kernels' kColsumMaxRows)
+  static_assert(kBnReduceMaxBlocks <= kColsumMaxRows, "partial-row capacity");
+  float* partial = t.get<float>((size_t)kBnReduceMaxBlocks * 2 * Cp);
+  int* status = t.get<int>(1);
+  if (!partial || !status) {
+    set_error("%s: allocation failed", who);
+    return MIMO_ERR_HIP;
+  }
+  const int dt = store_type(prec);
+  int rows = 0;
+  MIMO_TRY(bnrelu_bwd_reduce_launch(src, dt, zs.in, dt, a.ldz, a.scale, a.shift, a.mean, a.invstd, a.mask, a.c, Cp, N, H, W, partial,
+                                    &rows, st));
+  MIMO_TRY(bn_bwd_stats_launch(partial, rows, a.c, Cp, (int64_t)N * H * W, a.training ? 1 : 0, a.c1, a.c2, a.dgamma, a.dbeta,
+                               a.training ? a.dbias : nullptr, status, st));
+  if (a.kind == GS_HEAD) MIMO_TRY(head_bwd_stats_launch(head_partial, rows, a.c, Cp, 2, a.head_dw, a.head_db, st));
+  int absmax_n = 0;
+  MIMO_TRY(bn_bwd_apply_launch(src, dt, zs.in, dt, a.ldz, a.scale, a.shift, a.mean, a.invstd, a.mask, a.c, a.c1, a.c2, Cp, N, H, W,
+                               dzs.out, a.split_out ? 1 : 0, a.training ? nullptr : partial, &rows, st, a.absmax, &absmax_n));
+  if (!a.training) MIMO_TRY(colsum_vec_launch(partial, rows, Cp, a.c, a.dbias, st));
+  MIMO_TRY(stage_back(dzs, prec, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  if (a.absmax_n) *a.absmax_n = absmax_n;
+  if (a.status) MIMO_HIP_CHECK(hipMemcpy(a.status, status, sizeof(int), hipMemcpyDeviceToHost));
+  return MIMO_OK;
+}
+
+int mimo_op_head_backward(const mimo_op_head_backward_args* p, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_head_backward";
+  if (!p) {
+    set_error("%s: null arguments", who);
+    return MIMO_ERR_INVALID;
+  }
+  const mimo_op_head_backward_args& a = *p;
+  const int Cp = a.c_p;
+  // (one workgroup column: the head's channel quads fit one workgroup, filter_base_count <= 256)
+  if (a.n < 1 || a.hw < 1 || (int64_t)a.n * a.hw >= (int64_t)1 << 31 || Cp < 8 || Cp % 8 != 0 || Cp > 256 || a.c < 1 || a.c > Cp ||
+      bad_slice(who, "a", a.lda, 0, Cp) || a.co < 2 || a.co > kMaxHeadOut || (a.co & 1) || a.subnetworks < 1 || a.s < 0 ||
+      a.s >= a.subnetworks || !a.a || !a.w || !a.da || !a.dw || !a.db || (!a.dout && !a.dloss) ||
+      (a.dloss && (!a.out || !a.label)) || (!a.in_scale != !a.in_shift) ||
+      (a.loss_kind != MIMO_LOSS_LAPLACE_NLL && a.loss_kind != MIMO_LOSS_GAUSSIAN_NLL)) {
+    set_error("%s: unsupported geometry or a missing tensor (c_p a multiple of 8 up to 256, an even co <= %d, dout and / or dloss "
+              "with logits and labels)", who, kMaxHeadOut);
+    return MIMO_ERR_INVALID;
+  }
+  Temp t;
+  Stored act, dst;
+  MIMO_TRY(stage_in(t, a.a, (int64_t)a.n * a.hw * a.lda, a.precision, st, &act));
+  MIMO_TRY(stage_out(t, a.da, (int64_t)a.n * a.hw * Cp, a.precision, st, &dst));
+  static_assert(kEwMaxBlocks <= kColsumMaxRows, "partial-row capacity");
+  float* partial = t.get<float>((size_t)kEwMaxBlocks * (a.co * Cp + a.co));  // one row per workgroup, head_bwd_launch's grid cap
+  if (!partial) {
+    set_error("%s: allocation failed", who);
+    return MIMO_ERR_HIP;
+  }
+  int rows = 0;
+  MIMO_TRY(head_bwd_launch(act.in, store_type(a.precision), a.lda, a.w, a.c, Cp, a.co, a.n, a.subnetworks, a.s, (int)a.hw, a.out, a.dout,
+                           a.dloss, a.label, a.mask, a.perm, a.loss_kind, a.eps_min, a.eps_max, dst.out, partial, &rows, st,
+                           a.in_scale, a.in_shift));
+  MIMO_TRY(head_bwd_stats_launch(partial, rows, a.c, Cp, a.co, a.dw, a.db, st));
+  MIMO_TRY(stage_back(dst, a.precision, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+}  // extern "C"
