@@ -311,6 +311,26 @@ int mimo_adam_step_amp(float* params, const float* grads, float* exp_avg, float*
                        float beta1, float beta2, float eps, float weight_decay, float* step_dev, float grad_scale,
                        const float* amp_scale, const float* found_inf, mimo_stream stream);
 
+/* The same step with gradient clipping: torch.nn.utils.clip_grad_norm_ (clip_mode MIMO_CLIP_NORM, the global L2 norm) or
+ * clip_grad_value_ (MIMO_CLIP_VALUE) followed by the Adam update above, without a host synchronisation.  The arguments of
+ * mimo_adam_step_amp (step_dev always on the device) plus clip > 0, clip_out (2 device floats) and scratch (device,
+ * mimo_grad_clip_scratch_bytes() bytes, 8-byte aligned, owned by the caller, reusable by ordered calls on one stream).
+ * With ge = g * s, s = grad_scale (/ *amp_scale when given), formed in fp32:
+ *   norm : norm = sqrt(sum ge^2) (squares in fp32, sums in double, a fixed order: two runs give the same bits),
+ *          coef = min(1, clip / (norm + 1e-6)); weight decay and the moments see (g * s) * coef.
+ *   value: weight decay and the moments see clamp(g * s, -clip, clip); a NaN stays a NaN.
+ * clip_out[0] = the norm before clipping (value mode: 0), clip_out[1] = the coefficient applied (value mode: 1; 0 when the
+ * norm is not finite), both written whether or not the step is applied.  A norm that is not finite skips the whole step —
+ * parameters, moments and step_dev stay untouched, exactly as with *found_inf != 0 (torch would multiply every gradient
+ * by NaN instead; clip_out[0] tells what happened).  step_dev advances only when the step is applied.  With coef == 1 the
+ * update is bit-identical to mimo_adam_step_amp.  Norm mode: three launches; value mode: two (no reduction). */
+enum { MIMO_CLIP_NORM = 1, MIMO_CLIP_VALUE = 2 };
+size_t mimo_grad_clip_scratch_bytes(void);
+int mimo_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, float* step_dev, float grad_scale,
+                           const float* amp_scale, const float* found_inf, int32_t clip_mode, float clip, float* clip_out,
+                           void* scratch, mimo_stream stream);
+
 /* ---- uncertainties: replaces compute_uncertainties (utils.py:76-101) --------------------
  * p1, p2 [N,S,C,HW] contiguous -> mean, aleatoric_var, epistemic_var [N,C,HW]. */
 int mimo_uncertainties(const float* p1, const float* p2, int32_t n, int32_t s, int32_t c, int64_t hw,

@@ -119,6 +119,8 @@ _SIGNATURES = {
     "mimo_plan_profile_read_kind_tier": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "mimo_adam_step": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P]),
     "mimo_adam_step_amp": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _F, _P, _P, _P]),
+    "mimo_grad_clip_scratch_bytes": (C.c_size_t, []),
+    "mimo_adam_step_clipped": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _F, _P, _P, _I, _F, _P, _P, _P]),
     "mimo_uncertainties": (C.c_int, [_P, _P, _I, _I, _I, _L, _I, _P, _P, _P, _P]),
     "mimo_evidential_forward": (C.c_int, [_P, _P, _P, _I, _L, _P, _P, _P]),
     "mimo_evidential_backward": (C.c_int, [_P, _P, _P, _P, _P, _I, _L, _P, _P]),

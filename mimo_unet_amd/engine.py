@@ -285,6 +285,41 @@ def adam_step_amp(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tens
             "mimo_adam_step_amp")
 
 
+CLIP_MODES = {"norm": 1, "value": 2}  # include/mimo_hip.h MIMO_CLIP_NORM / MIMO_CLIP_VALUE
+_clip_scratch: Dict[Tuple[int, int], torch.Tensor] = {}
+
+
+def _grad_clip_scratch(device: torch.device, stream: int) -> torch.Tensor:
+    """The partial row and verdict of mimo_adam_step_clipped, kept per (device, stream) like _evidential_step_scratch"""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), stream)
+    buf = _clip_scratch.get(key)
+    if buf is None:
+        nbytes = int(L.load().mimo_grad_clip_scratch_bytes())
+        buf = _clip_scratch[key] = torch.empty((nbytes + 7) // 8, device=device, dtype=torch.float64)
+    return buf
+
+
+def adam_step_clipped(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *, lr: float,
+                      betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, step_dev: torch.Tensor,
+                      reduce_scale: float = 1.0, amp_scale: Optional[torch.Tensor] = None,
+                      found_inf: Optional[torch.Tensor] = None, clip_mode: str, clip: float, clip_out: torch.Tensor) -> None:
+    """adam_step_amp with the gradient clipped on the way in: by its global L2 norm (`clip_mode` "norm") or by value
+    ("value").  `clip_out` (2 device floats) receives the norm before clipping and the coefficient applied; a norm that is
+    not finite skips the step like `found_inf` does (include/mimo_hip.h mimo_adam_step_clipped).  No host synchronisation."""
+    lib = L.load()
+    for t in (step_dev, amp_scale, found_inf):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1)
+    assert clip_out.is_cuda and clip_out.dtype == torch.float32 and clip_out.numel() == 2 and clip_out.is_contiguous()
+    with torch.cuda.device(params.device):
+        stream = L.current_stream()
+        scratch = _grad_clip_scratch(params.device, stream)
+        L.check(lib.mimo_adam_step_clipped(params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                           params.numel(), lr, betas[0], betas[1], eps, weight_decay, step_dev.data_ptr(),
+                                           reduce_scale, L.ptr(amp_scale) or None, L.ptr(found_inf) or None,
+                                           CLIP_MODES[clip_mode], clip, clip_out.data_ptr(), scratch.data_ptr(), stream),
+                "mimo_adam_step_clipped")
+
+
 def fgsm_perturb(image: torch.Tensor, dimage: torch.Tensor, epsilons: Sequence[float], lo: float = 0.0,
                  hi: float = 1.0) -> torch.Tensor:
     """[K, *image.shape] = clamp(image + eps_k * sign(dimage), lo, hi) for all K perturbation sizes in one pass over image

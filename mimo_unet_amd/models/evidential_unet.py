@@ -19,13 +19,14 @@ from ..losses import EvidentialLoss
 from ..metrics import compute_regression_metrics
 from ..optim import FlatAdam
 from ..utils import count_trainable_parameters
+from .clipping import FlatAdamClipping
 from .mimo_components.model import MimoUNet
 
 # 0: the tensor operations on the NIG parameters and the loss map (A/B)
 _FUSED_STEP = os.environ.get("MIMO_EVIDENTIAL_STEP_FUSED", "1") != "0"
 
 
-class EvidentialUnetModel(LightningModule):
+class EvidentialUnetModel(FlatAdamClipping, LightningModule):
     def __init__(self, in_channels: int, out_channels: int, filter_base_count: int, center_dropout_rate: float,
                  final_dropout_rate: float, encoder_dropout_rate: float, core_dropout_rate: float,
                  decoder_dropout_rate: float, weight_decay: float, learning_rate: float, seed: int,
@@ -152,6 +153,7 @@ class EvidentialUnetModel(LightningModule):
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int) -> Dict[str, torch.Tensor]:
         image, label = batch["image"], batch["label"]
         mask = batch["mask"] if "mask" in batch else None
+        self._log_grad_norm()
         fused = self._fused_step(image, label, mask, "train")
         if fused is not None:
             return fused
@@ -199,6 +201,7 @@ class EvidentialUnetModel(LightningModule):
             optimizer = FlatAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)
         else:
             optimizer = torch.optim.Adam(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay)
+        self._flat_adam = optimizer if self.use_fused_optimizer else None  # whose clipped steps training_step logs
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=self.scheduler_step_size,
                                                     gamma=self.scheduler_gamma)
         return dict(optimizer=optimizer, lr_scheduler=scheduler, monitor="val_loss")

@@ -25,6 +25,7 @@ from ..losses import UncertaintyLoss
 from ..metrics import compute_regression_metrics
 from ..optim import FlatAdam
 from ..utils import count_trainable_parameters
+from .clipping import FlatAdamClipping
 from .mimo_components.loss_buffer import LossBuffer
 from .mimo_components.model import MimoUNet
 from .utils import (compute_uncertainties, draw_subnetwork_permutations, flatten_subnetwork_dimension,
@@ -33,7 +34,7 @@ from .utils import (compute_uncertainties, draw_subnetwork_permutations, flatten
 _ENGINE_PERM = os.environ.get("MIMO_ENGINE_PERM", "0") != "0"  # 1: training_step's permutations are drawn inside the engine
 
 
-class MimoUnetModel(LightningModule):
+class MimoUnetModel(FlatAdamClipping, LightningModule):
     def __init__(
             self,
             in_channels: int,
@@ -123,6 +124,7 @@ class MimoUnetModel(LightningModule):
 
     def training_step_with_perms(self, image, label, mask, perms) -> Dict[str, torch.Tensor]:
         out, loss = self.model.forward_with_loss(image, label, mask, perms)
+        self._log_grad_norm()
         half = self.out_channels // 2
         p1, p2 = out[:, :, :half, ...], out[:, :, half:, ...]
         fused = self.loss_buffer.step(loss)  # weights read BEFORE the add (mimo_unet.py:243-245), one kernel
@@ -218,6 +220,7 @@ class MimoUnetModel(LightningModule):
             optimizer = FlatAdam(self.model, lr=self.learning_rate, weight_decay=self.weight_decay)
         else:
             optimizer = torch.optim.Adam(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay)
+        self._flat_adam = optimizer if self.use_fused_optimizer else None  # whose clipped steps training_step logs
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=self.scheduler_step_size,
                                                     gamma=self.scheduler_gamma)
         return dict(optimizer=optimizer, lr_scheduler=scheduler, monitor="val_loss")

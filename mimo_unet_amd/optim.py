@@ -3,17 +3,31 @@ instead of one kernel chain per tensor.  Same update rule and defaults as the
 ``torch.optim.Adam`` the reference configures (mimo/models/mimo_unet.py:186-190)."""
 from __future__ import annotations
 
+import math
+
 import torch
 
-from .engine import adam_step, adam_step_amp
+from .engine import adam_step, adam_step_amp, adam_step_clipped
 
 
 class FlatAdam(torch.optim.Optimizer):
     """`torch.optim.Optimizer` (so Lightning, LR schedulers and checkpoints treat it like any
-    other) whose `step()` is a single fused kernel over `net.flat_parameters()`."""
+    other) whose `step()` is a single fused kernel over `net.flat_parameters()`.
 
-    def __init__(self, net, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    `max_grad_norm` / `clip_value` (at most one; constructor arguments and plain attributes that may be set later): the flat
+    gradient — times `reduce_scale`, divided by the loss scale — is clipped by its global L2 norm / by value inside the step
+    (`mimo_adam_step_clipped`: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ followed by Adam, no host synchronisation).
+    A norm that is not finite skips the step, as a loss scaler's `found_inf` does.  `last_grad_norm` / `last_clip_coef`:
+    device scalars of the last clipped step (the norm before clipping, the coefficient applied), None before the first;
+    views of one buffer that the next clipped step overwrites, so clone what has to outlive it.
+    Hyper-parameters, not state: they are not part of `state_dict()`."""
+
+    def __init__(self, net, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_grad_norm=None, clip_value=None):
         self.net = net
+        self.max_grad_norm, self.clip_value = max_grad_norm, clip_value
+        self._clip_setting()
+        self._clip_out = None
         super().__init__(list(net.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._step = 0
         self._m = self._v = None
@@ -45,6 +59,26 @@ class FlatAdam(torch.optim.Optimizer):
             self._step = max(self._step, int(st["step"]))
         self._ref_state = None
 
+    def _clip_setting(self):
+        """(mode, bound) of the clipping asked for, or None"""
+        if self.max_grad_norm is not None and self.clip_value is not None:
+            raise ValueError("FlatAdam: set max_grad_norm or clip_value, not both")
+        for mode, val in (("norm", self.max_grad_norm), ("value", self.clip_value)):
+            if val is not None:
+                val = float(val)
+                if math.isnan(val) or val <= 0.0:
+                    raise ValueError(f"FlatAdam: the clipping bound must be positive, got {val!r}")
+                return mode, val
+        return None
+
+    @property
+    def last_grad_norm(self):
+        return None if self._clip_out is None else self._clip_out[0]
+
+    @property
+    def last_clip_coef(self):
+        return None if self._clip_out is None else self._clip_out[1]
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -63,7 +97,18 @@ class FlatAdam(torch.optim.Optimizer):
             self._m, self._v = self._m.to(p.device), self._v.to(p.device)
         grp = self.param_groups[0]
         amp_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
-        if amp_scale is not None or found_inf is not None or self._step_dev is not None:
+        clip = self._clip_setting()
+        if clip is not None:
+            if self._step_dev is None or self._step_dev.device != p.device:
+                self._step_dev = torch.full((1,), float(self.step_count), device=p.device, dtype=torch.float32)
+            if self._clip_out is None or self._clip_out.device != p.device:
+                self._clip_out = torch.zeros(2, device=p.device, dtype=torch.float32)
+            adam_step_clipped(p, g, self._m, self._v, lr=float(grp["lr"]), betas=grp["betas"], eps=grp["eps"],
+                              weight_decay=grp["weight_decay"], step_dev=self._step_dev, reduce_scale=self.reduce_scale,
+                              amp_scale=None if amp_scale is None else amp_scale.reshape(1).float(),
+                              found_inf=None if found_inf is None else found_inf.reshape(1).float(),
+                              clip_mode=clip[0], clip=clip[1], clip_out=self._clip_out)
+        elif amp_scale is not None or found_inf is not None or self._step_dev is not None:
             if self._step_dev is None or self._step_dev.device != p.device:
                 self._step_dev = torch.full((1,), float(self.step_count), device=p.device, dtype=torch.float32)
             adam_step_amp(p, g, self._m, self._v, lr=float(grp["lr"]), betas=grp["betas"], eps=grp["eps"],
