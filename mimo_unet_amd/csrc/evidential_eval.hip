@@ -25,14 +25,59 @@
 // mimo_evidential_step: one streaming pass, 20 B read (24 with a mask) and 8 B written per pixel (12 with the epistemic
 // map), the same two access widths as mimo_evidential_uncertainties; double sums per thread, an LDS tree per workgroup, one
 // partial row per workgroup and a one-workgroup finalize kernel — no atomics.
+//
+// The head and loss themselves, with their backward (mimo_evidential_forward / mimo_evidential_backward), come first: every
+// kernel of this file runs the same device functions of evidential.h.  The sums of the step kernels: block_reduce.h.
 #include <algorithm>
 #include <cstdint>
 
+#include "block_reduce.h"
 #include "common.h"
 #include "evidential.h"
 
 namespace mimo {
 namespace {
+
+// ---------------------------------------------------------------------------------------
+// Evidential regression head + loss (mimo/models/evidential_unet.py:74-96, mimo/losses.py:202-247):
+//   (mu, v, alpha, beta) = (l0, softplus(l1), softplus(l2) + 1, softplus(l3))
+//   loss = G(alpha) / (v sqrt(beta)) * (2 beta (1 + v) + (2 alpha - 1) v (y - mu)^2) + (y - mu)^2 (2 alpha + v),
+//   G(alpha) = Gamma(alpha - 1/2) / (4 Gamma(alpha))
+// One pass for the four NIG parameters + the per-pixel loss, one pass for the gradient w.r.t. the logits (analytic:
+// dG/dalpha = G (psi(alpha - 1/2) - psi(alpha))) instead of ~40 element-wise tensor operations and their autograd
+// nodes.  G is evaluated as exp(lgamma(alpha - 1/2) - lgamma(alpha)) / 4 — the reference exponentiates the two
+// lgammas separately, which overflows fp32 (inf / inf = nan) for alpha > 35; this form stays finite there.
+// ---------------------------------------------------------------------------------------
+// (softplus_f, nig_point and the loss gradient: evidential.h)
+__global__ void evidential_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ label,
+                                      const float* __restrict__ mask, int64_t total, int64_t hw, float* __restrict__ ev,
+                                      float* __restrict__ loss) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t n = i / hw, r = i - n * hw;
+    const float* l = logits + n * 4 * hw + r;
+    const NigPoint q = nig_point(l[0], l[hw], l[2 * hw], l[3 * hw], label ? label[i] : 0.f);
+    float* e = ev + n * 4 * hw + r;
+    e[0] = q.mu;
+    e[hw] = q.v;
+    e[2 * hw] = q.alpha;
+    e[3 * hw] = q.beta;
+    if (loss && label) {
+      const float sq = q.d * q.d;
+      float v = q.c * q.T + sq * (2.f * q.alpha + q.v);
+      if (mask) v *= mask[i];
+      loss[i] = v;
+    }
+  }
+}
+
+// dlogits = d_loss * dloss/dlogits (+ d_ev * dev/dlogits): both upstream gradients optional
+__global__ void evidential_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ label,
+                                      const float* __restrict__ mask, const float* __restrict__ d_ev,
+                                      const float* __restrict__ d_loss, int64_t total, int64_t hw, float* __restrict__ dlogits) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    nig_bwd_pixel(logits, label, mask, d_ev, NigUpTensor{d_loss}, i, hw, dlogits);
+  }
+}
 
 struct NigVars {
   float aleatoric, epistemic;
@@ -141,7 +186,6 @@ __global__ __launch_bounds__(256) void evidential_step_kernel(const float* __res
                                                              const float* __restrict__ mask, int64_t total, int64_t hw,
                                                              float* __restrict__ alea_std, float* __restrict__ epi_std,
                                                              float* __restrict__ err, double* __restrict__ partial) {
-  __shared__ double red[kStepSums][256];
   const bool masked = mask != nullptr, want_epi = epi_std != nullptr;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -183,59 +227,60 @@ __global__ __launch_bounds__(256) void evidential_step_kernel(const float* __res
       step_accumulate(acc, a, y);
     }
   }
-#pragma unroll
-  for (int k = 0; k < kStepSums; ++k) red[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-#pragma unroll
-      for (int k = 0; k < kStepSums; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  const auto red = block_reduce_rows(acc);
   if (threadIdx.x < kStepSums) partial[(size_t)blockIdx.x * 8 + threadIdx.x] = red[threadIdx.x][0];
 }
 
-// scalars: [0] mean loss, [1] mae, [2] mse, [3] rmse, [4] r2, [5] mean clip(aleatoric_std, 0, 5),
-//          [6] mean clip(epistemic_std, 0, 5) (0 when it was not wanted), [7] element count — as val_finalize_kernel (optim.hip)
+// scalars: write_step_scalars (block_reduce.h); [6] is 0 when the epistemic map was not wanted
 __global__ __launch_bounds__(256) void evidential_step_finalize_kernel(const double* __restrict__ partial, int blocks, double count,
                                                                       float* __restrict__ scalars) {
-  __shared__ double red[kStepSums][256];
   __shared__ double tot[kStepSums];
   double a[kStepSums];
 #pragma unroll
   for (int k = 0; k < kStepSums; ++k) a[k] = 0.0;
-  for (int b = threadIdx.x; b < blocks; b += 256)  // 256 threads walk the partial rows, then a fixed-order tree
+  for (int b = threadIdx.x; b < blocks; b += 256)  // 256 threads walk the partial rows, then the fixed-order tree
 #pragma unroll
     for (int k = 0; k < kStepSums; ++k) a[k] += partial[(size_t)b * 8 + k];
-#pragma unroll
-  for (int k = 0; k < kStepSums; ++k) red[k][threadIdx.x] = a[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-#pragma unroll
-      for (int k = 0; k < kStepSums; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  const auto red = block_reduce_rows(a);
   if (threadIdx.x < kStepSums) tot[threadIdx.x] = red[threadIdx.x][0];
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const double mse = tot[1] / count;
-    const double ss_tot = tot[4] - tot[3] * tot[3] / count;
-    scalars[0] = (float)(tot[0] / count);
-    scalars[1] = (float)(tot[2] / count);
-    scalars[2] = (float)mse;
-    scalars[3] = (float)sqrt(mse);
-    scalars[4] = (float)(1.0 - tot[1] / ss_tot);
-    scalars[5] = (float)(tot[5] / count);
-    scalars[6] = (float)(tot[6] / count);
-    scalars[7] = (float)count;
-  }
+  if (threadIdx.x == 0) write_step_scalars(tot, count, scalars);
 }
 
 }  // namespace
 }  // namespace mimo
 
 using namespace mimo;
+
+extern "C" int mimo_evidential_forward(const float* logits, const float* label, const float* mask, int32_t n, int64_t hw,
+                                       float* ev, float* loss_map, mimo_stream stream) {
+  if (!logits || !ev || n < 0 || hw < 0 || (loss_map && !label)) {
+    set_error("mimo_evidential_forward: invalid argument");
+    return MIMO_ERR_INVALID;
+  }
+  const int64_t total = (int64_t)n * hw;
+  if (total == 0) return MIMO_OK;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
+  hipLaunchKernelGGL(evidential_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, label, mask, total, hw, ev,
+                     loss_map);
+  MIMO_KERNEL_CHECK();
+  return MIMO_OK;
+}
+
+extern "C" int mimo_evidential_backward(const float* logits, const float* label, const float* mask, const float* d_ev,
+                                        const float* d_loss, int32_t n, int64_t hw, float* dlogits, mimo_stream stream) {
+  if (!logits || !dlogits || n < 0 || hw < 0 || (d_loss && !label)) {
+    set_error("mimo_evidential_backward: invalid argument");
+    return MIMO_ERR_INVALID;
+  }
+  const int64_t total = (int64_t)n * hw;
+  if (total == 0) return MIMO_OK;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
+  hipLaunchKernelGGL(evidential_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, label, mask, d_ev, d_loss,
+                     total, hw, dlogits);
+  MIMO_KERNEL_CHECK();
+  return MIMO_OK;
+}
 
 extern "C" int mimo_evidential_uncertainties(const float* logits, int32_t n, int64_t hw, float* mean, float* aleatoric_var,
                                              float* epistemic_var, mimo_stream stream) {

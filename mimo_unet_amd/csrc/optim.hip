@@ -1,13 +1,17 @@
-// Fused flat-buffer Adam and the subnetwork-axis uncertainty reduction (gfx950, HBM-bound).
+// The tail of a MIMO U-Net step (gfx950, HBM-bound): the fused flat-buffer Adam step, the subnetwork-axis uncertainty
+// reduction, the training and validation epilogues with their one-workgroup finalize kernels (the workgroup sums and the
+// validation scalars: block_reduce.h) and the loss-buffer step.
 //
-// Replaces: torch.optim.Adam.step as configured by mimo/models/mimo_unet.py:186-190
-//           (betas .9/.999, eps 1e-8, L2 weight decay folded into the gradient, not AdamW);
-//           compute_uncertainties, mimo/models/utils.py:76-101.
+// Replaces: torch.optim.Adam.step as configured by mimo/models/mimo_unet.py:186-190;
+//           compute_uncertainties, mimo/models/utils.py:76-101;
+//           the metric and logging tails of training_step / validation_step, mimo_unet.py:121-183, and
+//           _calculate_train_loss, mimo_unet.py:223-247.
 #include <algorithm>
 #include <cmath>
 
+#include "adam_update.h"
+#include "block_reduce.h"
 #include "common.h"
-#include "evidential.h"
 
 namespace mimo {
 
@@ -26,10 +30,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   if (found_inf && *found_inf != 0.f) return;  // the scaler saw an inf / nan gradient: skip this step
   if (step_dev) {
     const float t = *step_dev;
-    // 1 - beta^t as -expm1(t log1p(beta - 1)) (beta - 1 is exact): 1 - powf(beta, t) keeps the rounding of a number near 1
-    // in a result of about t (1 - beta) — 6.7e-6 of the second-moment correction at t = 2, 1.7e-8 in this form
-    bc1 = -expm1f(t * log1pf(beta1 - 1.f));
-    bc2_sqrt = sqrtf(-expm1f(t * log1pf(beta2 - 1.f)));
+    bc1 = adam_bias_correction(t, beta1);
+    bc2_sqrt = sqrtf(adam_bias_correction(t, beta2));
   }
   if (amp_scale) grad_scale /= *amp_scale;
   const int64_t n4 = n / 4;
@@ -44,28 +46,15 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     float* ma = &mm.x;
     float* va = &vv.x;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gr = ga[j] * grad_scale;
-      if (wd != 0.f) gr = fmaf(wd, pa[j], gr);
-      ma[j] = beta1 * ma[j] + (1.f - beta1) * gr;
-      va[j] = beta2 * va[j] + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(va[j]) / bc2_sqrt + eps;
-      pa[j] -= (lr / bc1) * (ma[j] / denom);
-    }
+    for (int j = 0; j < 4; ++j)
+      adam_element(&pa[j], ga[j] * grad_scale, &ma[j], &va[j], lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
   // tail (n not a multiple of 4)
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float gr = g[i] * grad_scale;
-    if (wd != 0.f) gr = fmaf(wd, p[i], gr);
-    const float mi = beta1 * m[i] + (1.f - beta1) * gr;
-    const float vi = beta2 * v[i] + (1.f - beta2) * gr * gr;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    adam_element(&p[i], g[i] * grad_scale, &m[i], &v[i], lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
 }
 
 __global__ void uncertainty_kernel(const float* __restrict__ p1, const float* __restrict__ p2, int N, int S, int64_t chw,
@@ -107,7 +96,6 @@ __global__ void val_epilogue_kernel(const float* __restrict__ out, const float* 
                                     const float* __restrict__ mask, int N, int S, int Ct, int64_t hw, int kind, float eps_min,
                                     float eps_max, float* __restrict__ mean, float* __restrict__ alea_std,
                                     float* __restrict__ epi_std, float* __restrict__ err, double* __restrict__ partial) {
-  __shared__ double red[kValSums][256];
   const int64_t chw = (int64_t)Ct * hw, total = (int64_t)N * chw;
   double acc[kValSums];
 #pragma unroll
@@ -151,52 +139,23 @@ __global__ void val_epilogue_kernel(const float* __restrict__ out, const float* 
     acc[5] += fminf(fmaxf(as, 0.f), 5.f);
     acc[6] += fminf(fmaxf(es, 0.f), 5.f);
   }
-#pragma unroll
-  for (int k = 0; k < kValSums; ++k) red[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-#pragma unroll
-      for (int k = 0; k < kValSums; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  const auto red = block_reduce_rows(acc);
   if (threadIdx.x < kValSums) partial[(size_t)blockIdx.x * kValSums + threadIdx.x] = red[threadIdx.x][0];
 }
 
-// scalars: [0] combined NLL (mean), [1] mae, [2] mse, [3] rmse, [4] r2, [5] mean clip(aleatoric_std, 0, 5),
-//          [6] mean clip(epistemic_std, 0, 5), [7] element count
+// scalars: [0] combined NLL (mean), then as write_step_scalars (block_reduce.h)
 __global__ void val_finalize_kernel(const double* __restrict__ partial, int blocks, double count, float* __restrict__ scalars) {
-  __shared__ double red[kValSums][256];
   __shared__ double tot[kValSums];
   double a[kValSums];
 #pragma unroll
   for (int k = 0; k < kValSums; ++k) a[k] = 0.0;
-  for (int b = threadIdx.x; b < blocks; b += 256)
+  for (int b = threadIdx.x; b < blocks; b += 256)  // 256 threads walk the partial rows, then the fixed-order tree
 #pragma unroll
     for (int k = 0; k < kValSums; ++k) a[k] += partial[(size_t)b * kValSums + k];
-#pragma unroll
-  for (int k = 0; k < kValSums; ++k) red[k][threadIdx.x] = a[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-#pragma unroll
-      for (int k = 0; k < kValSums; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  const auto red = block_reduce_rows(a);
   if (threadIdx.x < kValSums) tot[threadIdx.x] = red[threadIdx.x][0];
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const double mse = tot[1] / count;
-    const double ss_tot = tot[4] - tot[3] * tot[3] / count;
-    scalars[0] = (float)(tot[0] / count);
-    scalars[1] = (float)(tot[2] / count);
-    scalars[2] = (float)mse;
-    scalars[3] = (float)sqrt(mse);
-    scalars[4] = (float)(1.0 - tot[1] / ss_tot);
-    scalars[5] = (float)(tot[5] / count);
-    scalars[6] = (float)(tot[6] / count);
-    scalars[7] = (float)count;
-  }
+  if (threadIdx.x == 0) write_step_scalars(tot, count, scalars);
 }
 
 // Training-step epilogue (mimo_unet.py:121-144): gathered labels, predictions, aleatoric std, error map and the
@@ -205,7 +164,6 @@ __global__ void train_epilogue_kernel(const float* __restrict__ out, const float
                                       const int64_t* __restrict__ perm, int N, int S, int Ct, int64_t hw, int kind,
                                       float* __restrict__ label_t, float* __restrict__ preds, float* __restrict__ alea_std,
                                       float* __restrict__ err, double* __restrict__ partial) {
-  __shared__ double red[4][256];
   const int64_t chw = (int64_t)Ct * hw, total = (int64_t)N * S * chw;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -225,35 +183,18 @@ __global__ void train_epilogue_kernel(const float* __restrict__ out, const float
     acc[2] += y;
     acc[3] += (double)y * y;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  const auto red = block_reduce_rows(acc);
   if (threadIdx.x < 4) partial[(size_t)blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
 }
 
 // scalars: [0] mae, [1] mse, [2] rmse, [3] r2, [4] element count
 __global__ void train_finalize_kernel(const double* __restrict__ partial, int blocks, double count, float* __restrict__ scalars) {
-  __shared__ double red[4][256];
   __shared__ double tot[4];
   double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < blocks; b += 256)  // 256 threads walk the partial rows, then a fixed-order tree
+  for (int b = threadIdx.x; b < blocks; b += 256)  // 256 threads walk the partial rows, then the fixed-order tree
 #pragma unroll
     for (int k = 0; k < 4; ++k) a[k] += partial[(size_t)b * 4 + k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = a[k];
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  const auto red = block_reduce_rows(a);
   if (threadIdx.x < 4) tot[threadIdx.x] = red[threadIdx.x][0];
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -345,84 +286,6 @@ extern "C" int mimo_validation_epilogue(const float* out, const float* label, co
                      loss_kind, eps_min, eps_max, mean, aleatoric_std, epistemic_std, err, scratch);
   MIMO_KERNEL_CHECK();
   hipLaunchKernelGGL(val_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, blocks, (double)total, scalars);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// Evidential regression head + loss (mimo/models/evidential_unet.py:74-96, mimo/losses.py:202-247):
-//   (mu, v, alpha, beta) = (l0, softplus(l1), softplus(l2) + 1, softplus(l3))
-//   loss = G(alpha) / (v sqrt(beta)) * (2 beta (1 + v) + (2 alpha - 1) v (y - mu)^2) + (y - mu)^2 (2 alpha + v),
-//   G(alpha) = Gamma(alpha - 1/2) / (4 Gamma(alpha))
-// One pass for the four NIG parameters + the per-pixel loss, one pass for the gradient w.r.t. the logits (analytic:
-// dG/dalpha = G (psi(alpha - 1/2) - psi(alpha))) instead of ~40 element-wise tensor operations and their autograd
-// nodes.  G is evaluated as exp(lgamma(alpha - 1/2) - lgamma(alpha)) / 4 — the reference exponentiates the two
-// lgammas separately, which overflows fp32 (inf / inf = nan) for alpha > 35; this form stays finite there.
-// ---------------------------------------------------------------------------------------
-// (softplus_f, nig_point and the loss gradient: evidential.h, shared with the evaluation kernels of evidential_eval.hip)
-using mimo::nig_bwd_pixel;
-using mimo::nig_point;
-using mimo::NigPoint;
-using mimo::NigUpTensor;
-
-__global__ void evidential_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ label,
-                                      const float* __restrict__ mask, int64_t total, int64_t hw, float* __restrict__ ev,
-                                      float* __restrict__ loss) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t n = i / hw, r = i - n * hw;
-    const float* l = logits + n * 4 * hw + r;
-    const NigPoint q = nig_point(l[0], l[hw], l[2 * hw], l[3 * hw], label ? label[i] : 0.f);
-    float* e = ev + n * 4 * hw + r;
-    e[0] = q.mu;
-    e[hw] = q.v;
-    e[2 * hw] = q.alpha;
-    e[3 * hw] = q.beta;
-    if (loss && label) {
-      const float sq = q.d * q.d;
-      float v = q.c * q.T + sq * (2.f * q.alpha + q.v);
-      if (mask) v *= mask[i];
-      loss[i] = v;
-    }
-  }
-}
-
-// dlogits = d_loss * dloss/dlogits (+ d_ev * dev/dlogits): both upstream gradients optional
-__global__ void evidential_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ label,
-                                      const float* __restrict__ mask, const float* __restrict__ d_ev,
-                                      const float* __restrict__ d_loss, int64_t total, int64_t hw, float* __restrict__ dlogits) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    nig_bwd_pixel(logits, label, mask, d_ev, NigUpTensor{d_loss}, i, hw, dlogits);
-  }
-}
-
-extern "C" int mimo_evidential_forward(const float* logits, const float* label, const float* mask, int32_t n, int64_t hw,
-                                       float* ev, float* loss_map, mimo_stream stream) {
-  using namespace mimo;
-  if (!logits || !ev || n < 0 || hw < 0 || (loss_map && !label)) {
-    set_error("mimo_evidential_forward: invalid argument");
-    return MIMO_ERR_INVALID;
-  }
-  const int64_t total = (int64_t)n * hw;
-  if (total == 0) return MIMO_OK;
-  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
-  hipLaunchKernelGGL(evidential_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, label, mask, total, hw, ev,
-                     loss_map);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-extern "C" int mimo_evidential_backward(const float* logits, const float* label, const float* mask, const float* d_ev,
-                                        const float* d_loss, int32_t n, int64_t hw, float* dlogits, mimo_stream stream) {
-  using namespace mimo;
-  if (!logits || !dlogits || n < 0 || hw < 0 || (d_loss && !label)) {
-    set_error("mimo_evidential_backward: invalid argument");
-    return MIMO_ERR_INVALID;
-  }
-  const int64_t total = (int64_t)n * hw;
-  if (total == 0) return MIMO_OK;
-  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
-  hipLaunchKernelGGL(evidential_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, label, mask, d_ev, d_loss,
-                     total, hw, dlogits);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }

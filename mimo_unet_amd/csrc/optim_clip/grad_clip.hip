@@ -3,9 +3,10 @@
 // Replaces: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ over the parameter views followed by torch.optim.Adam.step
 //           (what Lightning's Trainer(gradient_clip_val=...) runs around the optimiser of mimo/models/mimo_unet.py:186-190).
 //
-// Lives in a subdirectory because the benchmark never launches it (bench.csrc_hash covers csrc/*.hip, csrc/*.h); optim.hip's
-// adam_kernel / amp_step_kernel are untouched and the update kernel below repeats adam_kernel's per-element expressions in
-// the same shape, so that with a coefficient of 1 both give the same bits.
+// Lives in a subdirectory because the benchmark never launches it (bench.csrc_hash covers csrc/*.hip, csrc/*.h).  The update
+// kernel below and optim.hip's adam_kernel call one per-element update and one bias-correction helper (../adam_update.h):
+// they differ only in how a raw gradient element becomes the effective gradient, so that with a coefficient of 1 both give
+// the same bits.
 //
 // Effective gradient ge = g * s, s = grad_scale (/ *amp_scale when given): the factor adam_kernel applies.
 //   norm mode : norm = sqrt(sum ge^2), coef = min(1, clip / (norm + 1e-6)), the update sees (g * s) * coef
@@ -16,7 +17,8 @@
 //   2. clip_finalize_kernel one workgroup folds the row in a fixed order, forms norm and coef in double, rounds each to fp32
 //                          once, writes clip_out, decides skip / apply (found_inf, finiteness of the norm), advances step_dev
 //                          (amp_step_kernel's job on this route) and leaves {coef, skip} behind the row
-//   3. adam_clipped_kernel reads {coef, skip}; adam_kernel's arithmetic
+//   3. adam_clipped_kernel reads {coef, skip}; the shared update
+#include "../adam_update.h"
 #include "../common.h"
 
 #include <algorithm>
@@ -115,7 +117,7 @@ __device__ __forceinline__ float clipped(float ge, float c) {
 }
 
 // adam_kernel (optim.hip) with the clipped gradient; c = the coefficient (norm mode, read from the verdict) or the bound
-// (value mode).  Every expression after `gr` is adam_kernel's, in its shape: the compiler contracts them alike.
+// (value mode).  Everything after the effective gradient is adam_element (adam_update.h), which adam_kernel calls too.
 template <int MODE>
 __global__ void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                     float* __restrict__ v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
@@ -124,8 +126,8 @@ __global__ void adam_clipped_kernel(float* __restrict__ p, const float* __restri
   if (verdict->skip != 0) return;  // found_inf, or a norm that is not finite: skip this step
   const float c = MODE == MIMO_CLIP_NORM ? verdict->coef : clip;
   const float t = *step_dev;
-  const float bc1 = -expm1f(t * log1pf(beta1 - 1.f));
-  const float bc2_sqrt = sqrtf(-expm1f(t * log1pf(beta2 - 1.f)));
+  const float bc1 = adam_bias_correction(t, beta1);
+  const float bc2_sqrt = sqrtf(adam_bias_correction(t, beta2));
   if (amp_scale) grad_scale /= *amp_scale;
   const int64_t n4 = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -139,28 +141,15 @@ __global__ void adam_clipped_kernel(float* __restrict__ p, const float* __restri
     float* ma = &mm.x;
     float* va = &vv.x;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gr = clipped<MODE>(ga[j] * grad_scale, c);
-      if (wd != 0.f) gr = fmaf(wd, pa[j], gr);
-      ma[j] = beta1 * ma[j] + (1.f - beta1) * gr;
-      va[j] = beta2 * va[j] + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(va[j]) / bc2_sqrt + eps;
-      pa[j] -= (lr / bc1) * (ma[j] / denom);
-    }
+    for (int j = 0; j < 4; ++j)
+      adam_element(&pa[j], clipped<MODE>(ga[j] * grad_scale, c), &ma[j], &va[j], lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
   // tail (n not a multiple of 4)
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float gr = clipped<MODE>(g[i] * grad_scale, c);
-    if (wd != 0.f) gr = fmaf(wd, p[i], gr);
-    const float mi = beta1 * m[i] + (1.f - beta1) * gr;
-    const float vi = beta2 * v[i] + (1.f - beta2) * gr * gr;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    adam_element(&p[i], clipped<MODE>(g[i] * grad_scale, c), &m[i], &v[i], lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
 }
 
 }  // namespace gradclip
