@@ -570,6 +570,113 @@ typedef struct mimo_op_head_backward_args {
 } mimo_op_head_backward_args;
 int mimo_op_head_backward(const mimo_op_head_backward_args* args, mimo_stream stream);
 
+/* ---- single-operator entry points of the forward element-wise kernels (elementwise.hip) -------
+ * The conventions of the backward block above: fp32 NHWC tensors at the interface, c_p a multiple of 8, pitches multiples of
+ * 4; MIMO_PREC_BF16_MIXED / MIMO_PREC_FP16_MIXED round whole activation-like buffers (at their pitch) into 16-bit copies,
+ * run the 16-bit storage kernels and widen the outputs again (an output buffer makes the round trip as a whole: what the
+ * kernel leaves unwritten comes back rounded to the storage type, a NaN as a NaN).  Statistics, BatchNorm vectors, Dropout2d
+ * multipliers, weights, logits and losses are fp32 in every mode.  An invalid call returns MIMO_ERR_INVALID with nothing
+ * launched and nothing written. */
+
+/* BatchNorm2d statistics (components.py:24) from the partial rows [rows][2][cout_pad] of a convolution epilogue (row r: the
+ * sums, then the sums of squares, of the channels over that workgroup's pixels; `count` elements per channel in all):
+ *   mean = s1 / count, var = max(s2 / count - mean^2, 0), invstd = 1 / sqrt(var + eps), scale = gamma invstd,
+ *   shift = beta - mean scale;  running_mean / running_var (in place) move by `momentum` towards mean and the unbiased
+ *   variance var count / (count - 1) (var itself when count == 1);  channels [c, c_p) of the four vectors are zeros.
+ * route: 1 = the one-launch column sum + finalize (rows <= 2048); 2 = the chunked row sum (at most 64 fp64 chunk rows)
+ * followed by the finalize launch, which has no status word; 0 = the plan's rule: "rows <= kColsumMaxRows (2048): the one
+ * launch; otherwise row sum + finalize".  training = 0: mean / invstd / scale / shift from the running statistics instead
+ * (partial, rows, count, route and momentum unused).  status (host, or NULL): bit 1 when a channel sum (eval: a running
+ * statistic or its scale) is not finite.
+ * Invalid: rows < 1, c < 1, c > c_p, c_p > cout_pad, c_p or cout_pad not a multiple of 8, count < 1, route outside 0..2,
+ * route 1 with rows > 2048, a NULL tensor. */
+enum mimo_bn_stats_route { MIMO_BN_ROUTE_PLAN = 0, MIMO_BN_ROUTE_ONE_LAUNCH = 1, MIMO_BN_ROUTE_ROWSUM = 2 };
+typedef struct mimo_op_bn_stats_args {
+  const float* partial;
+  int32_t rows, cout_pad, c, c_p, training, route;
+  int64_t count;
+  const float *gamma, *beta;          /* [c] */
+  float *running_mean, *running_var;  /* [c] */
+  float momentum, eps;
+  float *mean, *invstd, *scale, *shift; /* [c_p] */
+  int32_t* status;
+} mimo_op_bn_stats_args;
+int mimo_op_bn_stats(const mimo_op_bn_stats_args* args, mimo_stream stream);
+
+/* a[n,h,w] (lda) = relu(fma(z (ldz), scale, shift)) * mask[n][c] (mask: Dropout2d multipliers or NULL; channels [c, c_p) of
+ * a masked call are zeros).  pool != NULL: the fused kernel, which also writes pool[n, h/2, w/2] (ldpool) = MaxPool2d(2)(a).
+ * z_fp32 != 0 in a 16-bit mode: z stays fp32 (the image convolution's output), only a / pool are 16-bit.
+ * status (host, or NULL): bit 1 when an element of z is not finite.
+ * Invalid: bad dimensions or pitches, c outside [1, c_p], a NULL z / scale / shift / a, pool with h or w < 2. */
+typedef struct mimo_op_bn_relu_forward_args {
+  const float* z;
+  int32_t ldz;
+  const float *scale, *shift; /* [c_p] */
+  const float* mask;          /* [n][c] or NULL */
+  int32_t n, h, w, c, c_p, precision, z_fp32;
+  float* a;
+  int32_t lda;
+  float* pool;
+  int32_t ldpool;
+  int32_t* status;
+} mimo_op_bn_relu_forward_args;
+int mimo_op_bn_relu_forward(const mimo_op_bn_relu_forward_args* args, mimo_stream stream);
+
+/* mimo_op_maxpool2x2 with pitches and a storage mode: y[n, h/2, w/2] (ldo) = max over the 2x2 windows of x[n,h,w] (lda) */
+int mimo_op_maxpool2x2_ex(const float* x, int32_t lda, float* y, int32_t ldo, int32_t n, int32_t h, int32_t w, int32_t c_p,
+                          int32_t precision, mimo_stream stream);
+/* mimo_op_upsample_cat with pitches, a storage mode and the producer's BatchNorm + ReLU: out[n,hs,ws,cs_p + cl_p] =
+ * cat(skip (lds), zero_pad(bilinear_x2_align_corners(low [n,hl,wl] (ldl)))); lo_scale / lo_shift [cl_p] != NULL: low is a
+ * pre-activation tensor and relu(fma(low, lo_scale, lo_shift)) is interpolated.  skip == NULL writes only the up-sampled
+ * channels [cs_p, cs_p + cl_p) (with hs == 2 hl and ws == 2 wl: the kernel that works by 2x2 output blocks).
+ * Invalid: bad dimensions or pitches, hs < 2 hl or ws < 2 wl, only one of lo_scale / lo_shift. */
+int mimo_op_upsample_cat_ex(const float* skip, int32_t lds, const float* low, int32_t ldl, const float* lo_scale,
+                            const float* lo_shift, float* out, int32_t n, int32_t hs, int32_t ws, int32_t cs_p, int32_t hl,
+                            int32_t wl, int32_t cl_p, int32_t precision, mimo_stream stream);
+
+/* 1x1 head (components.py:126): out[n][s][co'][yx] = bias[co'] + sum_{c' < c} a[n,yx,c'] w[co'][c'] for subnetwork s of
+ * out [n][subnetworks][co][hw] (the other subnetworks are left alone).  a [n,hw] (lda >= c rounded up to 8; its padding
+ * channels are read and multiplied by zero, so they must be finite); in_scale / in_shift [c rounded up to 8] != NULL: a is
+ * the pre-activation tensor, relu(fma(a, in_scale, in_shift)) is applied on the way in.  status (host, or NULL): bit 4 when
+ * a logit is not finite.
+ * Invalid: c outside [1, 256], co outside [1, 8], n, hw < 1 or n hw >= 2^31, s outside [0, subnetworks), lda too small or
+ * not a multiple of 4, only one of in_scale / in_shift, a NULL tensor. */
+typedef struct mimo_op_head_forward_args {
+  const float* a;
+  int32_t lda;
+  const float *w, *bias; /* [co][c], [co] */
+  int32_t c, co, n, subnetworks, s, hw;
+  const float *in_scale, *in_shift;
+  int32_t precision;
+  float* out;
+  int32_t* status;
+} mimo_op_head_forward_args;
+int mimo_op_head_forward(const mimo_op_head_forward_args* args, mimo_stream stream);
+
+/* loss[s] = mean over n, target channel and pixel of mask * NLL(out[n][s][t] - label[perm[s][n]][t], out[n][s][co/2 + t])
+ * (losses.py:151-160; mimo_loss_forward's arithmetic: fp32 terms, fp32 per-thread and per-workgroup sums, fp64 across
+ * workgroups).  out [n][subnetworks][co][hw], label [n][co/2][hw], mask [n][hw] or NULL (indexed like the label), perm
+ * [subnetworks][n] (device int64, every entry in [0, n)) or NULL.
+ * Invalid: co odd or outside [2, 8], n, hw, subnetworks < 1, an unknown loss_kind, a perm entry outside [0, n), a NULL tensor. */
+int mimo_op_loss_forward(const float* out, const float* label, const float* mask, const int64_t* perm, int32_t n,
+                         int32_t subnetworks, int32_t co, int32_t hw, int32_t loss_kind, float eps_min, float eps_max,
+                         float* loss, mimo_stream stream);
+
+/* out[n,h,w,cp] = x[perm[s][n]][s][c'][y][x] for c' < c, zeros in channels [c, cp): the input gather of subnetwork s
+ * (utils.py:38-48).  x is addressed as x + image * stride_n + s * stride_s + c' * h * w + yx (strides in elements) and holds
+ * x_count elements.  Invalid: c outside [1, cp], cp not a multiple of 4, negative strides, an address beyond x_count, a perm
+ * entry outside [0, n). */
+int mimo_op_pack_input(const float* x, int64_t x_count, int64_t stride_n, int64_t stride_s, const int64_t* perm, int32_t s,
+                       int32_t n, int32_t c, int32_t h, int32_t w, float* out, int32_t cp, mimo_stream stream);
+/* dx[n][s][c'][y][x] = fold(dxpad [n, h + 2, w + 2] (ldp))[n][y][x][c'], c' < c, of dx [n][subnetworks][c][h][w] (fp32 in
+ * every mode; dxpad in the storage type).  Invalid: h or w < 2, ldp % 4 != 0 or below c rounded up to 4, s outside
+ * [0, subnetworks). */
+int mimo_op_unpack_dx(const float* dxpad, int32_t ldp, int32_t n, int32_t subnetworks, int32_t s, int32_t c, int32_t h,
+                      int32_t w, int32_t precision, float* dx, mimo_stream stream);
+/* dimage[n][c'][y][x] (=|+=) fold(dxpad)[n][y][x][c'] (fp32 storage) */
+int mimo_op_fold_image_grad(const float* dxpad, int32_t ldp, int32_t n, int32_t c, int32_t h, int32_t w, float* dimage,
+                            int32_t accumulate, mimo_stream stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

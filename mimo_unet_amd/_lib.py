@@ -78,6 +78,38 @@ class HeadBackwardArgs(C.Structure):
     ]
 
 
+class BnStatsArgs(C.Structure):
+    """mimo_op_bn_stats_args (include/mimo_hip.h)"""
+    _fields_ = [
+        ("partial", C.c_void_p), ("rows", C.c_int32), ("cout_pad", C.c_int32), ("c", C.c_int32), ("c_p", C.c_int32),
+        ("training", C.c_int32), ("route", C.c_int32), ("count", C.c_int64),
+        ("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+        ("momentum", C.c_float), ("eps", C.c_float),
+        ("mean", C.c_void_p), ("invstd", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+        ("status", C.POINTER(C.c_int32)),
+    ]
+
+
+class BnReluForwardArgs(C.Structure):
+    """mimo_op_bn_relu_forward_args (include/mimo_hip.h)"""
+    _fields_ = [
+        ("z", C.c_void_p), ("ldz", C.c_int32), ("scale", C.c_void_p), ("shift", C.c_void_p), ("mask", C.c_void_p),
+        ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("c_p", C.c_int32), ("precision", C.c_int32),
+        ("z_fp32", C.c_int32),
+        ("a", C.c_void_p), ("lda", C.c_int32), ("pool", C.c_void_p), ("ldpool", C.c_int32), ("status", C.POINTER(C.c_int32)),
+    ]
+
+
+class HeadForwardArgs(C.Structure):
+    """mimo_op_head_forward_args (include/mimo_hip.h)"""
+    _fields_ = [
+        ("a", C.c_void_p), ("lda", C.c_int32), ("w", C.c_void_p), ("bias", C.c_void_p),
+        ("c", C.c_int32), ("co", C.c_int32), ("n", C.c_int32), ("subnetworks", C.c_int32), ("s", C.c_int32), ("hw", C.c_int32),
+        ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("precision", C.c_int32),
+        ("out", C.c_void_p), ("status", C.POINTER(C.c_int32)),
+    ]
+
+
 LOSS_KINDS = {"laplace_nll": 0, "gaussian_nll": 1}
 # "bf16-mixed" / "16-mixed": Lightning's names for bf16 / fp16 autocast training — here 16-bit storage + operands
 PRECISIONS = {"fp32": 0, "split16": 1, "bf16": 2, "bf16-mixed": 3, "16-mixed": 4}
@@ -145,6 +177,15 @@ _SIGNATURES = {
     "mimo_op_up_backward": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mimo_op_bn_relu_backward": (C.c_int, [C.POINTER(BnReluBackwardArgs), _P]),
     "mimo_op_head_backward": (C.c_int, [C.POINTER(HeadBackwardArgs), _P]),
+    "mimo_op_bn_stats": (C.c_int, [C.POINTER(BnStatsArgs), _P]),
+    "mimo_op_bn_relu_forward": (C.c_int, [C.POINTER(BnReluForwardArgs), _P]),
+    "mimo_op_maxpool2x2_ex": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_op_upsample_cat_ex": (C.c_int, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_op_head_forward": (C.c_int, [C.POINTER(HeadForwardArgs), _P]),
+    "mimo_op_loss_forward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P]),
+    "mimo_op_pack_input": (C.c_int, [_P, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "mimo_op_unpack_dx": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "mimo_op_fold_image_grad": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -650,3 +650,283 @@ int mimo_op_head_backward(const mimo_op_head_backward_args* p, mimo_stream strea
 }
 
 }  // extern "C"
+
+// ---- forward element-wise operators (tests/test_ew_fwd_kernels_gpu.py) -----------------------------------------------------
+// The conventions of the backward block: fp32 at the interface, whole buffers rounded at their pitch in the 16-bit modes.
+
+namespace {
+
+// dimensions of a forward operator (no reflect fold: one row or column is a tensor)
+bool bad_fwd_dims(const char* who, int n, int h, int w, int c_p) {
+  if (n < 1 || h < 1 || w < 1 || c_p < 8 || c_p % 8 != 0 || (int64_t)n * h * w >= (int64_t)1 << 31) {
+    set_error("%s: n %d, %d x %d, c_p %d unsupported (n, h, w >= 1, n h w < 2^31, c_p a multiple of 8)", who, n, h, w, c_p);
+    return true;
+  }
+  return false;
+}
+bool bad_precision(const char* who, int precision) {
+  if (precision != MIMO_PREC_FP32 && !is_mixed(precision)) {
+    set_error("%s: precision %d (fp32, bf16-mixed or 16-mixed storage)", who, precision);
+    return true;
+  }
+  return false;
+}
+// a device permutation [rows][n]: every entry of row s (all rows: s < 0) in [0, n)
+int bad_perm(const char* who, const int64_t* perm, int rows, int s, int n, hipStream_t st, bool* bad) {
+  *bad = false;
+  if (!perm) return MIMO_OK;
+  const int r0 = s < 0 ? 0 : s, nr = s < 0 ? rows : 1;
+  std::vector<int64_t> h((size_t)nr * n);
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  MIMO_HIP_CHECK(hipMemcpy(h.data(), perm + (size_t)r0 * n, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  for (int64_t v : h)
+    if (v < 0 || v >= n) {
+      set_error("%s: permutation entry %lld outside [0, %d)", who, (long long)v, n);
+      *bad = true;
+      break;
+    }
+  return MIMO_OK;
+}
+int read_status(const int* dev, int32_t* host) {
+  if (host) MIMO_HIP_CHECK(hipMemcpy(host, dev, sizeof(int), hipMemcpyDeviceToHost));
+  return MIMO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mimo_op_bn_stats(const mimo_op_bn_stats_args* p, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_bn_stats";
+  if (!p) {
+    set_error("%s: null arguments", who);
+    return MIMO_ERR_INVALID;
+  }
+  const mimo_op_bn_stats_args& a = *p;
+  if (a.c < 1 || a.c > a.c_p || a.c_p % 8 != 0 || a.cout_pad % 8 != 0 || a.c_p > a.cout_pad || !a.gamma || !a.beta || !a.running_mean ||
+      !a.running_var || !a.mean || !a.invstd || !a.scale || !a.shift ||
+      (a.training && (!a.partial || a.rows < 1 || a.count < 1 || a.route < MIMO_BN_ROUTE_PLAN || a.route > MIMO_BN_ROUTE_ROWSUM ||
+                      (a.route == MIMO_BN_ROUTE_ONE_LAUNCH && a.rows > kColsumMaxRows)))) {
+    set_error("%s: c %d of c_p %d of cout_pad %d, rows %d, count %lld, route %d (one launch: rows <= %d) or a missing tensor", who, a.c,
+              a.c_p, a.cout_pad, a.rows, (long long)a.count, a.route, kColsumMaxRows);
+    return MIMO_ERR_INVALID;
+  }
+  Temp t;
+  int* status = t.get<int>(1);
+  double* sums = t.get<double>((size_t)kMaxChunks * 2 * a.cout_pad);
+  if (!status || !sums) {
+    set_error("%s: allocation failed", who);
+    return MIMO_ERR_HIP;
+  }
+  if (!a.training) {
+    MIMO_TRY(bn_eval_prepare_launch(a.c, a.c_p, a.gamma, a.beta, a.running_mean, a.running_var, a.eps, a.mean, a.invstd, a.scale,
+                                    a.shift, st, status));
+  } else if (a.route == MIMO_BN_ROUTE_ONE_LAUNCH || (a.route == MIMO_BN_ROUTE_PLAN && a.rows <= kColsumMaxRows)) {
+    MIMO_TRY(bn_fwd_stats_launch(a.partial, a.rows, a.cout_pad, a.c, a.c_p, a.count, a.gamma, a.beta, a.running_mean, a.running_var,
+                                 a.momentum, a.eps, a.mean, a.invstd, a.scale, a.shift, status, st));
+  } else {
+    int chunks = 0;
+    MIMO_TRY(rowsum_launch(a.partial, a.rows, 2 * a.cout_pad, sums, &chunks, st));
+    MIMO_TRY(bn_fwd_finalize_launch(sums, chunks, a.cout_pad, a.c, a.c_p, a.count, a.gamma, a.beta, a.running_mean, a.running_var,
+                                    a.momentum, a.eps, a.mean, a.invstd, a.scale, a.shift, st));
+  }
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return read_status(status, a.status);
+}
+
+int mimo_op_bn_relu_forward(const mimo_op_bn_relu_forward_args* p, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_bn_relu_forward";
+  if (!p) {
+    set_error("%s: null arguments", who);
+    return MIMO_ERR_INVALID;
+  }
+  const mimo_op_bn_relu_forward_args& a = *p;
+  const int Cp = a.c_p;
+  if (bad_fwd_dims(who, a.n, a.h, a.w, Cp) || bad_precision(who, a.precision) || bad_slice(who, "z", a.ldz, 0, Cp) ||
+      bad_slice(who, "a", a.lda, 0, Cp))
+    return MIMO_ERR_INVALID;
+  if (a.c < 1 || a.c > Cp || !a.z || !a.scale || !a.shift || !a.a) {
+    set_error("%s: c %d of %d or a missing tensor", who, a.c, Cp);
+    return MIMO_ERR_INVALID;
+  }
+  if (a.pool && (bad_dims(who, a.n, a.h, a.w, Cp) || bad_slice(who, "pool", a.ldpool, 0, Cp))) return MIMO_ERR_INVALID;
+  const int prec = a.precision, zprec = a.z_fp32 ? (int)MIMO_PREC_FP32 : prec;
+  const int64_t P = (int64_t)a.n * a.h * a.w;
+  Temp t;
+  Stored zs, as, ps;
+  int* status = t.get<int>(1);
+  if (!status) {
+    set_error("%s: allocation failed", who);
+    return MIMO_ERR_HIP;
+  }
+  MIMO_TRY(stage_in(t, a.z, P * a.ldz, zprec, st, &zs));
+  MIMO_TRY(stage_out(t, a.a, P * a.lda, prec, st, &as));
+  if (a.pool) {
+    MIMO_TRY(stage_out(t, a.pool, (int64_t)a.n * (a.h / 2) * (a.w / 2) * a.ldpool, prec, st, &ps));
+    MIMO_TRY(bn_relu_pool_fwd_launch(zs.in, store_type(zprec), a.ldz, as.out, store_type(prec), a.lda, a.scale, a.shift, a.mask, a.c, Cp,
+                                     a.n, a.h, a.w, ps.out, a.ldpool, st, status));
+    MIMO_TRY(stage_back(ps, prec, st));
+  } else {
+    MIMO_TRY(bn_relu_fwd_launch(zs.in, store_type(zprec), a.ldz, as.out, store_type(prec), a.lda, a.scale, a.shift, a.mask, a.c, Cp, P,
+                                a.h * a.w, st, status));
+  }
+  MIMO_TRY(stage_back(as, prec, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return read_status(status, a.status);
+}
+
+int mimo_op_maxpool2x2_ex(const float* x, int32_t lda, float* y, int32_t ldo, int32_t n, int32_t h, int32_t w, int32_t c_p,
+                          int32_t precision, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_maxpool2x2_ex";
+  if (bad_dims(who, n, h, w, c_p) || bad_precision(who, precision) || bad_slice(who, "x", lda, 0, c_p) ||
+      bad_slice(who, "y", ldo, 0, c_p))
+    return MIMO_ERR_INVALID;
+  if (!x || !y) {
+    set_error("%s: a missing tensor", who);
+    return MIMO_ERR_INVALID;
+  }
+  Temp t;
+  Stored src, dst;
+  MIMO_TRY(stage_in(t, x, (int64_t)n * h * w * lda, precision, st, &src));
+  MIMO_TRY(stage_out(t, y, (int64_t)n * (h / 2) * (w / 2) * ldo, precision, st, &dst));
+  MIMO_TRY(maxpool_fwd_launch(src.in, store_type(precision), lda, n, h, w, c_p, dst.out, ldo, st));
+  MIMO_TRY(stage_back(dst, precision, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_upsample_cat_ex(const float* skip, int32_t lds, const float* low, int32_t ldl, const float* lo_scale,
+                            const float* lo_shift, float* out, int32_t n, int32_t hs, int32_t ws, int32_t cs_p, int32_t hl,
+                            int32_t wl, int32_t cl_p, int32_t precision, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_upsample_cat_ex";
+  if (bad_fwd_dims(who, n, hs, ws, cs_p) || bad_fwd_dims(who, n, hl, wl, cl_p) || bad_precision(who, precision) ||
+      bad_slice(who, "low", ldl, 0, cl_p) || (skip && bad_slice(who, "skip", lds, 0, cs_p)))
+    return MIMO_ERR_INVALID;
+  if (hs < 2 * hl || ws < 2 * wl || !low || !out || (!lo_scale != !lo_shift)) {
+    set_error("%s: %d x %d is smaller than twice %d x %d, a missing tensor, or only one of lo_scale / lo_shift", who, hs, ws, hl, wl);
+    return MIMO_ERR_INVALID;
+  }
+  Temp t;
+  Stored sk, lo, dst;
+  MIMO_TRY(stage_in(t, skip, (int64_t)n * hs * ws * lds, precision, st, &sk));
+  MIMO_TRY(stage_in(t, low, (int64_t)n * hl * wl * ldl, precision, st, &lo));
+  MIMO_TRY(stage_out(t, out, (int64_t)n * hs * ws * (cs_p + cl_p), precision, st, &dst));
+  MIMO_TRY(upcat_fwd_launch(sk.in, store_type(precision), lds, cs_p, lo.in, ldl, cl_p, n, hs, ws, hl, wl, dst.out, st, lo_scale, lo_shift));
+  MIMO_TRY(stage_back(dst, precision, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_head_forward(const mimo_op_head_forward_args* p, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_head_forward";
+  if (!p) {
+    set_error("%s: null arguments", who);
+    return MIMO_ERR_INVALID;
+  }
+  const mimo_op_head_forward_args& a = *p;
+  if (a.c < 1 || a.c > 256 || a.co < 1 || a.co > kMaxHeadOut || a.n < 1 || a.hw < 1 || (int64_t)a.n * a.hw >= (int64_t)1 << 31 ||
+      a.subnetworks < 1 || a.s < 0 || a.s >= a.subnetworks || !a.a || !a.w || !a.bias || !a.out || (!a.in_scale != !a.in_shift) ||
+      bad_precision(who, a.precision)) {
+    set_error("%s: c %d (1..256), co %d (1..%d), n %d, hw %d, subnetwork %d of %d, a missing tensor or only one of in_scale / in_shift",
+              who, a.c, a.co, kMaxHeadOut, a.n, a.hw, a.s, a.subnetworks);
+    return MIMO_ERR_INVALID;
+  }
+  if (bad_slice(who, "a", a.lda, 0, pad_channels(a.c))) return MIMO_ERR_INVALID;
+  Temp t;
+  Stored act;
+  int* status = t.get<int>(1);
+  if (!status) {
+    set_error("%s: allocation failed", who);
+    return MIMO_ERR_HIP;
+  }
+  MIMO_TRY(stage_in(t, a.a, (int64_t)a.n * a.hw * a.lda, a.precision, st, &act));
+  MIMO_TRY(head_fwd_launch(act.in, store_type(a.precision), a.lda, a.w, a.bias, a.c, a.co, a.n, a.subnetworks, a.s, a.hw, a.out, st,
+                           status, a.in_scale, a.in_shift));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return read_status(status, a.status);
+}
+
+int mimo_op_loss_forward(const float* out, const float* label, const float* mask, const int64_t* perm, int32_t n,
+                         int32_t subnetworks, int32_t co, int32_t hw, int32_t loss_kind, float eps_min, float eps_max,
+                         float* loss, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_loss_forward";
+  if (co < 2 || co > kMaxHeadOut || (co & 1) || n < 1 || hw < 1 || subnetworks < 1 || (int64_t)n * hw >= (int64_t)1 << 31 || !out ||
+      !label || !loss || (loss_kind != MIMO_LOSS_LAPLACE_NLL && loss_kind != MIMO_LOSS_GAUSSIAN_NLL)) {
+    set_error("%s: co %d (even, 2..%d), n %d, hw %d, %d subnetworks, loss kind %d or a missing tensor", who, co, kMaxHeadOut, n, hw,
+              subnetworks, loss_kind);
+    return MIMO_ERR_INVALID;
+  }
+  bool bad = false;
+  MIMO_TRY(bad_perm(who, perm, subnetworks, -1, n, st, &bad));
+  if (bad) return MIMO_ERR_INVALID;
+  Temp t;
+  float* partial = t.get<float>((size_t)subnetworks * 512);  // loss_fwd_launch's grid cap
+  if (!partial) {
+    set_error("%s: allocation failed", who);
+    return MIMO_ERR_HIP;
+  }
+  int blocks = 0;
+  MIMO_TRY(loss_fwd_launch(out, label, mask, perm, n, subnetworks, co, hw, loss_kind, eps_min, eps_max, partial, &blocks, st));
+  MIMO_TRY(loss_finalize_launch(partial, subnetworks, blocks, (double)n * (co / 2) * hw, loss, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_pack_input(const float* x, int64_t x_count, int64_t stride_n, int64_t stride_s, const int64_t* perm, int32_t s,
+                       int32_t n, int32_t c, int32_t h, int32_t w, float* out, int32_t cp, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_pack_input";
+  const int64_t hw = (int64_t)h * w;
+  if (n < 1 || h < 1 || w < 1 || (int64_t)n * hw >= (int64_t)1 << 31 || c < 1 || c > cp || cp % 4 != 0 || s < 0 || stride_n < 0 ||
+      stride_s < 0 || !x || !out || (int64_t)(n - 1) * stride_n + (int64_t)s * stride_s + (int64_t)c * hw > x_count) {
+    set_error("%s: n %d, %d x %d, c %d of %d, subnetwork %d, strides %lld / %lld do not fit %lld elements", who, n, h, w, c, cp, s,
+              (long long)stride_n, (long long)stride_s, (long long)x_count);
+    return MIMO_ERR_INVALID;
+  }
+  bool bad = false;
+  MIMO_TRY(bad_perm(who, perm, s + 1, s, n, st, &bad));
+  if (bad) return MIMO_ERR_INVALID;
+  MIMO_TRY(pack_input_launch(x, stride_n, stride_s, perm, s, n, c, h, w, out, cp, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_unpack_dx(const float* dxpad, int32_t ldp, int32_t n, int32_t subnetworks, int32_t s, int32_t c, int32_t h,
+                      int32_t w, int32_t precision, float* dx, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_unpack_dx";
+  if (c < 1 || bad_dims(who, n, h, w, 8) || bad_precision(who, precision) || bad_slice(who, "dxpad", ldp, 0, round_up(c, 4)))
+    return MIMO_ERR_INVALID;
+  if (subnetworks < 1 || s < 0 || s >= subnetworks || !dxpad || !dx) {
+    set_error("%s: subnetwork %d of %d or a missing tensor", who, s, subnetworks);
+    return MIMO_ERR_INVALID;
+  }
+  Temp t;
+  Stored src;
+  MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (h + 2) * (w + 2) * ldp, precision, st, &src));
+  MIMO_TRY(unpack_dx_launch(src.in, store_type(precision), ldp, n, subnetworks, s, c, h, w, dx, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+int mimo_op_fold_image_grad(const float* dxpad, int32_t ldp, int32_t n, int32_t c, int32_t h, int32_t w, float* dimage,
+                            int32_t accumulate, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_fold_image_grad";
+  if (c < 1 || bad_dims(who, n, h, w, 8) || bad_slice(who, "dxpad", ldp, 0, round_up(c, 4))) return MIMO_ERR_INVALID;
+  if (!dxpad || !dimage) {
+    set_error("%s: a missing tensor", who);
+    return MIMO_ERR_INVALID;
+  }
+  MIMO_TRY(fold_image_grad_launch(dxpad, ldp, n, c, h, w, dimage, accumulate, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
+}  // extern "C"
