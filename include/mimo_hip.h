@@ -262,6 +262,19 @@ int64_t mimo_plan_encoder_param_floats(const mimo_plan* plan);
 int mimo_input_gradient(mimo_plan* plan, const float* dout, const float* dloss, float* dimage, int accumulate,
                         mimo_stream stream);
 
+/* ---- the same for an MC-dropout forward (scripts/test/test_nyuv2_depth.py --monte_carlo_steps): the plan batch N holds
+ * `replicas` stochastic passes of the same N / replicas images, stacked pass-major (pass m, image b at row m * N / replicas + b,
+ * the layout of EnsembleModule.forward), each row with its own dropout multipliers — drop_masks / elem_masks of the forward, or
+ * drawn in the engine (rng_sites).  State checks, stages, kernels and encoder order of mimo_input_gradient; the dropout
+ * multipliers of the forward are applied to the gradients where the forward applied them.  dimage [N / replicas,Ci,H,W]: per
+ * encoder s = S-1 ... 0 one launch folds the first-layer data gradient and adds its passes in the fixed order
+ * m = 0 ... replicas-1 with fp32 adds (no atomics: deterministic); the first encoder assigns unless accumulate != 0.
+ * With dloss[s] = k / (M * S_total) for a chunk of k = replicas of M passes this is the chunk's share of
+ * d/d image of the mean NLL over all M * S_total outputs (the per-subnetwork loss is a mean over the chunk's N samples).
+ * replicas = 1: the bits of mimo_input_gradient.  MIMO_ERR_INVALID: replicas < 1 or N % replicas != 0. */
+int mimo_input_gradient_mc(mimo_plan* plan, const float* dout, const float* dloss, float* dimage, int accumulate, int replicas,
+                           mimo_stream stream);
+
 /* ---- FGSM: replaces fgsm_attack (scripts/test/test_nyuv2_depth.py:16-24) for all perturbation sizes of a sweep at once.
  * out[k][i] = clamp(image[i] + eps[k] * sign(dimage[i]), lo, hi), i < elems, k < K, with torch.sign's and torch.clamp's
  * arithmetic for every non-NaN gradient (sign(0) = 0; eps = 0 still clamps).  A NaN gradient or image pixel gives a NaN
@@ -676,6 +689,11 @@ int mimo_op_unpack_dx(const float* dxpad, int32_t ldp, int32_t n, int32_t subnet
 /* dimage[n][c'][y][x] (=|+=) fold(dxpad)[n][y][x][c'] (fp32 storage) */
 int mimo_op_fold_image_grad(const float* dxpad, int32_t ldp, int32_t n, int32_t c, int32_t h, int32_t w, float* dimage,
                             int32_t accumulate, mimo_stream stream);
+/* dimage[b][c'][y][x] (=|+=) sum over m = 0 .. replicas-1, in that order, of fold(dxpad)[m * (n / replicas) + b][y][x][c']:
+ * dxpad [n, h + 2, w + 2] (ldp) holds `replicas` passes of n / replicas images, pass-major; dimage [n / replicas][c][h][w].
+ * replicas = 1: the bits of mimo_op_fold_image_grad.  Invalid additionally: replicas < 1 or not a divisor of n. */
+int mimo_op_fold_image_grad_mc(const float* dxpad, int32_t ldp, int32_t n, int32_t replicas, int32_t c, int32_t h, int32_t w,
+                               float* dimage, int32_t accumulate, mimo_stream stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

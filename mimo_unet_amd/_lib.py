@@ -141,6 +141,7 @@ _SIGNATURES = {
     "mimo_backward_stage_async": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_void_p)]),
     "mimo_plan_encoder_param_floats": (_L, [_P]),
     "mimo_input_gradient": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "mimo_input_gradient_mc": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "mimo_fgsm_perturb": (C.c_int, [_P, _P, _L, C.POINTER(_F), C.c_int, _F, _F, _P, _P]),
     "mimo_plan_num_backward_stages": (C.c_int, [_P]),
     "mimo_plan_backward_stage_range": (C.c_int, [_P, C.c_int, C.POINTER(_L), C.POINTER(_L)]),
@@ -186,6 +187,7 @@ _SIGNATURES = {
     "mimo_op_pack_input": (C.c_int, [_P, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "mimo_op_unpack_dx": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mimo_op_fold_image_grad": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "mimo_op_fold_image_grad_mc": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -23,8 +23,29 @@ and test_ndvi_evidential.py drive the model itself, :42-65): `EvidentialUnetMode
 logit gradient of `loss_fn(out, labels).mean()` in one kernel, `mimo_input_gradient` with that `dout` — then the same one
 `mimo_fgsm_perturb` launch and `predict_uncertainties` per eps.
 
-MC-dropout ensembles are rejected: the reference draws fresh dropout masks in each of its three forwards (clean, backward,
-perturbed), so there is no gradient "at the same network" to be in parity with.
+MC-dropout ensembles (`monte_carlo_steps = M > 0`, the reference's ``--monte_carlo_steps``) are opt-in: without
+`mc_dropout=True` they are refused as before — the reference draws fresh dropout masks in each of its forwards, so a sweep has
+no bit parity to be held to.  The gradient GIVEN the masks is deterministic, and that is what `mc_dropout=True` computes:
+
+* the loss of the reference's script is the mean NLL over the concatenated axis of all M * S_total outputs, each pass with
+  its own mask draw; the gradient here is
+
+      d/d image of (1 / (M * S_total)) * sum_member sum_m sum_s loss_{m,s}
+
+  taken ONCE at the clean image, with one draw of M mask sets per member, and it serves every eps of the sweep.  The
+  reference redraws per eps; the draw does not depend on eps, so each eps's result has the same distribution either way;
+* per member the M passes are stacked on the batch axis, pass-major as in `EnsembleModule.forward`, in chunks of
+  `ensemble.max_samples_per_launch // B` passes: one masked eval-mode forward, the loss, and `mimo_input_gradient_mc`, whose
+  first-layer fold sums the chunk's passes in a fixed order (no atomics: two calls with the same masks give the same bits).
+  A chunk of k passes gets dloss[s] = k / (M * S_total) — the engine's per-subnetwork loss is already the mean over the
+  chunk's k * B samples.  The first chunk of member 0 assigns, every other chunk accumulates;
+* the masks come from the engine's generator (keyed by torch's CUDA generator: `torch.cuda.manual_seed` replays a
+  gradient), or from `mask_override` / `elem_mask_override` with rows for all M * B samples, sliced per chunk;
+* the perturbed predictions per eps are the ordinary MC forward of the ensemble, with fresh masks;
+* BatchNorm uses its running statistics throughout.
+
+Still refused: an `EvidentialUnetModel` with active dropout (the reference's evidential scripts have no MC mode), and the
+precisions other than fp32 / split16.
 """
 from __future__ import annotations
 
@@ -54,7 +75,7 @@ def _validate_epsilons(epsilons: Sequence[float]) -> Tuple[float, ...]:
     return eps
 
 
-def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
+def _validate(ensemble, epsilons: Sequence[float], mc_dropout: bool = False) -> Tuple[float, ...]:
     """Everything that can be refused is refused here, before anything touches the GPU."""
     if _is_evidential(ensemble):  # the model itself, not an ensemble of it
         ensemble.require_eval("fgsm_sweep")
@@ -62,7 +83,7 @@ def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
             raise NotImplementedError(f"fgsm_sweep: the input gradient is implemented for the fp32 and split16 precisions, not "
                                       f"{ensemble.model._geom.precision!r}")
         return _validate_epsilons(epsilons)
-    if getattr(ensemble, "monte_carlo_steps", 0) > 0:
+    if getattr(ensemble, "monte_carlo_steps", 0) > 0 and not mc_dropout:
         raise NotImplementedError("fgsm_sweep: MC-dropout ensembles (monte_carlo_steps > 0) are not supported: the reference "
                                   "draws fresh dropout masks in each of its forwards, there is nothing to be in parity with")
     from .models.mimo_unet import MimoUnetModel
@@ -77,12 +98,24 @@ def _validate(ensemble, epsilons: Sequence[float]) -> Tuple[float, ...]:
     return _validate_epsilons(epsilons)
 
 
-def image_gradient(ensemble, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _mc_chunk_weights(passes: int, batch: int, max_samples_per_launch: int, s_total: int):
+    """[(m0, m1, weight)]: the passes [m0, m1) of each launch — chunks of `max_samples_per_launch // batch` passes, as
+    `EnsembleModule.forward` forms them — and the dloss entry of the chunk, (m1 - m0) / (passes * s_total): the engine's
+    per-subnetwork loss is the mean over the chunk's (m1 - m0) * batch samples, the wanted one the mean over passes * batch.
+    The weights of a subnetwork sum to 1 / s_total over the chunks."""
+    chunk = max(1, min(passes, max_samples_per_launch // max(batch, 1)))
+    return [(m0, min(passes, m0 + chunk), (min(passes, m0 + chunk) - m0) / (passes * s_total)) for m0 in range(0, passes, chunk)]
+
+
+def image_gradient(ensemble, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                   mc_dropout: bool = False) -> torch.Tensor:
     """d loss / d image [B,C,H,W] of `loss_fn(y_pred, log_param, labels)` as the reference's script forms it
     (test_nyuv2_depth.py:44-55): the mean NLL over the concatenated subnetwork axis of ALL members, i.e. a weight of
     1 / S_total on every subnetwork's mean loss.  Members are summed in list order (member 0 assigns, the others add).
-    A bare `EvidentialUnetModel`: the gradient of `loss_fn(out, labels).mean()` (`EvidentialUnetModel.image_gradient`)."""
-    _validate(ensemble, (0.0,))
+    A bare `EvidentialUnetModel`: the gradient of `loss_fn(out, labels).mean()` (`EvidentialUnetModel.image_gradient`).
+    mc_dropout=True with an ensemble of `monte_carlo_steps = M > 0`: the mean over the M * S_total outputs of M masked passes
+    per member (module docstring); with M = 0 the flag changes nothing."""
+    _validate(ensemble, (0.0,), mc_dropout)
     if _is_evidential(ensemble):
         return ensemble.image_gradient(image, label, mask)[0]
     if not image.is_cuda:
@@ -93,24 +126,51 @@ def image_gradient(ensemble, image: torch.Tensor, label: torch.Tensor, mask: Opt
     label = label.detach().to(image.device)
     mask = None if mask is None else mask.detach().to(image.device)
     dimage = torch.empty_like(image)
+    passes = getattr(ensemble, "monte_carlo_steps", 0) if mc_dropout else 0
     with torch.no_grad():
+        if passes > 0:
+            _mc_image_gradient(ensemble, image, label, mask, dimage, passes, s_total)
+            return dimage
         for i, model in enumerate(ensemble.models):
             dloss = torch.full((model.num_subnetworks,), 1.0 / s_total, device=image.device, dtype=torch.float32)
             model.model.image_gradient(image, label, mask, dloss, dimage, accumulate=i > 0)
     return dimage
 
 
+def _mc_image_gradient(ensemble, image, label, mask, dimage, passes: int, s_total: int) -> None:
+    b = image.shape[0]
+    chunks = _mc_chunk_weights(passes, b, ensemble.max_samples_per_launch, s_total)
+    first = True
+    for model in ensemble.models:
+        net = model.model
+        # tests: recorded masks for all passes x B samples, sliced per launch as EnsembleModule.forward slices them
+        recorded, recorded_elem = net.mask_override, net.elem_mask_override
+        try:
+            for m0, m1, weight in chunks:
+                if recorded is not None:
+                    net.mask_override = {j: t[m0 * b: m1 * b] for j, t in recorded.items()}
+                if recorded_elem is not None:
+                    net.elem_mask_override = {k: t[m0 * b: m1 * b] for k, t in recorded_elem.items()}
+                dloss = torch.full((model.num_subnetworks,), weight, device=image.device, dtype=torch.float32)
+                net.image_gradient(image, label, mask, dloss, dimage, accumulate=not first, passes=m1 - m0, mc_dropout=True)
+                first = False
+        finally:
+            net.mask_override, net.elem_mask_override = recorded, recorded_elem
+
+
 def fgsm_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Sequence[float] = DEFAULT_EPSILONS,
                mask: Optional[torch.Tensor] = None, clip: Optional[Tuple[float, float]] = (0.0, 1.0),
-               return_perturbed: bool = False) -> Dict[float, tuple]:
+               return_perturbed: bool = False, mc_dropout: bool = False) -> Dict[float, tuple]:
     """{eps: (mean, aleatoric_var, epistemic_var)} [B,Ct,H,W] on the device, for the image attacked with each eps
     (eps = 0 is the clamped clean image, as in the reference).  `ensemble`: an `EnsembleModule` or a bare `EvidentialUnetModel`.  image [B,C,H,W], label [B,Ct,H,W], mask [B,1,H,W] or None
     (weights the loss the gradient is taken of).  clip: the range the perturbed image is clamped to; None = no clamp.
     return_perturbed: the tuples get the perturbed image [B,C,H,W] as a fourth entry.
+    mc_dropout: accept an MC-dropout ensemble (`monte_carlo_steps > 0`): one gradient over its masked passes at the clean
+    image, then the ordinary MC forward per eps with fresh masks (module docstring).
     The members' `.grad`, BatchNorm buffers and train / eval flags are left as they were."""
-    eps = _validate(ensemble, epsilons)
+    eps = _validate(ensemble, epsilons, mc_dropout)
     from .engine import fgsm_perturb
-    dimage = image_gradient(ensemble, image, label, mask)
+    dimage = image_gradient(ensemble, image, label, mask, mc_dropout=mc_dropout)
     lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
     perturbed = fgsm_perturb(image.detach(), dimage, eps, lo, hi)
     if _is_evidential(ensemble):
@@ -133,10 +193,12 @@ def fgsm_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Seq
 
 class RobustnessEvaluator:
     """One `UncertaintyEvaluator` per noise level, fed by `fgsm_sweep`: the sparsification and calibration tables of
-    test_nyuv2_depth.py:215-234 for every eps of its sweep (:192).  `evaluator_kwargs` go to every UncertaintyEvaluator."""
+    test_nyuv2_depth.py:215-234 for every eps of its sweep (:192).  `evaluator_kwargs` go to every UncertaintyEvaluator.
+    mc_dropout: handed to `fgsm_sweep` (MC-dropout ensembles)."""
 
-    def __init__(self, epsilons: Sequence[float] = DEFAULT_EPSILONS, **evaluator_kwargs):
+    def __init__(self, epsilons: Sequence[float] = DEFAULT_EPSILONS, mc_dropout: bool = False, **evaluator_kwargs):
         self.epsilons = tuple(float(e) for e in epsilons)
+        self.mc_dropout = bool(mc_dropout)
         if not self.epsilons or any(not e >= 0.0 for e in self.epsilons):
             raise NotImplementedError(f"RobustnessEvaluator: epsilons must be non-negative, got {self.epsilons}")
         if len(set(self.epsilons)) != len(self.epsilons):
@@ -148,7 +210,7 @@ class RobustnessEvaluator:
             ev.reset()
 
     def update_from(self, ensemble, image, label, mask=None) -> None:
-        sweep = fgsm_sweep(ensemble, image, label, self.epsilons, mask=mask)
+        sweep = fgsm_sweep(ensemble, image, label, self.epsilons, mask=mask, mc_dropout=self.mc_dropout)
         for e, (mean, av, ev) in sweep.items():
             self.evaluators[e].update(mean, av, ev, label.to(mean.device), None if mask is None else mask.to(mean.device))
 

@@ -46,6 +46,11 @@ int unpack_dx_launch(const void* dxpad, int dt, int ldp, int N, int S, int s, in
 // the image that repeat_subnetworks broadcast (utils.py:51-61) — mimo_input_gradient launches it once per subnetwork, in
 // the order s = S-1 ... 0, instead of S unpack_dx launches and a sum over the subnetwork axis (fp32 storage)
 int fold_image_grad_launch(const float* dxpad, int ldp, int N, int C, int H, int W, float* dimage, int accumulate, hipStream_t st);
+// dimage[b][c][y][x] (=|+=) sum_{m = 0 .. R-1} fold(dxpad)[m * B + b][y][x][c], added in that order with fp32 adds: R
+// Monte-Carlo passes of the same B images stacked pass-major on the batch axis (EnsembleModule.forward's layout), folded and
+// summed in one pass — mimo_input_gradient_mc.  R = 1: the bits of fold_image_grad_launch.
+int fold_image_grad_mc_launch(const float* dxpad, int ldp, int B, int R, int C, int H, int W, float* dimage, int accumulate,
+                              hipStream_t st);
 
 // ---- BatchNorm + ReLU (+ Dropout2d) forward ---------------------------------------------
 // training, more than kColsumMaxRows partial rows: sums = rowsum of the conv epilogue partials ([chunks][2*cout_pad]).

@@ -432,6 +432,41 @@ int fold_image_grad_launch(const float* dxpad, int ldp, int N, int C, int H, int
   return MIMO_OK;
 }
 
+// The same fold for R Monte-Carlo passes stacked pass-major on the batch axis (pass m, image b at row m * B + b of dxpad):
+// one thread per pixel of the B images, the R folded float4 reads (each coalesced along x like the one above) added in the
+// fixed order m = 0 ... R-1 in fp32 registers, one store per channel.  Pass 0 assigns (or adds to the stored value), so R = 1
+// gives the bits of fold_image_grad_kernel, -0 included.
+__global__ void fold_image_grad_mc_kernel(const float* __restrict__ dxpad, int ldp, int B, int R, int C, int H, int W,
+                                          float* __restrict__ dimage, int accumulate) {
+  const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW);
+    const int yx = (int)(i - (int64_t)b * HW);
+    const int y = yx / W, x = yx - y * W;
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      float4 s = fold_read(dxpad, ldp, b, y, x, H, W, c0);
+      float* d = dimage + ((int64_t)b * C + c0) * HW + yx;
+      if (accumulate) {
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4 && c0 + j < C; ++j) o[j] = d[j * HW];
+        s = f4add(make_float4(o[0], o[1], o[2], o[3]), s);
+      }
+      for (int m = 1; m < R; ++m) s = f4add(s, fold_read(dxpad, ldp, m * B + b, y, x, H, W, c0));
+      const float vv[4] = {s.x, s.y, s.z, s.w};
+      for (int j = 0; j < 4 && c0 + j < C; ++j) d[j * HW] = vv[j];
+    }
+  }
+}
+
+int fold_image_grad_mc_launch(const float* dxpad, int ldp, int B, int R, int C, int H, int W, float* dimage, int accumulate,
+                              hipStream_t st) {
+  const int64_t total = (int64_t)B * H * W;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
+  hipLaunchKernelGGL(fold_image_grad_mc_kernel, dim3(blocks), dim3(256), 0, st, dxpad, ldp, B, R, C, H, W, dimage, accumulate);
+  MIMO_KERNEL_CHECK();
+  return MIMO_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // BatchNorm statistics -> scale/shift
 // ---------------------------------------------------------------------------------------

@@ -929,4 +929,22 @@ int mimo_op_fold_image_grad(const float* dxpad, int32_t ldp, int32_t n, int32_t 
   return MIMO_OK;
 }
 
+int mimo_op_fold_image_grad_mc(const float* dxpad, int32_t ldp, int32_t n, int32_t replicas, int32_t c, int32_t h, int32_t w,
+                               float* dimage, int32_t accumulate, mimo_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* who = "mimo_op_fold_image_grad_mc";
+  if (c < 1 || bad_dims(who, n, h, w, 8) || bad_slice(who, "dxpad", ldp, 0, round_up(c, 4))) return MIMO_ERR_INVALID;
+  if (replicas < 1 || n % replicas != 0) {
+    set_error("%s: replicas %d does not divide n %d", who, replicas, n);
+    return MIMO_ERR_INVALID;
+  }
+  if (!dxpad || !dimage) {
+    set_error("%s: a missing tensor", who);
+    return MIMO_ERR_INVALID;
+  }
+  MIMO_TRY(fold_image_grad_mc_launch(dxpad, ldp, n / replicas, replicas, c, h, w, dimage, accumulate, st));
+  MIMO_HIP_CHECK(hipStreamSynchronize(st));
+  return MIMO_OK;
+}
+
 }  // extern "C"

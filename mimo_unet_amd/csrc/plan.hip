@@ -173,6 +173,9 @@ struct BwdCall {
   bool ig = false;
   float* dimage = nullptr;  // ... the image gradient [N,Ci,H,W] the encoders' first-layer data gradients are folded into
   bool accumulate = false;  // ... the first fold adds to what is there
+  // mimo_input_gradient_mc: the plan batch holds `replicas` Monte-Carlo passes of N / replicas images, pass-major; dimage is
+  // [N / replicas,Ci,H,W] and each encoder's fold sums its passes (0: mimo_input_gradient, dimage is [N,Ci,H,W])
+  int replicas = 0;
 };
 
 // The dz buffers between the caller's stream (BatchNorm backward writes dz, the data gradient reads it) and the side stream
@@ -1909,7 +1912,13 @@ struct mimo_plan {
 
   // The 8 stages of the backward with the data-gradient chain only, the S first-layer data gradients folded and summed into
   // dimage [N,Ci,H,W] in the fixed order s = S-1, S-2, ..., 0 (fp32 adds; accumulate: on top of the caller's values).
-  int input_gradient(const float* dout, const float* dloss, float* dimage, int accumulate, hipStream_t st) {
+  // replicas > 0 (mimo_input_gradient_mc): the batch is `replicas` passes of N / replicas images, pass-major; dimage
+  // [N / replicas,Ci,H,W] receives, per encoder, the sum over its passes in the order m = 0 ... replicas-1.
+  int input_gradient(const float* dout, const float* dloss, float* dimage, int accumulate, int replicas, hipStream_t st) {
+    if (replicas < 0 || (replicas > 0 && N % replicas != 0)) {
+      set_error("mimo_input_gradient_mc: replicas %d does not divide the plan batch %d (need replicas >= 1)", replicas, N);
+      return MIMO_ERR_INVALID;
+    }
     if (cfg.inference_only == 1 || !s_zero) {
       set_error("mimo_input_gradient: inference-only plan (no buffers for a backward)");
       return MIMO_ERR_STATE;
@@ -1943,7 +1952,7 @@ struct mimo_plan {
       MIMO_TRY(pack_jobs_launch(pack_jobs + n_fwd_jobs, n_all_jobs - n_fwd_jobs, pack_max_total, params, st));
       dgrad_version = derived_version;
     }
-    const BwdCall call{dout, dloss, nullptr, true, dimage, accumulate != 0};
+    const BwdCall call{dout, dloss, nullptr, true, dimage, accumulate != 0, replicas};
     for (int stage = 0; stage < kBwdStages; ++stage) MIMO_TRY(backward_stage(stage, call, st));
     return MIMO_OK;
   }
@@ -1952,8 +1961,12 @@ struct mimo_plan {
     for (int s = S - 1; s >= 0; --s) MIMO_TRY(dc_backward(down1[s], true, call, st));
     for (int s = S - 1; s >= 0; --s) {
       MIMO_TRY(dc_backward(enc_in[s], call.dx != nullptr || call.ig, call, st));
-      if (call.ig)  // s = S-1 assigns (or adds to the caller's values), S-2 ... 0 add: s_dxpadB is reused per encoder
-        MIMO_TRY(fold_image_grad_launch(s_dxpadB, Ci_p, N, Ci, H, W, call.dimage, (s < S - 1 || call.accumulate) ? 1 : 0, st));
+      // s = S-1 assigns (or adds to the caller's values), S-2 ... 0 add: s_dxpadB is reused per encoder
+      const int acc = (s < S - 1 || call.accumulate) ? 1 : 0;
+      if (call.ig && call.replicas > 0)
+        MIMO_TRY(fold_image_grad_mc_launch(s_dxpadB, Ci_p, N / call.replicas, call.replicas, Ci, H, W, call.dimage, acc, st));
+      else if (call.ig)
+        MIMO_TRY(fold_image_grad_launch(s_dxpadB, Ci_p, N, Ci, H, W, call.dimage, acc, st));
       else if (call.dx)
         MIMO_TRY(unpack_dx_launch(s_dxpadB, this->st, Ci_p, N, S, s, Ci, H, W, call.dx, st));
     }
@@ -2164,7 +2177,20 @@ int mimo_input_gradient(mimo_plan* plan, const float* dout, const float* dloss, 
     set_error("mimo_input_gradient: null plan");
     return MIMO_ERR_INVALID;
   }
-  return plan->input_gradient(dout, dloss, dimage, accumulate, (hipStream_t)stream);
+  return plan->input_gradient(dout, dloss, dimage, accumulate, 0, (hipStream_t)stream);
+}
+
+int mimo_input_gradient_mc(mimo_plan* plan, const float* dout, const float* dloss, float* dimage, int accumulate, int replicas,
+                           mimo_stream stream) {
+  if (!plan) {
+    set_error("mimo_input_gradient_mc: null plan");
+    return MIMO_ERR_INVALID;
+  }
+  if (replicas < 1) {
+    set_error("mimo_input_gradient_mc: replicas %d (need replicas >= 1)", replicas);
+    return MIMO_ERR_INVALID;
+  }
+  return plan->input_gradient(dout, dloss, dimage, accumulate, replicas, (hipStream_t)stream);
 }
 
 int64_t mimo_plan_encoder_param_floats(const mimo_plan* plan) { return plan ? plan->encoder_param_floats : 0; }

@@ -224,6 +224,20 @@ class Plan:
         L.check(self.lib.mimo_input_gradient(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
                                              int(bool(accumulate)), L.current_stream()), "mimo_input_gradient")
 
+    def input_gradient_mc(self, dout: Optional[torch.Tensor], dloss: Optional[torch.Tensor], dimage: torch.Tensor,
+                          accumulate: bool = False, replicas: int = 1) -> None:
+        """`input_gradient` after a forward whose batch holds `replicas` MC-dropout passes of the same batch / replicas
+        images, stacked pass-major (pass m, image b at row m * B + b): dimage [B,Ci,H,W] receives the passes' gradients
+        summed in the fixed order m = 0 ... replicas-1 per subnetwork (mimo_input_gradient_mc)."""
+        g = self.geom
+        replicas = int(replicas)
+        if replicas < 1 or self.batch % replicas != 0:
+            raise ValueError(f"input_gradient_mc: replicas {replicas} does not divide the plan batch {self.batch}")
+        assert dimage.is_cuda and dimage.dtype == torch.float32 and dimage.is_contiguous()
+        assert tuple(dimage.shape) == (self.batch // replicas, g.in_channels, self.height, self.width), tuple(dimage.shape)
+        L.check(self.lib.mimo_input_gradient_mc(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
+                                                int(bool(accumulate)), replicas, L.current_stream()), "mimo_input_gradient_mc")
+
     PROF_KINDS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "bn_relu_fwd", "bn_bwd_reduce", "bn_bwd_apply",
                   "upcat_fwd", "up_bwd", "pool_bwd", "head_fwd", "head_bwd")
     PROF_TIERS = 5  # resolution levels: 0 = H x W ... 4 = H/16 x W/16

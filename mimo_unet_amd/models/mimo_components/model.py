@@ -525,13 +525,26 @@ class MimoUNet(nn.Module):
         return self._call(image, label, mask, perms)
 
     def image_gradient(self, image: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor], dloss: torch.Tensor,
-                       dimage: torch.Tensor, accumulate: bool = False):
+                       dimage: torch.Tensor, accumulate: bool = False, passes: int = 1, mc_dropout: bool = False):
         """Evaluation-grade input gradient (mimo_input_gradient): eval-mode forward of `image` [B,C,H,W] broadcast to the
         S subnetworks, the per-subnetwork mean NLL against `label` [B,Ct,H,W], and d sum_s(dloss[s] * loss[s]) / d image
         written (accumulate: added) into `dimage` [B,C,H,W].  Touches no `.grad`, no BatchNorm buffer, no autograd graph.
-        Returns (logits [B,S,Co,H,W], loss [S])."""
-        if self._bn_training() or any(d.p > 0.0 and d.training for d in self._dropout_modules()):
+        Returns (logits [B,S,Co,H,W], loss [S]).
+        mc_dropout=True (MC-dropout ensembles): active dropout modules are accepted — BatchNorm in training mode is still
+        refused — and `passes` stochastic passes run as one batch of passes * B samples, pass-major (pass m, image i at row
+        m * B + i, the layout of `EnsembleModule.forward`).  Image, label and mask are repeated `passes` times on the batch
+        axis in torch: they are small next to the activations, and the engine reads them once.  The dropout multipliers
+        come from the engine's generator, or from `mask_override` / `elem_mask_override` with rows for passes * B samples.
+        loss[s] is then the mean over the passes * B samples, and `dimage` [B,C,H,W] receives the passes' gradients summed
+        in the fixed order m = 0 ... passes-1 (mimo_input_gradient_mc); the logits returned are [passes * B,S,Co,H,W]."""
+        if not mc_dropout and (self._bn_training() or any(d.p > 0.0 and d.training for d in self._dropout_modules())):
             raise NotImplementedError("MimoUNet.image_gradient: eval mode only (BatchNorm on running statistics, dropout off)")
+        if self._bn_training():
+            raise NotImplementedError("MimoUNet.image_gradient: BatchNorm must be in eval mode (running statistics), also "
+                                      "with mc_dropout")
+        passes = int(passes)
+        if passes < 1 or (passes > 1 and not mc_dropout):
+            raise ValueError(f"MimoUNet.image_gradient: passes = {passes} needs mc_dropout=True and passes >= 1")
         image = image.contiguous().float()
         if image.dim() != 4 or image.shape[1] != self.in_channels:
             raise ValueError(f"expected [B,{self.in_channels},H,W], got {tuple(image.shape)}")
@@ -539,16 +552,34 @@ class MimoUNet(nn.Module):
         mask = None if mask is None else mask.contiguous().float()
         dloss = dloss.to(device=image.device, dtype=torch.float32).contiguous()
         assert dloss.shape == (self.num_subnetworks,)
+        if passes > 1:
+            image, label = image.repeat(passes, 1, 1, 1), label.repeat(passes, 1, 1, 1)
+            mask = None if mask is None else mask.repeat(passes, 1, 1, 1)
         plan = self._plan_for(image, None, grad_only=True)
-        out = torch.empty(image.shape[0], self.num_subnetworks, self.out_channels, plan.height, plan.width, device=image.device,
+        n = image.shape[0]
+        masks = elem_masks = rng = None
+        if mc_dropout:
+            rng = self._engine_rng_sites(image.device)
+            if rng is None:
+                masks = self._dropout_masks(n, image.device)
+                elem_masks = self._elem_dropout_masks(n, image.shape[-2], image.shape[-1], image.device)
+                for i, m in enumerate(masks or ()):  # (the engine reads n rows of every mask it is handed)
+                    if m is not None and tuple(m.shape) != (n, plan.double_conv_channels[i]):
+                        raise ValueError(f"Dropout2d mask of site {i}: expected {(n, plan.double_conv_channels[i])} "
+                                         f"(passes * B rows), got {tuple(m.shape)}")
+        out = torch.empty(n, self.num_subnetworks, self.out_channels, plan.height, plan.width, device=image.device,
                           dtype=torch.float32)
         loss = torch.empty(self.num_subnetworks, device=image.device, dtype=torch.float32)
         plan.bind(self._flat_params, None, self._flat_buffers)
-        plan.forward(image, out, training=False, broadcast_subnetworks=True, no_grad=False, param_version=self._param_version())
+        plan.forward(image, out, training=False, broadcast_subnetworks=True, masks=masks, elem_masks=elem_masks, no_grad=False,
+                     param_version=self._param_version(), rng=rng)
         plan.loss_forward(label, mask, None, loss)
-        plan.input_gradient(None, dloss, dimage, accumulate)
+        if mc_dropout:
+            plan.input_gradient_mc(None, dloss, dimage, accumulate, passes)
+        else:
+            plan.input_gradient(None, dloss, dimage, accumulate)
         plan.generation += 1
-        self._inference_keep = (image, label, mask, dloss, out)  # the plan still points at these
+        self._inference_keep = (image, label, mask, dloss, out, masks, elem_masks)  # the plan still points at these
         return out, loss
 
     def image_gradient_from_dout(self, image: torch.Tensor, dout_fn, dimage: torch.Tensor, accumulate: bool = False):
