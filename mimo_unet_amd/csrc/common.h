@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/mimo_hip.h"
+#include "pack_layout.h"
 #include "tile_sched.h"
 
 namespace mimo {
@@ -34,9 +35,6 @@ static inline int pad_channels(int c) { return round_up(c, 8); }
 
 constexpr int kWave = 64;
 
-// Element type of the activation-like tensors in HBM (conv outputs, activations and their gradients): fp32, or bf16 /
-// fp16 in the 16-bit storage modes MIMO_PREC_BF16_MIXED / MIMO_PREC_FP16_MIXED.  Arithmetic is always fp32.
-enum StoreType { ST_F32 = 0, ST_BF16 = 1, ST_F16 = 2 };
 static inline int store_bytes(int dt) { return dt == ST_F32 ? 4 : 2; }
 
 // Workgroups are dealt round-robin to the 8 XCDs (each with a private L2) in linear-id order.  This maps a
@@ -119,8 +117,6 @@ int wgrad_thin_launch(const float* x, int ldx, const float* dz, int lddz, int N,
 // mode 0: split16 data gradient (bf16 pairs, pre-split input); 1: split16 forward (fp16 pairs);
 // 2: bf16 forward (one MFMA per product); 3: bf16 data gradient
 int conv3x3_bf16x3_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t stream);
-int pack_weights_bf16x3_launch(const float* w, void* dst, int f16, int cout, int cin, int rows_pad, int cols,
-                               const int* row_map, const int* col_map, int transposed, hipStream_t stream, int pair = 0);
 // 1 when conv3x3_bf16x3_launch(mode) runs a layer with cin_p input channels and Ho x Wo outputs on the tap-paired
 // instance (last chunk <= 16 channels: two taps per MFMA); the weights must then be packed with pair = 1
 int conv3x3_pair_tail(int mode, int cin_p, int Ho, int Wo);
@@ -128,12 +124,8 @@ int conv3x3_pair_tail(int mode, int cin_p, int Ho, int Wo);
 // the padded Cout; data gradient: the layer's padded input channels); returns the packed weight rows, 0 = the layer
 // stays on conv_bf16x3.hip.  The packer and the launch must agree (ConvLaunch::wide).
 int conv3x3_wide_rows(int mode, int N, int cin_p, int rows, int Ho, int Wo);
-size_t conv3x3_wide_weight_elems(int cin_p, int rows_pad);  // 16-bit elements of the packed image
 int conv3x3_wide_stat_rows();
 int conv3x3_wide_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t stream);
-int pack_weights_wide_launch(const float* w, void* dst, int f16, int cout, int cin, int rows_pad, int cols,
-                             const int* row_map, const int* col_map, int nrows_map, int transposed, hipStream_t stream,
-                             int single = 0);
 int conv3x3_pick_nfrag(int cout);            // fragments (of 16 output channels) per workgroup
 int conv3x3_cout_pad(int cout);              // packed weight rows for that choice
 int conv3x3_stat_rows(int N, int Ho, int Wo);  // spatial workgroups == partial-stat rows
@@ -202,30 +194,12 @@ int wgrad_reduce_launch(const float* partial, int splits, int cin_pad, int cout_
                         int cin_p, int cin, int cout, float* dw, hipStream_t stream, const float* dz_absmax = nullptr,
                         int dz_absmax_n = 0, hipEvent_t done = nullptr);  // done: recorded when the reduction completes
 
-// All weight repacks of a step in ONE launch (a per-layer launch each cost more in dispatch gaps than in
-// work): a device table of jobs, blockIdx.y = job.  kind 0: fp32 [tap][rows_pad][cols]; 1 / 2: fp16 / bf16
-// (hi, lo) pairs [chunk][tap][rows_pad][hi 32 | lo 32]; 3 / 4: fp16 / bf16 pairs in the wide kernel's layout
-// [16-channel chunk][tap][rows_pad][hi 16 | lo 16]; 5 / 6: fp16 (x 2^8) / bf16 single values in the wide kernel's
-// 16-bit storage layout [32-channel chunk][tap][rows_pad][32] (kinds 3-6: rows beyond map_rows are zero); bias_n > 0
-// additionally copies the layer's bias.
-struct PackJob {
-  int64_t w_off, bias_off;  // float offsets into the bound parameter buffer
-  void* dst;
-  float* bias_dst;
-  const int *row_map, *col_map;
-  int kind, cout, cin, rows_pad, cols, transposed, total, bias_n;
-  int pair;  // kind 1 / 2: tap-paired image of the last chunk (conv3x3_pair_tail)
-  int map_rows;  // kind 3 / 4: entries of row_map (rows_pad may exceed it)
-  unsigned* wmax;  // fp16 kinds (1, 3, 5): max |w| of the layer at this pack, float bits (wabsmax_jobs_launch); image scale = w16_scale
-};
+// All weight repacks of a step in ONE launch (a per-layer launch each cost more in dispatch gaps than in work): a device
+// table of PackJob records (pack_layout.h: the layouts and the builder of a job), blockIdx.y = job.
 int pack_jobs_launch(const PackJob* jobs_dev, int njobs, int max_total, const float* params, hipStream_t stream);
 // max |w| of every job with a wmax word (run in front of pack_jobs_launch, on words the caller has zeroed: the maximum of
 // THIS pack).  status != nullptr: bit 0 (kStatusFwdStats) is OR-ed in when a maximum is not finite
 int wabsmax_jobs_launch(const PackJob* jobs_dev, int njobs, int max_total, const float* params, hipStream_t stream,
                         int* status = nullptr);
-
-// weight packing: torch OIHW -> [9][rows_pad][cols] (see conv3x3.hip)
-int pack_weights_launch(const float* w, float* dst, int cout, int cin, int rows_pad, int cols,
-                        const int* row_map, const int* col_map, int transposed, hipStream_t stream);
 
 }  // namespace mimo

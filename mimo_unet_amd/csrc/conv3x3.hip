@@ -513,39 +513,4 @@ int wgrad_reduce_launch(const float* partial, int splits, int cin_pad, int cout_
   return MIMO_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// weight packing: torch OIHW -> dst[tap][row][col]
-//   transposed == 0 (forward):  row -> co = row_map[row], col -> ci = col_map[col], tap = kh*3+kw
-//   transposed == 1 (dgrad):    row -> ci = row_map[row], col -> co = col_map[col], tap = (2-kh)*3+(2-kw)
-// map value -1 = zero padding.
-// ---------------------------------------------------------------------------------------
-__global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ dst, int cout, int cin,
-                                    int rows_pad, int cols, const int* __restrict__ row_map,
-                                    const int* __restrict__ col_map, int transposed) {
-  const int total = 9 * rows_pad * cols;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int col = i % cols;
-    const int rest = i / cols;
-    const int row = rest % rows_pad, tap = rest / rows_pad;
-    const int rm = row_map[row], cm = col_map[col];
-    float v = 0.f;
-    if (rm >= 0 && cm >= 0) {
-      const int co = transposed ? cm : rm, ci = transposed ? rm : cm;
-      const int kh = transposed ? 2 - tap / 3 : tap / 3, kw = transposed ? 2 - tap % 3 : tap % 3;
-      v = w[(((size_t)co * cin + ci) * 3 + kh) * 3 + kw];
-    }
-    dst[i] = v;
-  }
-}
-
-int pack_weights_launch(const float* w, float* dst, int cout, int cin, int rows_pad, int cols, const int* row_map,
-                        const int* col_map, int transposed, hipStream_t stream) {
-  const int total = 9 * rows_pad * cols;
-  const int blocks = min(ceil_div(total, 256), 4096);
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, stream, w, dst, cout, cin, rows_pad, cols,
-                     row_map, col_map, transposed);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
 }  // namespace mimo

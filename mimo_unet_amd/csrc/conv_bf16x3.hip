@@ -1183,8 +1183,10 @@ int conv3x3_bf16x3_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t 
 }
 
 // ---------------------------------------------------------------------------------------
-// weight packing for the split kernel: torch OIHW -> [chunk][tap][row][hi 32 | lo 32] bf16
-// (row/col maps and the transposed flag as in pack_weights_kernel, conv3x3.hip)
+// weight packing: torch OIHW -> every layout the convolutions read (PackKind, pack_layout.h)
+//   transposed == 0 (forward):  row -> co = row_map[row], col -> ci = col_map[col], tap = kh*3+kw
+//   transposed == 1 (dgrad):    row -> ci = row_map[row], col -> co = col_map[col], tap = (2-kh)*3+(2-kw)
+// map value -1 = zero padding.
 // ---------------------------------------------------------------------------------------
 // paired last chunk (conv3x3_pair_tail): tap (row, kw) of channel k < 16 -> of the chunk's nine weight slots, slot kw
 // for rows 0 (K lane k) and 1 (K lane 16 + k), slot 3 + kw for row 2 (K lane k).  K lanes 16-31 of slots 3-5 and
@@ -1195,67 +1197,30 @@ __device__ __forceinline__ void pair_slot(int tap, int k, int* slot, int* kk) {
   *kk = k + (row == 1 ? 16 : 0);
 }
 
-template <bool F16>
-__global__ void pack_weights_bf16x3_kernel(const float* __restrict__ w, typename Elem<F16>::T* __restrict__ dst, int cout,
-                                           int cin, int rows_pad, int cols, int nchunks, const int* __restrict__ row_map,
-                                           const int* __restrict__ col_map, int transposed, int pair) {
-  typedef typename Elem<F16>::T ET;
-  const int total = nchunks * 9 * rows_pad * 32;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int k = i & 31;
-    int rest = i >> 5;
-    const int row = rest % rows_pad;
-    rest /= rows_pad;
-    const int tap = rest % 9, chunk = rest / 9;
-    const int col = chunk * 32 + k;
-    float v = 0.f;
-    if (col < cols) {
-      const int rm = row_map[row], cm = col_map[col];
-      if (rm >= 0 && cm >= 0) {
-        const int co = transposed ? cm : rm, ci = transposed ? rm : cm;
-        const int kh = transposed ? 2 - tap / 3 : tap / 3, kw = transposed ? 2 - tap % 3 : tap % 3;
-        v = w[(((size_t)co * cin + ci) * 3 + kh) * 3 + kw];
-      }
-    }
-    if (F16) v *= kF16WeightScale;
-    const ET hi = (ET)v;
-    const ET lo = (ET)(v - (float)hi);
-    int slot = tap, kk = k;
-    if (pair && chunk == nchunks - 1) {
-      if (k >= 16) continue;  // K lanes 16-31 of the paired image belong to the odd taps of channels 0-15
-      pair_slot(tap, k, &slot, &kk);
-    }
-    ET* d = dst + (((size_t)chunk * 9 + slot) * rows_pad + row) * 64;
-    d[kk] = hi;
-    d[32 + kk] = lo;
-  }
-}
-
-// one launch for every repack of a step (PackJob, common.h); element formulas as in the kernels above / in
-// pack_weights_kernel (conv3x3.hip)
+// one launch for every repack of a step (PackJob, pack_layout.h)
 __global__ void pack_jobs_kernel(const PackJob* __restrict__ jobs, const float* __restrict__ params) {
   const PackJob j = jobs[blockIdx.y];
   const float* w = params + j.w_off;
-  const float wscale = j.wmax ? w16_scale(*j.wmax, false) : kF16WeightScale;  // fp16 kinds (1, 3, 5)
+  const float wscale = j.wmax ? w16_scale(*j.wmax, false) : kF16WeightScale;  // fp16 kinds
   if (blockIdx.x == 0 && j.bias_n > 0)
     for (int i = threadIdx.x; i < j.bias_n; i += blockDim.x) j.bias_dst[i] = params[j.bias_off + i];
   // One thread per (row, column) = one (output channel, input channel) pair: its nine taps are 36 contiguous bytes
   // of the OIHW tensor, so a wave reads one contiguous span (the tap-major order of round 1 read 4 of every 36
   // bytes per pass: 113 us per step for 60 MB of weights); the nine stores per thread are coalesced across the wave
   // (consecutive columns of one tap).
-  const int per_tap = j.total / 9;  // elements of one tap: kind 0: rows_pad * cols; else chunks * rows_pad * 32
+  const int per_tap = j.total / 9;  // weights of one tap (pack::total): PK_F32: rows_pad * cols; else chunks * rows_pad * chunk width
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per_tap; i += gridDim.x * blockDim.x) {
     int row, col, k = 0, chunk = 0;
-    if (j.kind == 0) {
+    if (j.kind == PK_F32) {
       col = i % j.cols;
       row = i / j.cols;
-    } else if (j.kind >= 5) {  // wide layout, 16-bit storage modes: 32-channel chunks of single values
+    } else if (j.kind >= PK_WIDE_F16) {  // wide layout, 16-bit storage modes: 32-channel chunks of single values
       k = i & 31;
       const int rest = i >> 5;
       row = rest % j.rows_pad;
       chunk = rest / j.rows_pad;
       col = chunk * 32 + k;
-    } else if (j.kind >= 3) {  // wide layout: 16-channel chunks
+    } else if (j.kind >= PK_WIDE_F16_PAIR) {  // wide layout: 16-channel chunks
       k = i & 15;
       const int rest = i >> 4;
       row = rest % j.rows_pad;
@@ -1271,7 +1236,7 @@ __global__ void pack_jobs_kernel(const PackJob* __restrict__ jobs, const float* 
     float v[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) v[t] = 0.f;
-    if (col < j.cols && (j.kind < 3 || row < j.map_rows)) {
+    if (col < j.cols && (j.kind < PK_WIDE_F16_PAIR || row < j.map_rows)) {
       const int rm = j.row_map[row], cm = j.col_map[col];
       if (rm >= 0 && cm >= 0) {
         const int co = j.transposed ? cm : rm, ci = j.transposed ? rm : cm;
@@ -1280,31 +1245,31 @@ __global__ void pack_jobs_kernel(const PackJob* __restrict__ jobs, const float* 
         for (int t = 0; t < 9; ++t) v[t] = src[j.transposed ? 8 - t : t];  // transposed: taps flipped (kh, kw -> 2-kh, 2-kw)
       }
     }
-    const bool paired = (j.kind == 1 || j.kind == 2) && j.pair && chunk == (j.cols + 31) / 32 - 1;
+    const bool paired = (j.kind == PK_F16_PAIR || j.kind == PK_BF16_PAIR) && j.pair && chunk == (j.cols + 31) / 32 - 1;
     if (paired && k >= 16) continue;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const float x = v[tap];
       int slot = tap, kk = k;
       if (paired) pair_slot(tap, k, &slot, &kk);
-      if (j.kind == 0) {
+      if (j.kind == PK_F32) {
         reinterpret_cast<float*>(j.dst)[((size_t)tap * j.rows_pad + row) * j.cols + col] = x;
-      } else if (j.kind == 5) {
+      } else if (j.kind == PK_WIDE_F16) {
         reinterpret_cast<_Float16*>(j.dst)[(((size_t)chunk * 9 + tap) * j.rows_pad + row) * 32 + k] = (_Float16)(x * wscale);
-      } else if (j.kind == 6) {
+      } else if (j.kind == PK_WIDE_BF16) {
         reinterpret_cast<__bf16*>(j.dst)[(((size_t)chunk * 9 + tap) * j.rows_pad + row) * 32 + k] = (__bf16)x;
-      } else if (j.kind == 3) {
+      } else if (j.kind == PK_WIDE_F16_PAIR) {
         const float xs = x * wscale;
         const _Float16 hi = (_Float16)xs, lo = (_Float16)(xs - (float)hi);
         _Float16* d = reinterpret_cast<_Float16*>(j.dst) + (((size_t)chunk * 9 + tap) * j.rows_pad + row) * 32;
         d[k] = hi;
         d[16 + k] = lo;
-      } else if (j.kind == 4) {
+      } else if (j.kind == PK_WIDE_BF16_PAIR) {
         const __bf16 hi = (__bf16)x, lo = (__bf16)(x - (float)hi);
         __bf16* d = reinterpret_cast<__bf16*>(j.dst) + (((size_t)chunk * 9 + tap) * j.rows_pad + row) * 32;
         d[k] = hi;
         d[16 + k] = lo;
-      } else if (j.kind == 1) {
+      } else if (j.kind == PK_F16_PAIR) {
         const float xs = x * wscale;
         const _Float16 hi = (_Float16)xs, lo = (_Float16)(xs - (float)hi);
         _Float16* d = reinterpret_cast<_Float16*>(j.dst) + (((size_t)chunk * 9 + slot) * j.rows_pad + row) * 64;
@@ -1358,21 +1323,6 @@ int pack_jobs_launch(const PackJob* jobs_dev, int njobs, int max_total, const fl
   if (njobs <= 0) return MIMO_OK;
   const int gx = max(1, min(ceil_div(max_total / 9, 256 * 2), 512));
   hipLaunchKernelGGL(pack_jobs_kernel, dim3(gx, njobs), dim3(256), 0, stream, jobs_dev, params);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-int pack_weights_bf16x3_launch(const float* w, void* dst, int f16, int cout, int cin, int rows_pad, int cols,
-                               const int* row_map, const int* col_map, int transposed, hipStream_t stream, int pair) {
-  const int nchunks = ceil_div(cols, 32);
-  const int total = nchunks * 9 * rows_pad * 32;
-  const int blocks = min(ceil_div(total, 256), 4096);
-  if (f16)
-    hipLaunchKernelGGL(pack_weights_bf16x3_kernel<true>, dim3(blocks), dim3(256), 0, stream, w,
-                       reinterpret_cast<_Float16*>(dst), cout, cin, rows_pad, cols, nchunks, row_map, col_map, transposed, pair);
-  else
-    hipLaunchKernelGGL(pack_weights_bf16x3_kernel<false>, dim3(blocks), dim3(256), 0, stream, w,
-                       reinterpret_cast<__bf16*>(dst), cout, cin, rows_pad, cols, nchunks, row_map, col_map, transposed, pair);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }

@@ -794,8 +794,6 @@ static int wide_force() {
 int conv3x3_wide_rows(int mode, int N, int cin_p, int rows, int Ho, int Wo) {
   return sched::wide_config(mode, N, cin_p, rows, Ho, Wo, wide_force()).rows_pad;
 }
-// 16-bit elements of the packed wide weight image
-size_t conv3x3_wide_weight_elems(int cin_p, int rows_pad) { return (size_t)ceil_div(cin_p, 16) * 9 * rows_pad * 32; }
 int conv3x3_wide_stat_rows() { return 256; }  // one row per persistent workgroup column
 
 int conv3x3_wide_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t stream) {
@@ -876,67 +874,6 @@ int conv3x3_wide_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t st
 #undef WIDE_FWD
 #undef WIDE_DG
 #undef WIDE_LAUNCH
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
-}
-
-// weight packing: torch OIHW -> [chunk][tap][rows_pad][64 bytes]: split16 modes: chunks of 16 input channels, row =
-// [hi 16 | lo 16]; 16-bit storage modes (single): chunks of 32 input channels, row = 32 values.  fp16 images carry
-// x 2^8.  Element formulas as pack_weights_bf16x3_kernel (conv_bf16x3.hip): row / column maps, transposed = data gradient.
-template <bool F16, bool SINGLE>
-__global__ void pack_weights_wide_kernel(const float* __restrict__ w, void* __restrict__ dstv, int cout, int cin,
-                                         int rows_pad, int cols, int nchunks, const int* __restrict__ row_map,
-                                         const int* __restrict__ col_map, int nrows_map, int transposed) {
-  typedef typename std::conditional<F16, _Float16, __bf16>::type ET;
-  constexpr int CK = SINGLE ? 32 : 16;
-  ET* dst = reinterpret_cast<ET*>(dstv);
-  const int total = nchunks * 9 * rows_pad * CK;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int k = i % CK;
-    int rest = i / CK;
-    const int row = rest % rows_pad;
-    rest /= rows_pad;
-    const int tap = rest % 9, chunk = rest / 9;
-    const int col = chunk * CK + k;
-    float v = 0.f;
-    if (col < cols && row < nrows_map) {
-      const int rm = row_map[row], cm = col_map[col];
-      if (rm >= 0 && cm >= 0) {
-        const int co = transposed ? cm : rm, ci = transposed ? rm : cm;
-        const int kh = transposed ? 2 - tap / 3 : tap / 3, kw = transposed ? 2 - tap % 3 : tap % 3;
-        v = w[(((size_t)co * cin + ci) * 3 + kh) * 3 + kw];
-      }
-    }
-    if (F16) v *= kWideF16Scale;
-    const ET hi = (ET)v;
-    ET* d = dst + (((size_t)chunk * 9 + tap) * rows_pad + row) * 32;
-    d[k] = hi;
-    if (!SINGLE) d[16 + k] = (ET)(v - (float)hi);
-  }
-}
-
-// single != 0: the 16-bit storage modes' image (one value per weight, 32-channel chunks)
-int pack_weights_wide_launch(const float* w, void* dst, int f16, int cout, int cin, int rows_pad, int cols,
-                             const int* row_map, const int* col_map, int nrows_map, int transposed, hipStream_t stream,
-                             int single) {
-  const int nchunks = ceil_div(cols, single ? 32 : 16);
-  const int total = nchunks * 9 * rows_pad * (single ? 32 : 16);
-  const int blocks = min(ceil_div(total, 256), 4096);
-#define PW_LAUNCH(F_, S_)                                                                                              \
-  hipLaunchKernelGGL((pack_weights_wide_kernel<F_, S_>), dim3(blocks), dim3(256), 0, stream, w, dst, cout, cin, rows_pad, \
-                     cols, nchunks, row_map, col_map, nrows_map, transposed)
-  if (f16) {
-    if (single)
-      PW_LAUNCH(true, true);
-    else
-      PW_LAUNCH(true, false);
-  } else {
-    if (single)
-      PW_LAUNCH(false, true);
-    else
-      PW_LAUNCH(false, false);
-  }
-#undef PW_LAUNCH
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }

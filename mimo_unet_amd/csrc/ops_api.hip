@@ -1,5 +1,6 @@
 // Single-operator C-ABI entry points (mimo_op_*): thin drivers around the same kernels the
-// plan runs, for the per-kernel parity tests.  They allocate temporaries and synchronise —
+// plan runs, for the per-kernel parity tests.  The convolutions pack their weight image as the plan does: one PackJob
+// from pack::make_job (pack_layout.h), written by pack_jobs_kernel.  They allocate temporaries and synchronise —
 // test plumbing, never on the timed path.
 #include <algorithm>
 #include <vector>
@@ -7,18 +8,28 @@
 #include "elementwise.h"
 
 using namespace mimo;
+using pack::is_mixed;
+using pack::store_type;
 
 namespace {
 
+// zeroed device temporaries of one call of the entry point `who`.  A failed allocation returns nullptr, is remembered and
+// reported by ok(): allocate what a step needs, then MIMO_TRY(t.ok()) before the first use
 struct Temp {
+  const char* who;
+  bool failed = false;
   std::vector<void*> ptrs;
+  explicit Temp(const char* who_) : who(who_) {}
   ~Temp() {
     for (void* p : ptrs) (void)hipFree(p);
   }
   template <typename T>
   T* get(size_t count) {
     void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return nullptr;
+    if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
+      failed = true;
+      return nullptr;
+    }
     (void)hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T));
     ptrs.push_back(q);
     return static_cast<T*>(q);
@@ -27,6 +38,10 @@ struct Temp {
     int* p = get<int>(v.size());
     if (p) (void)hipMemcpy(p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
     return p;
+  }
+  int ok() const {
+    if (failed) set_error("%s: allocation failed", who);
+    return failed ? MIMO_ERR_HIP : MIMO_OK;
   }
 };
 
@@ -90,7 +105,61 @@ int from16(const void* s, float* d, int64_t n, bool f16, hipStream_t st) {
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
-bool is_mixed(int precision) { return precision == MIMO_PREC_BF16_MIXED || precision == MIMO_PREC_FP16_MIXED; }
+
+// `count` fp32 elements of `src` as the storage type of `precision`: src itself for fp32 storage, a rounded 16-bit copy otherwise
+struct Stored {
+  const void* in = nullptr;  // what the kernel reads
+  void* out = nullptr;       // what the kernel writes (out16 or dst)
+  uint16_t* b16 = nullptr;
+  float* dst = nullptr;
+  int64_t count = 0;
+};
+int stage_in(Temp& t, const float* src, int64_t count, int precision, hipStream_t st, Stored* s) {
+  s->count = count;
+  s->in = src;
+  if (!src || !is_mixed(precision)) return MIMO_OK;
+  s->b16 = t.get<uint16_t>(count);
+  MIMO_TRY(t.ok());
+  MIMO_TRY(to16(src, s->b16, count, precision == MIMO_PREC_FP16_MIXED, st));
+  s->in = s->b16;
+  return MIMO_OK;
+}
+// an output (read as well when the operator accumulates into it)
+int stage_out(Temp& t, float* dst, int64_t count, int precision, hipStream_t st, Stored* s) {
+  MIMO_TRY(stage_in(t, dst, count, precision, st, s));
+  s->dst = dst;
+  s->out = s->b16 ? (void*)s->b16 : (void*)dst;
+  return MIMO_OK;
+}
+int stage_back(const Stored& s, int precision, hipStream_t st) {
+  if (s.b16) MIMO_TRY(from16(s.b16, s.dst, s.count, precision == MIMO_PREC_FP16_MIXED, st));
+  return MIMO_OK;
+}
+
+// The weight image of one convolution launch, written by the plan's packer from a table of one job: w is the bound
+// parameter buffer (w_off = 0), the bias lies at its distance from w.  The fp16 kinds get no wmax word: the image keeps
+// the fixed 2^8 (ConvLaunch::wmax == nullptr).  rows: entries of the row map; bias_dst != nullptr: the bias is copied.
+int pack_image(Temp& t, int dir, int precision, bool split, const float* w, const float* bias, float* bias_dst, int cout, int cin,
+               int cin_p, int cout_p, int rows, int wide, int pair, hipStream_t st, ConvLaunch* a) {
+  const int kind = pack::kind(precision, dir, split, wide != 0);
+  const size_t elems = pack::image_elems(kind, wide ? wide : rows, dir == PACK_FWD ? cin_p : cout_p);
+  void* img = kind == PK_F32 ? (void*)t.get<float>(elems) : (void*)t.get<uint16_t>(elems);
+  const int* rm = t.ints(ident_map(rows, dir == PACK_FWD ? cout : cin));
+  const int* cm = dir == PACK_FWD ? t.ints(ident_map(cin_p, cin)) : t.ints(ident_map(cout_p, cout));
+  PackJob* job_dev = t.get<PackJob>(1);
+  MIMO_TRY(t.ok());
+  const bool with_bias = bias && bias_dst;
+  const PackJob job = pack::make_job(dir, precision, split, cout, cin, cin_p, cout_p, rows, wide, pair, rm, cm, img, nullptr, 0,
+                                     with_bias ? (int64_t)(((intptr_t)bias - (intptr_t)w) / (intptr_t)sizeof(float)) : 0,
+                                     with_bias ? bias_dst : nullptr);
+  MIMO_HIP_CHECK(hipMemcpy(job_dev, &job, sizeof(PackJob), hipMemcpyHostToDevice));
+  MIMO_TRY(pack_jobs_launch(job_dev, 1, job.total, w, st));
+  a->w = kind == PK_F32 ? static_cast<const float*>(img) : nullptr;
+  a->wpk = kind == PK_F32 ? nullptr : img;
+  a->pair = job.pair;
+  a->wide = wide;
+  return MIMO_OK;
+}
 
 }  // namespace
 
@@ -100,55 +169,33 @@ int mimo_op_conv3x3_forward(const float* x, const float* w, const float* bias, f
                             int32_t h, int32_t wd, int32_t cin, int32_t cin_p, int32_t cout, int32_t cout_p,
                             int32_t precision, mimo_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  Temp t;
+  Temp t("mimo_op_conv3x3_forward");
   const int cout_pad = conv3x3_cout_pad(cout);
-  // 16-bit storage modes: the fp32 tensors of this interface are rounded into 16-bit buffers, the storage-mode kernels
-  // run on those, the result is widened again (exact)
-  const bool mixed = is_mixed(precision), f16s = precision == MIMO_PREC_FP16_MIXED;
-  const bool split = precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed;
-  const bool bf16 = precision == MIMO_PREC_BF16 || precision == MIMO_PREC_BF16_MIXED;
-  float* wf = t.get<float>((size_t)9 * cout_pad * cin_p);
-  void* wpk = t.get<uint16_t>((size_t)ceil_div(cin_p, 32) * 9 * cout_pad * 64);
+  const bool mixed = is_mixed(precision);
+  const int fmode = pack::conv_mode(precision, PACK_FWD);
+  // (an image convolution — <= 4 input channels in an 8-channel pixel — runs on the plain-FMA kernel, as in the plan)
+  const bool thin = !mixed && cin_p < 16 && conv3x3_thin_ok(cin, cout_p);
+  const bool split = (precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed) && !thin;
+  // split16: the decomposition the plan would pick for this geometry (conv_wide.hip or conv_bf16x3.hip)
+  const int wide = (split && (precision == MIMO_PREC_SPLIT16 || mixed)) ? conv3x3_wide_rows(fmode, n, cin_p, cout_p, h, wd) : 0;
+  const int pair = (split && !wide) ? conv3x3_pair_tail(fmode, cin_p, h, wd) : 0;
   float* bp = t.get<float>(cout_pad);
-  int* rm = t.ints(ident_map(cout_pad, cout));
-  int* cm = t.ints(ident_map(cin_p, cin));
   const int rows_cap = std::max(std::max(conv3x3_stat_rows(n, h, wd), conv3x3_ws_stat_rows(n, h, wd)), 2048);
   float* partial = t.get<float>((size_t)rows_cap * 2 * cout_pad);
   double* sums = t.get<double>((size_t)kMaxChunks * 2 * cout_pad);
-  if (!wf || !bp || !rm || !cm || !partial || !sums) {
-    set_error("mimo_op_conv3x3_forward: allocation failed");
-    return MIMO_ERR_HIP;
-  }
-  MIMO_TRY(pack_weights_launch(w, wf, cout, cin, cout_pad, cin_p, rm, cm, 0, st));
-  const int fmode = mixed ? (f16s ? 6 : 4) : (bf16 ? 2 : 1);
-  // split16: the decomposition the plan would pick for this geometry (conv_wide.hip or conv_bf16x3.hip)
-  const int wide = (precision == MIMO_PREC_SPLIT16 || mixed) ? conv3x3_wide_rows(fmode, n, cin_p, cout_p, h, wd) : 0;
-  const int pair = (split && !wide) ? conv3x3_pair_tail(fmode, cin_p, h, wd) : 0;
-  if (wide) {
-    wpk = t.get<uint16_t>(conv3x3_wide_weight_elems(cin_p, wide));
-    if (!wpk) {
-      set_error("mimo_op_conv3x3_forward: allocation failed");
-      return MIMO_ERR_HIP;
-    }
-    MIMO_TRY(pack_weights_wide_launch(w, wpk, bf16 ? 0 : 1, cout, cin, wide, cin_p, rm, cm, cout_pad, 0, st, mixed ? 1 : 0));
-  } else if (split)
-    MIMO_TRY(pack_weights_bf16x3_launch(w, wpk, bf16 ? 0 : 1, cout, cin, cout_pad, cin_p, rm, cm, 0, st, pair));
-  if (bias) MIMO_HIP_CHECK(hipMemcpyAsync(bp, bias, cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-  const int64_t nx = (int64_t)n * h * wd * cin_p, nz = (int64_t)n * h * wd * cout_p;
-  uint16_t *x16 = nullptr, *z16 = nullptr;
-  if (mixed) {
-    x16 = t.get<uint16_t>(nx);
-    z16 = t.get<uint16_t>(nz);
-    if (!x16 || !z16) {
-      set_error("mimo_op_conv3x3_forward: allocation failed");
-      return MIMO_ERR_HIP;
-    }
-    MIMO_TRY(to16(x, x16, nx, f16s, st));
-  }
+  // (with the K split the plan would use for this geometry, conv3x3_ksplit: scratch for its partial slabs)
+  const size_t kfl = (!split || mixed || wide) ? 0 : conv3x3_ksplit_scratch(fmode, n, cin_p, cout_pad, h, wd, cout_p);
+  float* kpart = kfl ? t.get<float>(kfl) : nullptr;
+  MIMO_TRY(t.ok());
+  // 16-bit storage modes: the fp32 tensors of this interface are rounded into 16-bit buffers, the storage-mode kernels
+  // run on those, the result is widened again (exact)
+  Stored xs, zs;
+  MIMO_TRY(stage_in(t, x, (int64_t)n * h * wd * cin_p, precision, st, &xs));
+  MIMO_TRY(stage_out(t, z, (int64_t)n * h * wd * cout_p, precision, st, &zs));
   ConvLaunch a;
-  a.x = mixed ? reinterpret_cast<const float*>(x16) : x;
-  a.y = mixed ? reinterpret_cast<float*>(z16) : z;
-  a.w = wf;
+  MIMO_TRY(pack_image(t, PACK_FWD, precision, split, w, bias, bp, cout, cin, cin_p, cout_p, cout_pad, wide, pair, st, &a));
+  a.x = static_cast<const float*>(xs.in);
+  a.y = static_cast<float*>(zs.out);
   a.bias = bp;
   a.stats = stats ? partial : nullptr;
   a.N = n;
@@ -160,21 +207,14 @@ int mimo_op_conv3x3_forward(const float* x, const float* w, const float* bias, f
   a.cout_pad = cout_pad;
   a.cout_store = cout_p;
   a.off = 1;
-  a.wpk = wpk;
-  a.pair = pair;
-  a.wide = wide;
   int rows = 0;
-  // (an image convolution — <= 4 input channels in an 8-channel pixel — runs on the plain-FMA kernel, as in the plan)
-  if (!mixed && cin_p < 16 && conv3x3_thin_ok(cin, cout_p))
+  if (thin)
     MIMO_TRY(conv3x3_thin_launch(a, cin, &rows, st));
-  else if (split) {
-    // (with the K split the plan would use for this geometry, conv3x3_ksplit: scratch for its partial slabs)
-    const size_t kfl = (mixed || wide) ? 0 : conv3x3_ksplit_scratch(fmode, n, cin_p, cout_pad, h, wd, cout_p);
-    float* kpart = kfl ? t.get<float>(kfl) : nullptr;
+  else if (split)
     MIMO_TRY(conv3x3_bf16x3_launch_k(a, fmode, &rows, st, kpart, kfl));
-  } else
+  else
     MIMO_TRY(conv3x3_launch(a, &rows, st));
-  if (mixed) MIMO_TRY(from16(z16, z, nz, f16s, st));
+  MIMO_TRY(stage_back(zs, precision, st));
   if (stats) {
     int chunks = 0;
     MIMO_TRY(rowsum_launch(partial, rows, 2 * cout_pad, sums, &chunks, st));
@@ -188,58 +228,29 @@ int mimo_op_conv3x3_forward(const float* x, const float* w, const float* bias, f
 int mimo_op_conv3x3_dgrad(const float* dz, const float* w, float* dx, int32_t n, int32_t h, int32_t wd, int32_t cin,
                           int32_t cin_p, int32_t cout, int32_t cout_p, int32_t precision, mimo_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  Temp t;
+  Temp t("mimo_op_conv3x3_dgrad");
   const int rows_pad = conv3x3_cout_pad(cin_p);
-  const bool mixed = is_mixed(precision), f16s = precision == MIMO_PREC_FP16_MIXED;
+  const bool mixed = is_mixed(precision);
   const bool split = precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed;
-  const bool bf16 = precision == MIMO_PREC_BF16;
-  float* wdp = t.get<float>((size_t)9 * rows_pad * cout_p);
-  void* wpk = t.get<uint16_t>((size_t)ceil_div(cout_p, 32) * 9 * rows_pad * 64);
-  int* rm = t.ints(ident_map(rows_pad, cin));
-  int* cm = t.ints(ident_map(cout_p, cout));
-  float* dxpad = t.get<float>((size_t)n * (h + 2) * (wd + 2) * cin_p);
-  if (!wdp || !rm || !cm || !dxpad) {
-    set_error("mimo_op_conv3x3_dgrad: allocation failed");
-    return MIMO_ERR_HIP;
-  }
-  MIMO_TRY(pack_weights_launch(w, wdp, cout, cin, rows_pad, cout_p, rm, cm, 1, st));
-  const int dmode = mixed ? (f16s ? 7 : 5) : (bf16 ? 3 : 0);
+  const int dmode = pack::conv_mode(precision, PACK_DGRAD);
   const int wide = (precision == MIMO_PREC_SPLIT16 || mixed) ? conv3x3_wide_rows(dmode, n, cout_p, cin_p, h + 2, wd + 2) : 0;
   const int pair = (split && !wide) ? conv3x3_pair_tail(dmode, cout_p, h + 2, wd + 2) : 0;
-  if (wide) {
-    wpk = t.get<uint16_t>(conv3x3_wide_weight_elems(cout_p, wide));
-    if (!wpk) {
-      set_error("mimo_op_conv3x3_dgrad: allocation failed");
-      return MIMO_ERR_HIP;
-    }
-    MIMO_TRY(pack_weights_wide_launch(w, wpk, f16s ? 1 : 0, cout, cin, wide, cout_p, rm, cm, rows_pad, 1, st, mixed ? 1 : 0));
-  } else if (split)
-    MIMO_TRY(pack_weights_bf16x3_launch(w, wpk, f16s ? 1 : 0, cout, cin, rows_pad, cout_p, rm, cm, 1, st, pair));
-  const float* dz_in = dz;
   const int64_t ndz = (int64_t)n * h * wd * cout_p, ndx = (int64_t)n * h * wd * cin_p;
-  uint16_t* dx16 = nullptr;
-  if (mixed) {  // plain 16-bit dz in, 16-bit padded-domain gradient out, folded in 16-bit storage, widened at the end
-    uint16_t* dz16 = t.get<uint16_t>(ndz);
-    dx16 = t.get<uint16_t>(ndx);
-    if (!dz16 || !dx16) {
-      set_error("mimo_op_conv3x3_dgrad: allocation failed");
-      return MIMO_ERR_HIP;
-    }
-    MIMO_TRY(to16(dz, dz16, ndz, f16s, st));
-    dz_in = reinterpret_cast<const float*>(dz16);
-  } else if (split) {  // the bf16-pair kernel reads dz in split storage (see elementwise.h split_pairs_launch)
-    float* dzs = t.get<float>((size_t)n * h * wd * cout_p);
-    if (!dzs) {
-      set_error("mimo_op_conv3x3_dgrad: allocation failed");
-      return MIMO_ERR_HIP;
-    }
-    MIMO_TRY(split_pairs_launch(dz, dzs, (int64_t)n * h * wd, cout_p, st));
-    dz_in = dzs;
-  }
+  // the padded-domain gradient, in the storage type (sized for fp32), folded in that storage and widened at the end
+  float* dxpad = t.get<float>((size_t)n * (h + 2) * (wd + 2) * cin_p);
+  // the bf16-pair kernel reads dz in split storage (see elementwise.h split_pairs_launch)
+  float* dz_pairs = (split && !mixed) ? t.get<float>(ndz) : nullptr;
+  const size_t kfl = (!split || mixed || wide) ? 0 : conv3x3_ksplit_scratch(dmode, n, cout_p, rows_pad, h + 2, wd + 2, cin_p);
+  float* kpart = kfl ? t.get<float>(kfl) : nullptr;
+  MIMO_TRY(t.ok());
+  Stored dzs, dxs;
+  MIMO_TRY(stage_in(t, dz, ndz, precision, st, &dzs));
+  MIMO_TRY(stage_out(t, dx, ndx, precision, st, &dxs));
+  if (dz_pairs) MIMO_TRY(split_pairs_launch(dz, dz_pairs, (int64_t)n * h * wd, cout_p, st));
   ConvLaunch a;
-  a.x = dz_in;
+  MIMO_TRY(pack_image(t, PACK_DGRAD, precision, split, w, nullptr, nullptr, cout, cin, cin_p, cout_p, rows_pad, wide, pair, st, &a));
+  a.x = dz_pairs ? dz_pairs : static_cast<const float*>(dzs.in);
   a.y = dxpad;
-  a.w = wdp;
   a.bias = nullptr;
   a.stats = nullptr;
   a.N = n;
@@ -253,21 +264,12 @@ int mimo_op_conv3x3_dgrad(const float* dz, const float* w, float* dx, int32_t n,
   a.cout_pad = rows_pad;
   a.cout_store = cin_p;
   a.off = 2;
-  a.wpk = wpk;
-  a.pair = pair;
-  a.wide = wide;
-  if (split) {
-    const size_t kfl = (mixed || wide) ? 0 : conv3x3_ksplit_scratch(dmode, n, cout_p, rows_pad, h + 2, wd + 2, cin_p);
-    float* kpart = kfl ? t.get<float>(kfl) : nullptr;
+  if (split)
     MIMO_TRY(conv3x3_bf16x3_launch_k(a, dmode, nullptr, st, kpart, kfl));
-  } else
+  else
     MIMO_TRY(conv3x3_launch(a, nullptr, st));
-  if (mixed) {
-    MIMO_TRY(fold_slice_launch(dxpad, f16s ? ST_F16 : ST_BF16, cin_p, 0, dx16, cin_p, n, h, wd, cin_p, 0, st));
-    MIMO_TRY(from16(dx16, dx, ndx, f16s, st));
-  } else {
-    MIMO_TRY(fold_slice_launch(dxpad, ST_F32, cin_p, 0, dx, cin_p, n, h, wd, cin_p, 0, st));
-  }
+  MIMO_TRY(fold_slice_launch(dxpad, store_type(precision), cin_p, 0, dxs.out, cin_p, n, h, wd, cin_p, 0, st));
+  MIMO_TRY(stage_back(dxs, precision, st));
   MIMO_HIP_CHECK(hipStreamSynchronize(st));
   return MIMO_OK;
 }
@@ -276,16 +278,13 @@ int mimo_op_conv3x3_wgrad(const float* x, const float* dz, float* dw, float* dbi
                           int32_t cin, int32_t cin_p, int32_t cout, int32_t cout_p, int32_t precision,
                           mimo_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  Temp t;
+  Temp t("mimo_op_conv3x3_wgrad");
   const bool mixed = is_mixed(precision), f16s = precision == MIMO_PREC_FP16_MIXED;
   const bool split = precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed;
   const bool bf16 = precision == MIMO_PREC_BF16;
   if (!mixed && cin_p < 16 && wgrad_thin_ok(cin, cout_p, n, h, wd)) {  // the image convolution's kernel, as in the plan
     float* part = t.get<float>(wgrad_thin_scratch(cin, cout_p));
-    if (!part) {
-      set_error("mimo_op_conv3x3_wgrad: allocation failed");
-      return MIMO_ERR_HIP;
-    }
+    MIMO_TRY(t.ok());
     MIMO_TRY(wgrad_thin_launch(x, cin_p, dz, cout_p, n, h, wd, cin, cout, cout_p, part, dw, st));
     if (dbias) {
       hipLaunchKernelGGL(colsum_naive_kernel, dim3(cout), dim3(256), 0, st, dz, (int64_t)n * h * wd, cout_p, cout, dbias);
@@ -317,32 +316,21 @@ int mimo_op_conv3x3_wgrad(const float* x, const float* dz, float* dw, float* dbi
   }
   a.partial = t.get<float>((size_t)(a.splits + a.splits / 8 + 2) * 9 * a.cin_pad * a.cout_pad);
   int* cm = t.ints(ident_map(cin_p, cin));
-  if (!a.partial || !cm) {
-    set_error("mimo_op_conv3x3_wgrad: allocation failed");
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   if (mixed) {  // activations and dz as plain 16-bit NHWC tensors
-    const int64_t nx = (int64_t)n * h * wd * cin_p, ndz = (int64_t)n * h * wd * cout_p;
-    uint16_t *x16 = t.get<uint16_t>(nx), *dz16 = t.get<uint16_t>(ndz);
-    if (!x16 || !dz16) {
-      set_error("mimo_op_conv3x3_wgrad: allocation failed");
-      return MIMO_ERR_HIP;
-    }
-    MIMO_TRY(to16(x, x16, nx, f16s, st));
-    MIMO_TRY(to16(dz, dz16, ndz, f16s, st));
-    a.x = reinterpret_cast<const float*>(x16);
-    a.dz = reinterpret_cast<const float*>(dz16);
+    Stored xs, dzs;
+    MIMO_TRY(stage_in(t, x, (int64_t)n * h * wd * cin_p, precision, st, &xs));
+    MIMO_TRY(stage_in(t, dz, (int64_t)n * h * wd * cout_p, precision, st, &dzs));
+    a.x = static_cast<const float*>(xs.in);
+    a.dz = static_cast<const float*>(dzs.in);
     a.np = 1;
     a.store = f16s ? 2 : 1;
     MIMO_TRY(wgrad_split_launch(a, st));
   } else if (split) {  // split storage of dz, as the BatchNorm-backward kernel writes it in the plan
     float* dzs = t.get<float>((size_t)n * h * wd * cout_p);
-    if (!dzs) {
-      set_error("mimo_op_conv3x3_wgrad: allocation failed");
-      return MIMO_ERR_HIP;
-    }
     // as in the plan: two fp16 MFMAs per product where the geometry has that kernel, with max |dz| next to the split
     float* amax = (!bf16 && wgrad_split_has_np2(cin_p, cout_p)) ? t.get<float>(kDzMaxSlots) : nullptr;
+    MIMO_TRY(t.ok());
     int amax_n = 0;
     MIMO_TRY(split_pairs_launch(dz, dzs, (int64_t)n * h * wd, cout_p, st, amax, &amax_n));
     a.dz = dzs;
@@ -396,41 +384,6 @@ bool bad_slice(const char* who, const char* what, int ld, int off, int c_p) {
   }
   return false;
 }
-int store_type(int precision) { return precision == MIMO_PREC_BF16_MIXED ? ST_BF16 : precision == MIMO_PREC_FP16_MIXED ? ST_F16 : ST_F32; }
-
-// `count` fp32 elements of `src` as the storage type of `precision`: src itself for fp32 storage, a rounded 16-bit copy otherwise
-struct Stored {
-  const void* in = nullptr;  // what the kernel reads
-  void* out = nullptr;       // what the kernel writes (out16 or dst)
-  uint16_t* b16 = nullptr;
-  float* dst = nullptr;
-  int64_t count = 0;
-};
-int stage_in(Temp& t, const float* src, int64_t count, int precision, hipStream_t st, Stored* s) {
-  s->count = count;
-  s->in = src;
-  if (!src || !is_mixed(precision)) return MIMO_OK;
-  s->b16 = t.get<uint16_t>(count);
-  if (!s->b16) {
-    set_error("mimo_op: allocation failed");
-    return MIMO_ERR_HIP;
-  }
-  MIMO_TRY(to16(src, s->b16, count, precision == MIMO_PREC_FP16_MIXED, st));
-  s->in = s->b16;
-  return MIMO_OK;
-}
-// an output (read as well when the operator accumulates into it)
-int stage_out(Temp& t, float* dst, int64_t count, int precision, hipStream_t st, Stored* s) {
-  MIMO_TRY(stage_in(t, dst, count, precision, st, s));
-  s->dst = dst;
-  s->out = s->b16 ? (void*)s->b16 : (void*)dst;
-  return MIMO_OK;
-}
-int stage_back(const Stored& s, int precision, hipStream_t st) {
-  if (s.b16) MIMO_TRY(from16(s.b16, s.dst, s.count, precision == MIMO_PREC_FP16_MIXED, st));
-  return MIMO_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -441,7 +394,7 @@ int mimo_op_fold_slice(const float* dxpad, int32_t ldp, int32_t choff, float* da
   if (bad_dims("mimo_op_fold_slice", n, h, w, c_p) || bad_slice("mimo_op_fold_slice", "dxpad", ldp, choff, c_p) ||
       bad_slice("mimo_op_fold_slice", "da", ldda, 0, c_p))
     return MIMO_ERR_INVALID;
-  Temp t;
+  Temp t("mimo_op_fold_slice");
   Stored src, dst;
   MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (h + 2) * (w + 2) * ldp, precision, st, &src));
   MIMO_TRY(stage_out(t, da, (int64_t)n * h * w * ldda, precision, st, &dst));
@@ -460,7 +413,7 @@ int mimo_op_pool_backward(const float* dxpad, int32_t ldp, int32_t choff, const 
   if (bad_dims(who, n, h / 2, w / 2, c_p) || bad_dims(who, n, h, w, c_p) || bad_slice(who, "dxpad", ldp, choff, c_p) ||
       bad_slice(who, "a", lda, 0, c_p) || bad_slice(who, "da", ldda, 0, c_p) || (skip && bad_slice(who, "skip", ldsk, 0, c_p)))
     return MIMO_ERR_INVALID;
-  Temp t;
+  Temp t(who);
   Stored src, act, sk, dst;
   MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (h / 2 + 2) * (w / 2 + 2) * ldp, precision, st, &src));
   MIMO_TRY(stage_in(t, a, (int64_t)n * h * w * lda, precision, st, &act));
@@ -484,7 +437,7 @@ int mimo_op_up_backward(const float* dxpad, int32_t ldp, int32_t choff, float* d
     set_error("%s: %d x %d is not the x2 up-sampling of %d x %d (floor(hs / 2) == hl)", who, hs, ws, hl, wl);
     return MIMO_ERR_INVALID;
   }
-  Temp t;
+  Temp t(who);
   Stored src, dst;
   MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (hs + 2) * (ws + 2) * ldp, precision, st, &src));
   MIMO_TRY(stage_out(t, da, (int64_t)n * hl * wl * ldda, precision, st, &dst));
@@ -524,7 +477,7 @@ int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* p, mimo_stream
   }
   GradSrc src;
   src.kind = a.kind;
-  Temp t;
+  Temp t(who);
   Stored gsrc, sk, zs, dzs;
   float* head_partial = nullptr;
   if (a.kind == GS_PLAIN) {
@@ -558,10 +511,7 @@ int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* p, mimo_stream
       return MIMO_ERR_INVALID;
     }
     head_partial = t.get<float>((size_t)kBnReduceMaxBlocks * (2 * Cp + 2));
-    if (!head_partial) {
-      set_error("%s: allocation failed", who);
-      return MIMO_ERR_HIP;
-    }
+    MIMO_TRY(t.ok());
     HeadGrad& hg = src.head;
     hg.w = a.head_w;
     hg.C = a.c;
@@ -588,10 +538,7 @@ int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* p, mimo_stream
   static_assert(kBnReduceMaxBlocks <= kColsumMaxRows, "partial-row capacity");
   float* partial = t.get<float>((size_t)kBnReduceMaxBlocks * 2 * Cp);
   int* status = t.get<int>(1);
-  if (!partial || !status) {
-    set_error("%s: allocation failed", who);
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   const int dt = store_type(prec);
   int rows = 0;
   MIMO_TRY(bnrelu_bwd_reduce_launch(src, dt, zs.in, dt, a.ldz, a.scale, a.shift, a.mean, a.invstd, a.mask, a.c, Cp, N, H, W, partial,
@@ -629,16 +576,13 @@ int mimo_op_head_backward(const mimo_op_head_backward_args* p, mimo_stream strea
               "with logits and labels)", who, kMaxHeadOut);
     return MIMO_ERR_INVALID;
   }
-  Temp t;
+  Temp t(who);
   Stored act, dst;
   MIMO_TRY(stage_in(t, a.a, (int64_t)a.n * a.hw * a.lda, a.precision, st, &act));
   MIMO_TRY(stage_out(t, a.da, (int64_t)a.n * a.hw * Cp, a.precision, st, &dst));
   static_assert(kEwMaxBlocks <= kColsumMaxRows, "partial-row capacity");
   float* partial = t.get<float>((size_t)kEwMaxBlocks * (a.co * Cp + a.co));  // one row per workgroup, head_bwd_launch's grid cap
-  if (!partial) {
-    set_error("%s: allocation failed", who);
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   int rows = 0;
   MIMO_TRY(head_bwd_launch(act.in, store_type(a.precision), a.lda, a.w, a.c, Cp, a.co, a.n, a.subnetworks, a.s, (int)a.hw, a.out, a.dout,
                            a.dloss, a.label, a.mask, a.perm, a.loss_kind, a.eps_min, a.eps_max, dst.out, partial, &rows, st,
@@ -712,13 +656,10 @@ int mimo_op_bn_stats(const mimo_op_bn_stats_args* p, mimo_stream stream) {
               a.c_p, a.cout_pad, a.rows, (long long)a.count, a.route, kColsumMaxRows);
     return MIMO_ERR_INVALID;
   }
-  Temp t;
+  Temp t(who);
   int* status = t.get<int>(1);
   double* sums = t.get<double>((size_t)kMaxChunks * 2 * a.cout_pad);
-  if (!status || !sums) {
-    set_error("%s: allocation failed", who);
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   if (!a.training) {
     MIMO_TRY(bn_eval_prepare_launch(a.c, a.c_p, a.gamma, a.beta, a.running_mean, a.running_var, a.eps, a.mean, a.invstd, a.scale,
                                     a.shift, st, status));
@@ -754,13 +695,10 @@ int mimo_op_bn_relu_forward(const mimo_op_bn_relu_forward_args* p, mimo_stream s
   if (a.pool && (bad_dims(who, a.n, a.h, a.w, Cp) || bad_slice(who, "pool", a.ldpool, 0, Cp))) return MIMO_ERR_INVALID;
   const int prec = a.precision, zprec = a.z_fp32 ? (int)MIMO_PREC_FP32 : prec;
   const int64_t P = (int64_t)a.n * a.h * a.w;
-  Temp t;
+  Temp t(who);
   Stored zs, as, ps;
   int* status = t.get<int>(1);
-  if (!status) {
-    set_error("%s: allocation failed", who);
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   MIMO_TRY(stage_in(t, a.z, P * a.ldz, zprec, st, &zs));
   MIMO_TRY(stage_out(t, a.a, P * a.lda, prec, st, &as));
   if (a.pool) {
@@ -788,7 +726,7 @@ int mimo_op_maxpool2x2_ex(const float* x, int32_t lda, float* y, int32_t ldo, in
     set_error("%s: a missing tensor", who);
     return MIMO_ERR_INVALID;
   }
-  Temp t;
+  Temp t(who);
   Stored src, dst;
   MIMO_TRY(stage_in(t, x, (int64_t)n * h * w * lda, precision, st, &src));
   MIMO_TRY(stage_out(t, y, (int64_t)n * (h / 2) * (w / 2) * ldo, precision, st, &dst));
@@ -810,7 +748,7 @@ int mimo_op_upsample_cat_ex(const float* skip, int32_t lds, const float* low, in
     set_error("%s: %d x %d is smaller than twice %d x %d, a missing tensor, or only one of lo_scale / lo_shift", who, hs, ws, hl, wl);
     return MIMO_ERR_INVALID;
   }
-  Temp t;
+  Temp t(who);
   Stored sk, lo, dst;
   MIMO_TRY(stage_in(t, skip, (int64_t)n * hs * ws * lds, precision, st, &sk));
   MIMO_TRY(stage_in(t, low, (int64_t)n * hl * wl * ldl, precision, st, &lo));
@@ -837,13 +775,10 @@ int mimo_op_head_forward(const mimo_op_head_forward_args* p, mimo_stream stream)
     return MIMO_ERR_INVALID;
   }
   if (bad_slice(who, "a", a.lda, 0, pad_channels(a.c))) return MIMO_ERR_INVALID;
-  Temp t;
+  Temp t(who);
   Stored act;
   int* status = t.get<int>(1);
-  if (!status) {
-    set_error("%s: allocation failed", who);
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   MIMO_TRY(stage_in(t, a.a, (int64_t)a.n * a.hw * a.lda, a.precision, st, &act));
   MIMO_TRY(head_fwd_launch(act.in, store_type(a.precision), a.lda, a.w, a.bias, a.c, a.co, a.n, a.subnetworks, a.s, a.hw, a.out, st,
                            status, a.in_scale, a.in_shift));
@@ -865,12 +800,9 @@ int mimo_op_loss_forward(const float* out, const float* label, const float* mask
   bool bad = false;
   MIMO_TRY(bad_perm(who, perm, subnetworks, -1, n, st, &bad));
   if (bad) return MIMO_ERR_INVALID;
-  Temp t;
+  Temp t(who);
   float* partial = t.get<float>((size_t)subnetworks * 512);  // loss_fwd_launch's grid cap
-  if (!partial) {
-    set_error("%s: allocation failed", who);
-    return MIMO_ERR_HIP;
-  }
+  MIMO_TRY(t.ok());
   int blocks = 0;
   MIMO_TRY(loss_fwd_launch(out, label, mask, perm, n, subnetworks, co, hw, loss_kind, eps_min, eps_max, partial, &blocks, st));
   MIMO_TRY(loss_finalize_launch(partial, subnetworks, blocks, (double)n * (co / 2) * hw, loss, st));
@@ -907,7 +839,7 @@ int mimo_op_unpack_dx(const float* dxpad, int32_t ldp, int32_t n, int32_t subnet
     set_error("%s: subnetwork %d of %d or a missing tensor", who, s, subnetworks);
     return MIMO_ERR_INVALID;
   }
-  Temp t;
+  Temp t(who);
   Stored src;
   MIMO_TRY(stage_in(t, dxpad, (int64_t)n * (h + 2) * (w + 2) * ldp, precision, st, &src));
   MIMO_TRY(unpack_dx_launch(src.in, store_type(precision), ldp, n, subnetworks, s, c, h, w, dx, st));

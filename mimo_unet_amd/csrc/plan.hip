@@ -365,12 +365,8 @@ struct mimo_plan {
   int alloc_act(float** p, size_t elems, int dt) {  // activation-like tensor of `elems` elements of StoreType dt
     return dalloc(p, (elems * store_bytes(dt) + 3) / 4);
   }
-  int fwd_mode() const {  // conv3x3_bf16x3_launch modes
-    return cfg.precision == MIMO_PREC_BF16 ? 2 : cfg.precision == MIMO_PREC_BF16_MIXED ? 4 : cfg.precision == MIMO_PREC_FP16_MIXED ? 6 : 1;
-  }
-  int dgrad_mode() const {
-    return cfg.precision == MIMO_PREC_BF16 ? 3 : cfg.precision == MIMO_PREC_BF16_MIXED ? 5 : cfg.precision == MIMO_PREC_FP16_MIXED ? 7 : 0;
-  }
+  int fwd_mode() const { return pack::conv_mode(cfg.precision, PACK_FWD); }  // conv3x3_bf16x3_launch modes
+  int dgrad_mode() const { return pack::conv_mode(cfg.precision, PACK_DGRAD); }
   std::vector<TensorInfo> tensors;
   int64_t param_floats = 0, buffer_floats = 0;
   float *params = nullptr, *grads = nullptr, *bnbuf = nullptr;
@@ -589,8 +585,8 @@ struct mimo_plan {
     L.off_rv = add_tensor(L.bn_name + ".running_var", {Cout}, 1);
     const bool train_bufs = cfg.inference_only != 1;  // everything only a backward reads or writes
     const bool wgrad_bufs = cfg.inference_only == 0;  // ... only a weight gradient (inference_only = 2: input gradient only)
-    MIMO_TRY(dalloc(&L.wf, (size_t)9 * L.cout_pad * L.cin_p));
-    if (train_bufs) MIMO_TRY(dalloc(&L.wd, (size_t)9 * L.dg_rows * L.cout_p));
+    MIMO_TRY(dalloc(&L.wf, pack::image_elems(PK_F32, L.cout_pad, L.cin_p)));
+    if (train_bufs) MIMO_TRY(dalloc(&L.wd, pack::image_elems(PK_F32, L.dg_rows, L.cout_p)));
     MIMO_TRY(dalloc(&L.bias_p, L.cout_pad));
     // split-bf16 MFMA needs a K chunk of 32 channels; the 2..4-channel image conv stays on the fp32 kernel
     // (16-bit storage: every layer but the image convolution runs on the 16-bit kernels, whose loaders move 8-channel units)
@@ -630,14 +626,14 @@ struct mimo_plan {
     }
     if (L.fwd_split) {
       uint16_t* q = nullptr;
-      MIMO_TRY(dalloc(&q, L.fwd_wide ? conv3x3_wide_weight_elems(L.cin_p, L.fwd_wide)
-                                     : (size_t)ceil_div(L.cin_p, 32) * 9 * L.cout_pad * 64));
+      MIMO_TRY(dalloc(&q, pack::image_elems(pack::kind(cfg.precision, PACK_FWD, true, L.fwd_wide != 0),
+                                            L.fwd_wide ? L.fwd_wide : L.cout_pad, L.cin_p)));
       L.wf16 = q;
     }
     if (L.dg_split && train_bufs) {
       uint16_t* q = nullptr;
-      MIMO_TRY(dalloc(&q, L.dg_wide ? conv3x3_wide_weight_elems(L.cout_p, L.dg_wide)
-                                    : (size_t)ceil_div(L.cout_p, 32) * 9 * L.dg_rows * 64));
+      MIMO_TRY(dalloc(&q, pack::image_elems(pack::kind(cfg.precision, PACK_DGRAD, true, L.dg_wide != 0),
+                                            L.dg_wide ? L.dg_wide : L.dg_rows, L.cout_p)));
       L.wd16 = q;
     }
     MIMO_TRY(upload_ints(&L.cin_map, in_chmap));
@@ -773,9 +769,9 @@ struct mimo_plan {
       set_error("inference_only = 2 (input gradient only) exists for the fp32 and split16 precisions, not for precision %d", cfg.precision);
       return MIMO_ERR_INVALID;
     }
-    mixed = cfg.precision == MIMO_PREC_BF16_MIXED || cfg.precision == MIMO_PREC_FP16_MIXED;
+    mixed = pack::is_mixed(cfg.precision);
     f16 = cfg.precision == MIMO_PREC_FP16_MIXED;
-    st = !mixed ? ST_F32 : f16 ? ST_F16 : ST_BF16;
+    st = pack::store_type(cfg.precision);
     esz = store_bytes(st);
     {
       const int v = getenv("MIMO_FUSE_BWD_SRC") ? atoi(getenv("MIMO_FUSE_BWD_SRC")) : 1;
@@ -989,54 +985,13 @@ struct mimo_plan {
       std::vector<PackJob> jobs, dg;
       for (auto& dc : dcs)
         for (ConvBN* L : {&dc->c1, &dc->c2}) {
-          PackJob j{};
-          j.w_off = L->off_w;
-          j.bias_off = L->off_b;
-          j.bias_dst = L->bias_p;
-          j.bias_n = L->Cout;
-          j.cout = L->Cout;
-          j.cin = L->Cin;
-          j.rows_pad = L->cout_pad;
-          j.cols = L->cin_p;
-          j.row_map = L->fwd_row_map;
-          j.col_map = L->cin_map;
-          j.transposed = 0;
-          // split16 / fp16-mixed: fp16 (hi, lo) pairs x 2^8; bf16 / bf16-mixed: bf16 pairs (single-MFMA modes read hi only)
-          j.kind = L->fwd_split ? ((cfg.precision == MIMO_PREC_BF16 || cfg.precision == MIMO_PREC_BF16_MIXED) ? 2 : 1) : 0;
-          j.dst = L->fwd_split ? L->wf16 : (void*)L->wf;
-          j.total = L->fwd_split ? ceil_div(j.cols, 32) * 9 * j.rows_pad * 32 : 9 * j.rows_pad * j.cols;
-          j.pair = L->fwd_split ? conv3x3_pair_tail(fwd_mode(), L->cin_p, L->H, L->W) : 0;
-          if (L->fwd_wide) {  // conv_wide.hip layouts: 16-channel chunks of fp16 pairs / 32-channel chunks of 16-bit values
-            j.kind = !mixed ? 3 : f16 ? 5 : 6;
-            j.map_rows = L->cout_pad;
-            j.rows_pad = L->fwd_wide;
-            j.total = mixed ? ceil_div(j.cols, 32) * 9 * j.rows_pad * 32 : ceil_div(j.cols, 16) * 9 * j.rows_pad * 16;
-            j.pair = 0;
-          }
-          j.wmax = (j.kind == 1 || j.kind == 3 || j.kind == 5) ? L->wmax : nullptr;
-          jobs.push_back(j);
-          PackJob d{};
-          d.w_off = L->off_w;
-          d.bias_n = 0;
-          d.cout = L->Cout;
-          d.cin = L->Cin;
-          d.rows_pad = L->dg_rows;
-          d.cols = L->cout_p;
-          d.row_map = L->dg_row_map;
-          d.col_map = L->dg_col_map;
-          d.transposed = 1;
-          d.kind = L->dg_split ? (f16 ? 1 : 2) : 0;
-          d.dst = L->dg_split ? L->wd16 : (void*)L->wd;
-          d.total = L->dg_split ? ceil_div(d.cols, 32) * 9 * d.rows_pad * 32 : 9 * d.rows_pad * d.cols;
-          d.pair = L->dg_split ? conv3x3_pair_tail(dgrad_mode(), L->cout_p, L->H + 2, L->W + 2) : 0;
-          if (L->dg_wide) {  // bf16 pairs / 16-bit values
-            d.kind = !mixed ? 4 : f16 ? 5 : 6;
-            d.map_rows = L->dg_rows;
-            d.rows_pad = L->dg_wide;
-            d.total = mixed ? ceil_div(d.cols, 32) * 9 * d.rows_pad * 32 : ceil_div(d.cols, 16) * 9 * d.rows_pad * 16;
-            d.pair = 0;
-          }
-          dg.push_back(d);
+          // (fp16 forward images follow the layer's max |w|, L->wmax; the data gradient's keep the fixed 2^8)
+          jobs.push_back(pack::make_job(PACK_FWD, cfg.precision, L->fwd_split, L->Cout, L->Cin, L->cin_p, L->cout_p, L->cout_pad,
+                                        L->fwd_wide, conv3x3_pair_tail(fwd_mode(), L->cin_p, L->H, L->W), L->fwd_row_map, L->cin_map,
+                                        L->fwd_split ? L->wf16 : (void*)L->wf, L->wmax, L->off_w, L->off_b, L->bias_p));
+          dg.push_back(pack::make_job(PACK_DGRAD, cfg.precision, L->dg_split, L->Cout, L->Cin, L->cin_p, L->cout_p, L->dg_rows,
+                                      L->dg_wide, conv3x3_pair_tail(dgrad_mode(), L->cout_p, L->H + 2, L->W + 2), L->dg_row_map,
+                                      L->dg_col_map, L->dg_split ? L->wd16 : (void*)L->wd, nullptr, L->off_w));
         }
       n_fwd_jobs = (int)jobs.size();
       if (cfg.inference_only != 1) jobs.insert(jobs.end(), dg.begin(), dg.end());

@@ -38,11 +38,20 @@ def test_graph_replay_policy_under_asan_ubsan(tmp_path):
     _run_host_test(tmp_path, "graph_replay_test")
 
 
+def test_pack_layout_under_asan_ubsan(tmp_path):
+    """mimo_unet_amd/csrc/pack_layout.h: the layout kind and the convolution mode of every (precision, direction, split,
+    wide) the plan produces against a written-out table, and over a sweep of layer geometries the job the plan and the
+    per-operator entry points build: sizes consistent, every element pack_jobs_kernel's formulas store to inside the
+    image (tests/host/pack_layout_test.cpp)."""
+    _run_host_test(tmp_path, "pack_layout_test")
+
+
 def test_kernels_use_the_tested_header():
     """No private copy of a scheduler is left in the .hip sources."""
     csrc = os.path.join(ROOT, "mimo_unet_amd", "csrc")
     for fn, needles in (("conv_bf16x3.hip", ["using sched::pick_tile_n"]), ("conv3x3.hip", ["sched::pick_tile_n", "sched::conv_cout_pad"]),
-                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy", "sched::GraphReplayPolicy"]), ("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
+                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy", "sched::GraphReplayPolicy", "pack::make_job", "pack::image_elems"]),
+                        ("ops_api.hip", ["pack::make_job", "pack::image_elems"]),("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
                         ("conv_wide.hip", ["sched::wide_config", "sched::wide_grid_x"])):
         text = open(os.path.join(csrc, fn)).read()
         for n in needles:
