@@ -26,11 +26,7 @@ constexpr int kMaxTilePix = 360;  // (TR+2)*(TC+2) upper bound held in LDS
 // ---------------------------------------------------------------------------------------
 static void pick_tile(int Ho, int Wo, int* TR, int* TC) { sched::pick_tile_n(Ho, Wo, 256, kMaxTilePix, TR, TC); }
 
-int conv3x3_stat_rows(int N, int Ho, int Wo) {
-  int TR, TC;
-  pick_tile(Ho, Wo, &TR, &TC);
-  return N * ceil_div(Ho, TR) * ceil_div(Wo, TC);
-}
+int conv3x3_stat_rows(int N, int Ho, int Wo) { return sched::conv_stat_rows(N, Ho, Wo); }
 
 int conv3x3_pick_nfrag(int cout) { return sched::conv_pick_nfrag(cout); }
 int conv3x3_cout_pad(int cout) { return sched::conv_cout_pad(cout); }

@@ -78,14 +78,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPitchB = 144;  // bytes per LDS row (pixel or weight row)
 
-using sched::pick_tile_n;  // tile_sched.h (host-testable)
-
-template <int MF>
-struct TileCfg {
-  static constexpr int NPIX = 8 * MF * 16;
-  static constexpr int MAXPIX = MF == 4 ? 640 : 360;
-};
-
 template <int MF, int NF, int MODE>
 __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(ConvLaunch a, int TR, int TC, int tilesY, int tilesX) {
   MIMO_CONV_MODE_CONSTANTS
@@ -94,7 +86,7 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(ConvLaunch a, int T
   typedef typename Elem<F16>::V8 bf16x8;
   typedef typename Elem<F16>::V4 bf16x4;
   constexpr int NB = NF * 16;
-  constexpr int MAXPIX = TileCfg<MF>::MAXPIX;
+  constexpr int MAXPIX = sched::split_maxpix(false, MF);  // tile_sched.h: the tile families of both kernels
   constexpr int XU = (MAXPIX * 8 + 511) / 512;      // float4 units of the input tile per thread
   constexpr int WUNITS = 3 * NB * 8;                 // 16-byte units of one weight tap row
   constexpr int WU = (WUNITS + 511) / 512;
@@ -378,11 +370,6 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(ConvLaunch a, int T
 // (180-pixel halo); with NF <= 2 the workgroup needs 79 KB of LDS and 128 registers per lane, so TWO workgroups
 // share a CU and one's MFMAs fill the other's barrier / staging / epilogue bubbles — for the thin layers (<= 32
 // output channels), whose tiles carry too little MFMA work to hide those.
-template <int MF>
-struct WsTile {
-  static constexpr int NPIX = 64 * MF;
-  static constexpr int MAXPIX = MF == 4 ? 360 : 180;
-};
 constexpr int kWsMaxMF = 4;
 
 // PAIR (split16 modes, padded rows): the LAST 32-channel chunk of the input holds <= 16 channels.  Its taps are then
@@ -420,7 +407,7 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
   typedef typename std::conditional<OUT16, ET, float>::type OT;  // element type of the output tensor
   constexpr int NB = NF * 16;
   constexpr int MF = MF_;
-  constexpr int kWsMaxPix = WsTile<MF>::MAXPIX;
+  constexpr int kWsMaxPix = sched::split_maxpix(true, MF);
   // 16-byte units per LDS row that carry data: 8 (fp32 input: 4 channels each; pre-split input: hi + lo halves) or,
   // for plain 16-bit input, the 4 units of the hi half (8 channels each)
   constexpr int UPP = IN16 ? 4 : 8, UPPS = IN16 ? 2 : 3;
@@ -900,100 +887,71 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
 #undef C_PHASE
 }
 
+// Which instance, tile and grid a launch gets: sched::split_config and its rules (tile_sched.h, host-testable).  The
+// environment switches are read here, once, and passed in.
 static bool conv_ws_enabled() {
   static const bool on = !(getenv("MIMO_CONV_WS") && atoi(getenv("MIMO_CONV_WS")) == 0);
   return on;
 }
+static int conv_ksplit_force() {
+  static const int force = [] { const char* e = getenv("MIMO_CONV_KSPLIT"); return e ? atoi(e) : -1; }();
+  return force;
+}
 
-int conv3x3_ws_stat_rows(int, int, int) { return 512 * 4; }  // <= 512 persistent workgroups x 4 consumer waves
-
-// Tap pairing of a <= 16-channel last chunk (see conv3x3_ws_kernel): decided per layer from what the dispatch below
-// will launch — the packer lays the chunk's weights out for it, the launch selects the PAIR instance (ConvLaunch::pair).
-int conv3x3_pair_tail(int mode, int cin_p, int Ho, int Wo) {
-  if (mode < 0 || mode > 1 || !conv_ws_enabled() || Ho * Wo < 256) return 0;
-  const int tail = cin_p - 32 * (ceil_div(cin_p, 32) - 1);
-  return tail <= 16 ? 1 : 0;
+int conv3x3_ws_stat_rows(int, int, int) { return sched::kWsStatRows; }
+int conv3x3_pair_tail(int mode, int cin_p, int Ho, int Wo) { return sched::ws_tail_pairs(mode, cin_p, Ho, Wo, conv_ws_enabled()); }
+int conv3x3_split_fuses_input(int mode, int wide, int Ho, int Wo) {
+  return sched::split_fuses_input(mode, wide, Ho, Wo, conv_ws_enabled());
+}
+int conv3x3_ksplit(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo) {
+  return sched::split_pick_ksplit(mode, N, cin_p, cout_pad, Ho, Wo, conv_ws_enabled(), conv_ksplit_force());
+}
+size_t conv3x3_ksplit_scratch(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, int ldy) {
+  return sched::ksplit_scratch_floats(conv3x3_ksplit(mode, N, cin_p, cout_pad, Ho, Wo), N, Ho, Wo, ldy);
 }
 
 template <int NF, int MODE, int MF>
-static int launch_ws(const ConvLaunch& a, int* rows, hipStream_t stream) {
-  int TR, TC;
-  pick_tile_n(a.Ho, a.Wo, WsTile<MF>::NPIX, WsTile<MF>::MAXPIX, &TR, &TC);
-  const int tilesY = ceil_div(a.Ho, TR), tilesX = ceil_div(a.Wo, TC);
-  const int numTiles = a.N * tilesY * tilesX;
-  const int coTiles = a.cout_pad / (NF * 16);
-  // persistent: one workgroup per CU (two for the 128-pixel / <= 32-channel instances), every workgroup of a
-  // launch walks the same number of tiles
-  constexpr int kWgPerCU = (MF == 2 && NF <= 2) ? 2 : 1;
+static int launch_ws(const ConvLaunch& a, const sched::SplitCfg& c, hipStream_t stream) {
   const int ksplit = a.ksplit > 1 ? a.ksplit : 1;
-  if (ksplit > 1) {
-    const int nchunks = ceil_div(a.cin_p, 32), cpk = ceil_div(nchunks, ksplit);
-    if (MODE > 1 || a.pair || a.bias || a.stats || a.ep_scale || a.cin_p % 32 != 0 || cpk * (ksplit - 1) >= nchunks) {
-      set_error("conv3x3 split: K split %d needs a split16 launch without bias / stats / epilogue, whole 32-channel chunks "
-                "and at least one chunk per split (cin_p %d)", ksplit, a.cin_p);
-      return MIMO_ERR_INVALID;
-    }
+  if (ksplit > 1 && (MODE > 1 || a.pair || a.bias || a.stats || a.ep_scale || a.cin_p % 32 != 0 ||
+                     !sched::ksplit_legal(ceil_div(a.cin_p, 32), ksplit))) {
+    set_error("conv3x3 split: K split %d needs a split16 launch without bias / stats / epilogue, whole 32-channel chunks "
+              "and at least one chunk per split (cin_p %d)", ksplit, a.cin_p);
+    return MIMO_ERR_INVALID;
   }
-  int gx = max(1, 256 * kWgPerCU / (coTiles * ksplit));
-  if (gx > numTiles) gx = numTiles;
-  const int per = ceil_div(numTiles, gx);
-  gx = ceil_div(numTiles, per);
-  if (rows) *rows = gx;  // one partial-statistics row per workgroup
-  dim3 grid(gx * coTiles * ksplit);
-  const int xcd = 1;  // XCD-aware workgroup order (xcd_virtual_index)
-  if (a.in_scale) {
-    if constexpr (MODE == 1) {
-      if (a.ep_scale || !a.in_shift || (a.pair && a.pair != conv3x3_pair_tail(MODE, a.cin_p, a.Ho, a.Wo))) {
-        set_error("conv3x3 split: the input BatchNorm + ReLU can be fused into the split16 training forward only");
-        return MIMO_ERR_INVALID;
-      }
-      if (a.pair)
-        hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, true, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
-      else
-        hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, false, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
-      MIMO_KERNEL_CHECK();
-      return MIMO_OK;
-    } else {
-      set_error("conv3x3 split: the input BatchNorm + ReLU can be fused into the split16 forward only");
-      return MIMO_ERR_INVALID;
-    }
+  if (a.in_scale && (MODE != 1 || a.ep_scale || !a.in_shift)) {
+    set_error("conv3x3 split: the input BatchNorm + ReLU can be fused into the split16 training forward only");
+    return MIMO_ERR_INVALID;
   }
-  if (a.pair) {
-    if constexpr (MODE <= 1) {
-      if (a.pair != conv3x3_pair_tail(MODE, a.cin_p, a.Ho, a.Wo)) {
-        set_error("conv3x3 split: weights packed for tap pairing, launch is not");
-        return MIMO_ERR_INVALID;
-      }
-      hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, true>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
-    } else {
-      set_error("conv3x3 split: tap pairing exists for the split16 modes only");
-      return MIMO_ERR_INVALID;
-    }
-  } else
-    hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX, numTiles, xcd, gx, coTiles);
+  const int numTiles = a.N * c.tilesY * c.tilesX;
+  const dim3 grid(c.gx * c.coTiles * ksplit);
+  // (the 1: XCD-aware workgroup order, xcd_virtual_index)
+#define WS_LAUNCH(PAIR_, FIN_)                                                                                          \
+  hipLaunchKernelGGL((conv3x3_ws_kernel<NF, MODE, MF, PAIR_, FIN_>), grid, dim3(512), 0, stream, a, c.TR, c.TC, c.tilesY, \
+                     c.tilesX, numTiles, 1, c.gx, c.coTiles)
+  const bool fin = a.in_scale != nullptr, pair = a.pair != 0;  // (pair: the dispatch checked it against the geometry)
+  if constexpr (MODE == 1) {
+    if (fin && pair) WS_LAUNCH(true, true);
+    else if (fin) WS_LAUNCH(false, true);
+    else if (pair) WS_LAUNCH(true, false);
+    else WS_LAUNCH(false, false);
+  } else if constexpr (MODE == 0) {
+    if (pair) WS_LAUNCH(true, false);
+    else WS_LAUNCH(false, false);
+  } else {
+    WS_LAUNCH(false, false);
+  }
+#undef WS_LAUNCH
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
 
 template <int MF, int NF, int MODE>
-static int launch_bf16x3(const ConvLaunch& a, int* rows, hipStream_t stream) {
-  int TR, TC;
-  pick_tile_n(a.Ho, a.Wo, TileCfg<MF>::NPIX, TileCfg<MF>::MAXPIX, &TR, &TC);
-  const int tilesY = ceil_div(a.Ho, TR), tilesX = ceil_div(a.Wo, TC);
-  if (rows) *rows = a.N * tilesY * tilesX;
-  dim3 grid(a.N * tilesY * tilesX, a.cout_pad / (NF * 16));
-  hipLaunchKernelGGL((conv3x3_bf16x3_kernel<MF, NF, MODE>), grid, dim3(512), 0, stream, a, TR, TC, tilesY, tilesX);
+static int launch_bf16x3(const ConvLaunch& a, const sched::SplitCfg& c, hipStream_t stream) {
+  hipLaunchKernelGGL((conv3x3_bf16x3_kernel<MF, NF, MODE>), dim3(c.gx, c.coTiles), dim3(512), 0, stream, a, c.TR, c.TC, c.tilesY,
+                     c.tilesX);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
-}
-
-// MF = 4 (512-pixel tiles) when the image is large enough to fill them, else 2.
-static bool use_big_tile(int Ho, int Wo) { return Ho * Wo >= 1024; }
-
-// 1 when the launch runs on a kernel whose loaders can apply ConvLaunch::in_scale / in_shift (the wide kernel and the
-// 256-pixel wave-specialised kernel, split16 forward)
-int conv3x3_split_fuses_input(int mode, int wide, int Ho, int Wo) {
-  return mode == 1 && (wide != 0 || (conv_ws_enabled() && Ho * Wo >= 256)) ? 1 : 0;
 }
 
 template <int MODE>
@@ -1002,106 +960,29 @@ static int conv3x3_split_dispatch(const ConvLaunch& a, int* rows, hipStream_t st
     set_error("conv3x3 split: this launch cannot apply the input BatchNorm + ReLU in its loader (conv3x3_split_fuses_input)");
     return MIMO_ERR_INVALID;
   }
-  const int nfr = a.cout_pad / 16;
-  int nf = 4;
-  while (nfr % nf != 0) --nf;
-  if (conv_ws_enabled() && a.Ho * a.Wo >= 256) {
-    // Channel-tile width of the persistent kernel by cost, not just "the widest that divides": a launch with fewer
-    // (pixel tile, channel tile) pairs than CUs (the 16x16 .. 64x64 layers at a few images per GPU — the per-GPU
-    // batch of a strong-scaling run) finishes sooner with narrow channel tiles on many CUs than with wide ones on a
-    // few: time ~ (tiles per workgroup) x (per-phase fixed cost + NF x MFMA time), fixed cost ~ one NF unit.
-    if (a.ksplit <= 1) {  // (a K split keeps the widest channel tile: conv3x3_ksplit priced it that way)
-      int TR, TC;
-      pick_tile_n(a.Ho, a.Wo, WsTile<4>::NPIX, WsTile<4>::MAXPIX, &TR, &TC);
-      const int numTiles = a.N * ceil_div(a.Ho, TR) * ceil_div(a.Wo, TC);
-      long best = -1;
-      for (int c = 4; c >= 1; --c) {
-        if (nfr % c) continue;
-        const int gx = max(1, min(numTiles, 256 / (nfr / c)));
-        const long cost = (long)ceil_div(numTiles, gx) * (1 + c);
-        if (best < 0 || cost < best) best = cost, nf = c;
-      }
-    }
-    // NF <= 2: little MFMA work per tile -> 128-pixel tiles so that two workgroups share a CU and one's loads / stores
-    // overlap the other's MFMAs.  Forward only (measured per layer on one box: forward 30->30 at 256x256 169 -> 147 us,
-    // 45->30 282 -> 253 us; the data gradient of the same shapes 132 -> 145 us)
-    const bool mf2 = (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 6);
-    switch (nf) {
-      case 4: return launch_ws<4, MODE, 4>(a, rows, stream);
-      case 3: return launch_ws<3, MODE, 4>(a, rows, stream);
-      case 2: return mf2 ? launch_ws<2, MODE, 2>(a, rows, stream) : launch_ws<2, MODE, 4>(a, rows, stream);
-      default: return mf2 ? launch_ws<1, MODE, 2>(a, rows, stream) : launch_ws<1, MODE, 4>(a, rows, stream);
-    }
-  }
-  if (a.pair) {
+  const sched::SplitCfg c = sched::split_config(MODE, a.N, a.cin_p, a.cout_pad, a.Ho, a.Wo, a.ksplit, conv_ws_enabled());
+  if (a.pair && a.pair != c.pair) {
     set_error("conv3x3 split: weights packed for tap pairing, launch is not");
     return MIMO_ERR_INVALID;
   }
-  if (use_big_tile(a.Ho, a.Wo) && nf >= 3) {
-    switch (nf) {
-      case 4: return launch_bf16x3<4, 4, MODE>(a, rows, stream);
-      case 3: return launch_bf16x3<4, 3, MODE>(a, rows, stream);
-      case 2: return launch_bf16x3<4, 2, MODE>(a, rows, stream);
-      default: return launch_bf16x3<4, 1, MODE>(a, rows, stream);
+  if (rows) *rows = c.stat_rows;
+  if (c.ws) {
+    switch (c.NF) {
+      case 4: return launch_ws<4, MODE, 4>(a, c, stream);
+      case 3: return launch_ws<3, MODE, 4>(a, c, stream);
+      case 2: return c.MF == 2 ? launch_ws<2, MODE, 2>(a, c, stream) : launch_ws<2, MODE, 4>(a, c, stream);
+      default: return c.MF == 2 ? launch_ws<1, MODE, 2>(a, c, stream) : launch_ws<1, MODE, 4>(a, c, stream);
     }
   }
-  switch (nf) {
-    case 4: return launch_bf16x3<2, 4, MODE>(a, rows, stream);
-    case 3: return launch_bf16x3<2, 3, MODE>(a, rows, stream);
-    case 2: return launch_bf16x3<2, 2, MODE>(a, rows, stream);
-    default: return launch_bf16x3<2, 1, MODE>(a, rows, stream);
+  switch (c.NF) {
+    case 4: return c.MF == 4 ? launch_bf16x3<4, 4, MODE>(a, c, stream) : launch_bf16x3<2, 4, MODE>(a, c, stream);
+    case 3: return c.MF == 4 ? launch_bf16x3<4, 3, MODE>(a, c, stream) : launch_bf16x3<2, 3, MODE>(a, c, stream);
+    case 2: return c.MF == 4 ? launch_bf16x3<4, 2, MODE>(a, c, stream) : launch_bf16x3<2, 2, MODE>(a, c, stream);
+    default: return c.MF == 4 ? launch_bf16x3<4, 1, MODE>(a, c, stream) : launch_bf16x3<2, 1, MODE>(a, c, stream);
   }
 }
 
-// ---- K split (round 6) ------------------------------------------------------------------------------------------
-// Cost in the units of the channel-tile rule above: a phase of a persistent workgroup costs (1 + NF) — one unit of fixed
-// cost (barrier, pipeline latency) and one per 16-channel fragment of MFMA work.  Unsplit: the rule's own optimum over NF.
-// Split ks-fold: the widest channel tile, ceil(nchunks / ks) chunks per workgroup, plus the reduction pass (priced at
-// kKsplitReduceUnits: one more launch over ks + 1 small tensors).  Taken when it wins by >= 15 %.
-constexpr int kKsplitReduceUnits = 14;
-int conv3x3_ksplit(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo) {
-  static const int force = [] { const char* e = getenv("MIMO_CONV_KSPLIT"); return e ? atoi(e) : -1; }();
-  if (force == 0 || (mode != 0 && mode != 1) || !conv_ws_enabled() || Ho * Wo < 256 || cin_p % 32 != 0 ||
-      cout_pad % 16 != 0)
-    return 1;
-  const int nchunks = cin_p / 32;
-  if (nchunks < 2) return 1;
-  auto legal = [&](int ks) { return ks >= 2 && ceil_div(nchunks, ks) * (ks - 1) < nchunks; };
-  if (force >= 2) {
-    int ks = min(force, nchunks);
-    while (ks >= 2 && !legal(ks)) --ks;
-    return ks >= 2 ? ks : 1;
-  }
-  int TR, TC;
-  pick_tile_n(Ho, Wo, WsTile<4>::NPIX, WsTile<4>::MAXPIX, &TR, &TC);
-  const int numTiles = N * ceil_div(Ho, TR) * ceil_div(Wo, TC);
-  const int nfr = cout_pad / 16;
-  long unsplit = -1;
-  for (int c = 4; c >= 1; --c) {
-    if (nfr % c) continue;
-    const int gx = max(1, min(numTiles, 256 / (nfr / c)));
-    const long cost = (long)ceil_div(numTiles, gx) * (1 + c) * nchunks * 3;
-    if (unsplit < 0 || cost < unsplit) unsplit = cost;
-  }
-  int nf = 4;
-  while (nfr % nf != 0) --nf;
-  const int coTiles = nfr / nf;
-  int best = 1;
-  long best_cost = -1;
-  for (int ks = 2; ks <= 8 && ks <= nchunks; ++ks) {
-    if (!legal(ks) || coTiles * ks > 256) continue;
-    const int gx = max(1, min(numTiles, 256 / (coTiles * ks)));
-    const long cost = (long)ceil_div(numTiles, gx) * (1 + nf) * ceil_div(nchunks, ks) * 3 + kKsplitReduceUnits;
-    if (best_cost < 0 || cost < best_cost) best_cost = cost, best = ks;
-  }
-  return (best_cost >= 0 && best_cost * 100 < unsplit * 85) ? best : 1;
-}
-
-size_t conv3x3_ksplit_scratch(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, int ldy) {
-  const int ks = conv3x3_ksplit(mode, N, cin_p, cout_pad, Ho, Wo);
-  return ks > 1 ? (size_t)ks * N * Ho * Wo * ldy : 0;
-}
-
+// ---- K split (round 6; sched::split_pick_ksplit) ------------------------------------------------------------------
 // out[p][c] = bias[c] + sum over the slabs of part[k][p][c]; stats != nullptr: one row [2][cout_pad] of (sum, sum of squares)
 // per workgroup, the layout of the convolution epilogue's BatchNorm partial rows.  256 threads = QB channel quads x PPI pixels.
 __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __restrict__ part, int ksplit, int P, int ld, int Cv,
@@ -1143,7 +1024,7 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_kernel(const float* __
 
 int conv3x3_bf16x3_launch_k(const ConvLaunch& a, int mode, int* rows, hipStream_t stream, float* kpart, size_t kpart_floats) {
   const int ks = (a.wide || a.ep_scale || !kpart) ? 1 : conv3x3_ksplit(mode, a.N, a.cin_p, a.cout_pad, a.Ho, a.Wo);
-  const size_t need = (size_t)ks * a.N * a.Ho * a.Wo * a.ldy;
+  const size_t need = sched::ksplit_scratch_floats(ks, a.N, a.Ho, a.Wo, a.ldy);
   if (ks <= 1 || a.pair || need > kpart_floats || a.cout_store % 4 != 0 || a.ldy % 4 != 0 || (size_t)a.N * a.Ho * a.Wo > (1u << 30))
     return conv3x3_bf16x3_launch(a, mode, rows, stream);
   ConvLaunch p = a;

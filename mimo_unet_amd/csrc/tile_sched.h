@@ -3,6 +3,7 @@
 // g++ -fsanitize=address,undefined and sweeps every function over its whole argument range (tests/test_sched_cpu.py).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -69,6 +70,147 @@ static inline int conv_pick_nfrag(int cout) {
   return best;
 }
 static inline int conv_cout_pad(int cout) { return rup(cdiv(cout, 16), conv_pick_nfrag(cout)) * 16; }
+// BatchNorm partial rows of the fp32-MFMA kernel: one per 256-pixel tile
+static inline int conv_stat_rows(int N, int Ho, int Wo) {
+  int TR, TC;
+  pick_tile_n(Ho, Wo, 256, 360, &TR, &TC);
+  return N * cdiv(Ho, TR) * cdiv(Wo, TC);
+}
+
+// Persistent grid: gx pixel-tile columns x `column_wgs` workgroups per column (channel tiles x K splits), `wg_per_cu`
+// workgroups on each of the 256 CUs; gx is evened out so that every column walks the same number of tiles (+-1).
+// 1 <= gx <= numTiles for numTiles >= 1.
+static inline int persistent_grid_x(int numTiles, int column_wgs, int wg_per_cu) {
+  int gx = 256 * wg_per_cu / column_wgs;
+  if (gx < 1) gx = 1;
+  if (gx > numTiles) gx = numTiles;
+  return cdiv(numTiles, cdiv(numTiles, gx));
+}
+
+// ---- 256-pixel split convolution (conv_bf16x3.hip) --------------------------------------------------------------
+// Two kernel families.  ws: the wave-specialised persistent kernel (4 consumer waves x MF fragments of 16 pixels), on
+// outputs of >= 256 pixels.  Otherwise, and with the switch off, the kernel whose 8 waves all stage and multiply
+// (8 x MF fragments of 16 pixels, one workgroup per tile).  MF = 2 or 4.
+constexpr int split_npix(bool ws, int mf) { return (ws ? 64 : 128) * mf; }  // output pixels of a tile
+constexpr int split_maxpix(bool ws, int mf) { return ws ? (mf == 4 ? 360 : 180) : (mf == 4 ? 640 : 360); }  // LDS rows of its halo
+constexpr int kWsStatRows = 512 * 4;  // BatchNorm partial rows the plan reserves for a ws launch (it writes one per column)
+
+static inline bool split_uses_ws(int Ho, int Wo, bool ws_enabled) { return ws_enabled && Ho * Wo >= 256; }
+static inline bool split_is_forward(int mode) { return mode == 1 || mode == 2 || mode == 4 || mode == 6; }
+// the last 32-channel chunk of the input holds <= 16 channels
+static inline bool split_tail_short(int cin_p) { return cin_p - 32 * (cdiv(cin_p, 32) - 1) <= 16; }
+// 1 when the launch runs on the tap-paired ws instance (split16 modes, short last chunk: two taps per MFMA): the packer
+// lays that chunk's weights out for it
+static inline int ws_tail_pairs(int mode, int cin_p, int Ho, int Wo, bool ws_enabled) {
+  return (mode == 0 || mode == 1) && split_uses_ws(Ho, Wo, ws_enabled) && split_tail_short(cin_p) ? 1 : 0;
+}
+// 1 when the launch runs on a kernel whose loaders can apply ConvLaunch::in_scale / in_shift (split16 forward on the wide
+// kernel or the ws kernel)
+static inline int split_fuses_input(int mode, int wide, int Ho, int Wo, bool ws_enabled) {
+  return mode == 1 && (wide != 0 || split_uses_ws(Ho, Wo, ws_enabled)) ? 1 : 0;
+}
+
+// Cost model of a ws launch: a phase (tap row of a 32-channel chunk) of a persistent workgroup costs (1 + NF) — one unit
+// of fixed cost (barrier, pipeline latency) and one per 16-channel fragment of MFMA work — and a workgroup walks
+// ceil(tiles / gx) tiles of 256 pixels.  split_cost = that product for one phase per tile.
+static inline int split_ws_tiles(int N, int Ho, int Wo) {
+  int TR, TC;
+  pick_tile_n(Ho, Wo, split_npix(true, 4), split_maxpix(true, 4), &TR, &TC);
+  return N * cdiv(Ho, TR) * cdiv(Wo, TC);
+}
+static inline long split_cost(int numTiles, int column_wgs, int nf) {
+  return (long)cdiv(numTiles, persistent_grid_x(numTiles, column_wgs, 1)) * (1 + nf);
+}
+// Channel-tile width (fragments of 16 channels, a divisor of nfr = cout_pad / 16).  Widest: what the non-specialised
+// kernel and a K split run.  By cost, ties to the wider: a launch with fewer (pixel tile, channel tile) pairs than CUs
+// (the 16x16 .. 64x64 layers at a few images per GPU) finishes sooner with narrow channel tiles on many CUs.
+static inline int split_widest_nf(int nfr) {
+  int nf = 4;
+  while (nfr % nf != 0) --nf;
+  return nf;
+}
+static inline int split_pick_nf(int nfr, int numTiles) {
+  int nf = 1;
+  long best = -1;
+  for (int c = 4; c >= 1; --c) {
+    if (nfr % c) continue;
+    const long cost = split_cost(numTiles, nfr / c, c);
+    if (best < 0 || cost < best) best = cost, nf = c;
+  }
+  return nf;
+}
+
+// K split: the workgroups of a (column, channel tile) pair come ks-fold, each walks ceil(nchunks / ks) chunks; legal when
+// the last split still has a chunk.  Priced in split_cost units x phases: unsplit at the cost rule's own NF, split at the
+// widest NF plus the reduction pass (kKsplitReduceUnits: one more launch over ks + 1 small tensors); taken when it wins
+// by >= 15 %.  force: 0 = never, >= 2 = that many (or the most that is legal below it) wherever the launch has whole
+// 32-channel chunks, else by cost.  Returns 1 for no split.
+constexpr int kKsplitReduceUnits = 14;
+static inline bool ksplit_legal(int nchunks, int ks) { return ks >= 2 && cdiv(nchunks, ks) * (ks - 1) < nchunks; }
+static inline int split_pick_ksplit(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, bool ws_enabled, int force) {
+  if (force == 0 || (mode != 0 && mode != 1) || !split_uses_ws(Ho, Wo, ws_enabled) || cin_p % 32 != 0 || cout_pad % 16 != 0)
+    return 1;
+  const int nchunks = cin_p / 32;
+  if (nchunks < 2) return 1;
+  if (force >= 2) {
+    int ks = force < nchunks ? force : nchunks;
+    while (ks >= 2 && !ksplit_legal(nchunks, ks)) --ks;
+    return ks >= 2 ? ks : 1;
+  }
+  const int numTiles = split_ws_tiles(N, Ho, Wo), nfr = cout_pad / 16;
+  const int nf_u = split_pick_nf(nfr, numTiles);
+  const long unsplit = split_cost(numTiles, nfr / nf_u, nf_u) * nchunks * 3;
+  const int nf = split_widest_nf(nfr), coTiles = nfr / nf;
+  int best = 1;
+  long best_cost = -1;
+  for (int ks = 2; ks <= 8 && ks <= nchunks; ++ks) {
+    if (!ksplit_legal(nchunks, ks) || coTiles * ks > 256) continue;
+    const long cost = split_cost(numTiles, coTiles * ks, nf) * cdiv(nchunks, ks) * 3 + kKsplitReduceUnits;
+    if (best_cost < 0 || cost < best_cost) best_cost = cost, best = ks;
+  }
+  return (best_cost >= 0 && best_cost * 100 < unsplit * 85) ? best : 1;
+}
+// floats of scratch for the partial slabs [ks][N][Ho][Wo][ldy] of a K split
+static inline size_t ksplit_scratch_floats(int ks, int N, int Ho, int Wo, int ldy) {
+  return ks > 1 ? (size_t)ks * N * Ho * Wo * ldy : 0;
+}
+
+// What conv3x3_bf16x3_launch runs for a geometry.  ksplit: ConvLaunch::ksplit (<= 1: none).
+struct SplitCfg {
+  bool ws;         // kernel family
+  int MF, NF;      // fragments of 16 pixels per (consumer) wave, of 16 output channels per workgroup
+  int TR, TC;      // output tile
+  int tilesY, tilesX;
+  int gx;          // ws: persistent pixel-tile columns (grid = gx * coTiles * ksplit); else tiles (grid = gx x coTiles)
+  int coTiles;     // channel tiles = cout_pad / (16 NF)
+  int stat_rows;   // BatchNorm partial rows the launch writes
+  int pair;        // ws_tail_pairs: the weight image the launch accepts with ConvLaunch::pair set
+};
+static inline SplitCfg split_config(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, int ksplit, bool ws_enabled) {
+  SplitCfg c;
+  const int nfr = cout_pad / 16, ks = ksplit > 1 ? ksplit : 1;
+  c.ws = split_uses_ws(Ho, Wo, ws_enabled);
+  c.NF = split_widest_nf(nfr);
+  if (c.ws) {
+    if (ks == 1) c.NF = split_pick_nf(nfr, split_ws_tiles(N, Ho, Wo));  // (split_pick_ksplit priced a split at the widest)
+    // NF <= 2: little MFMA work per tile -> 128-pixel tiles so that two workgroups share a CU and one's loads / stores
+    // overlap the other's MFMAs.  Forward only (measured per layer on one box: forward 30->30 at 256x256 169 -> 147 us,
+    // 45->30 282 -> 253 us; the data gradient of the same shapes 132 -> 145 us)
+    c.MF = (c.NF <= 2 && split_is_forward(mode)) ? 2 : 4;
+  } else {
+    c.MF = (Ho * Wo >= 1024 && c.NF >= 3) ? 4 : 2;  // 512-pixel tiles when the image is large enough to fill them
+  }
+  pick_tile_n(Ho, Wo, split_npix(c.ws, c.MF), split_maxpix(c.ws, c.MF), &c.TR, &c.TC);
+  c.tilesY = cdiv(Ho, c.TR);
+  c.tilesX = cdiv(Wo, c.TC);
+  c.coTiles = nfr / c.NF;
+  const int numTiles = N * c.tilesY * c.tilesX;
+  // ws: one workgroup per CU, two for the 128-pixel / <= 32-channel instances
+  c.gx = c.ws ? persistent_grid_x(numTiles, c.coTiles * ks, (c.MF == 2 && c.NF <= 2) ? 2 : 1) : numTiles;
+  c.stat_rows = c.gx;
+  c.pair = ws_tail_pairs(mode, cin_p, Ho, Wo, ws_enabled);
+  return c;
+}
 
 // ---- split weight gradient (wgrad_split.hip) --------------------------------------------------------------------
 constexpr int kWgTC = 32;  // pixel-tile width of the weight-gradient kernels
@@ -176,7 +318,8 @@ struct WideCfg {
   int TR, TC;
 };
 
-static inline int wide_grid_x(int numTiles, int cotiles);
+// persistent grid of the wide kernel: gx pixel-tile columns x cotiles channel tiles, one workgroup per CU
+static inline int wide_grid_x(int numTiles, int cotiles) { return persistent_grid_x(numTiles, cotiles, 1); }
 
 // Which decomposition a split16 3x3 convolution runs on.  `rows` = output channels of the launch (forward: Cout;
 // data gradient: the layer's padded input channels), Ho x Wo its output domain.
@@ -212,11 +355,9 @@ static inline WideCfg wide_config(int mode, int N, int cin_p, int rows, int Ho, 
     //   256-pixel: K padded to 32 (tap pairing: a <= 16-channel tail costs 2/3 of a chunk), channels to 16, x 1.15
     //              (its matrix pipe is ~15 % less busy)
     const int k16 = rup(cin_p, s16 ? 32 : 16);
-    int TRo, TCo;
-    pick_tile_n(Ho, Wo, 256, 360, &TRo, &TCo);
-    const double eff_o = double(Ho) * Wo / (double(cdiv(Ho, TRo)) * cdiv(Wo, TCo) * 256);
-    const int tail = cin_p - 32 * (cdiv(cin_p, 32) - 1);
-    const double k_o = 32.0 * (cdiv(cin_p, 32) - 1) + ((tail <= 16 && !s16) ? 64.0 / 3.0 : 32.0);
+    const int tiles_o1 = split_ws_tiles(1, Ho, Wo), tiles_o = N * tiles_o1;
+    const double eff_o = double(Ho) * Wo / (double(tiles_o1) * split_npix(true, 4));
+    const double k_o = 32.0 * (cdiv(cin_p, 32) - 1) + ((split_tail_short(cin_p) && !s16) ? 64.0 / 3.0 : 32.0);
     double t_w = double(k16) * (cotiles * nf * 32) / eff * (1.0 + (nf == 2 ? 1.2 : 0.2) / (k16 / (s16 ? 32 : 16)));
     // (16-bit storage modes, one MFMA per product: the 256-pixel kernel is bound by its staging there, x 1.45)
     double t_o = (s16 ? 1.45 : 1.15) * k_o * rup(rows, 16) / eff_o;
@@ -228,36 +369,23 @@ static inline WideCfg wide_config(int mode, int N, int cin_p, int rows, int Ho, 
     // (with the factor applied always, four batch-32 decisions flipped for a net +0.02 ms).
     {
       const int cu_w = wide_grid_x(tiles, cotiles) * cotiles;
-      const int nf_o = conv_pick_nfrag(rows);
-      const int cot_o = cdiv(cdiv(rows, 16), nf_o);
-      const int tiles_o = N * cdiv(Ho, TRo) * cdiv(Wo, TCo);
-      int gx_o = 256 / cot_o > 0 ? 256 / cot_o : 1;
-      if (gx_o > tiles_o) gx_o = tiles_o;
-      const int cu_o = cdiv(tiles_o, cdiv(tiles_o, gx_o)) * cot_o;
+      // (the 256-pixel kernel is priced at the channel-tile width that pads least, conv_pick_nfrag — what the fit above
+      // was made with — not at the width split_pick_nf gives the launch)
+      const int cot_o = cdiv(cdiv(rows, 16), conv_pick_nfrag(rows));
+      const int cu_o = persistent_grid_x(tiles_o, cot_o, 1) * cot_o;
       if (cu_w < 192) t_w *= 256.0 / cu_w;
       if (cu_o < 192) t_o *= 256.0 / cu_o;
     }
     // the wide kernel is persistent with one workgroup per CU and nothing overlaps its pipeline fill: it needs a
     // (pixel tile, channel tile) pair for every CU and >= 8 K chunks of work per workgroup (at 4 images per GPU the
     // 64x64 layers have 128 pairs and 30->30 at 256x256 two 2-chunk tiles per workgroup: measured 4.5 % of the step)
-    const int gx = 256 / cotiles < tiles ? (256 / cotiles > 0 ? 256 / cotiles : 1) : tiles;
-    if (tiles * cotiles < 256 || cdiv(tiles, gx) * (k16 / (s16 ? 32 : 16)) < 8 || t_w >= t_o) return c;
+    if (tiles * cotiles < 256 || cdiv(tiles, wide_grid_x(tiles, cotiles)) * (k16 / (s16 ? 32 : 16)) < 8 || t_w >= t_o) return c;
   }
   c.nf = nf;
   c.rows_pad = cotiles * nf * 32;
   c.TR = TR;
   c.TC = TC;
   return c;
-}
-
-// persistent grid of the wide kernel: gx pixel-tile columns x cotiles channel tiles, every workgroup of a launch walks
-// the same number of tiles (+-1)
-static inline int wide_grid_x(int numTiles, int cotiles) {
-  int gx = 256 / cotiles;
-  if (gx < 1) gx = 1;
-  if (gx > numTiles) gx = numTiles;
-  const int per = cdiv(numTiles, gx);
-  return cdiv(numTiles, per);
 }
 
 }  // namespace sched

@@ -7,8 +7,12 @@
 //   * weight-gradient channel tiles / split counts: >= 1, slabs within the plan's scratch formula
 //   * conv_cout_pad: covers the channels, multiple of the fragment width
 //   * w16_scale / wg_dz_scale (round 5): exact powers of two, reciprocal pairs, scaled maxima inside fp16's range
+//   * 256-pixel split convolution (split_config, split_pick_ksplit, ws_tail_pairs, split_fuses_input)
+//     and wide_config: equal, field by field, to the launch code they replaced (namespace frozen below) over a sweep of
+//     modes, switches, batches, domains and channel counts; grid invariants over the same sweep
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "../../mimo_unet_amd/csrc/tile_sched.h"
@@ -78,6 +82,187 @@ static void test_tiles() {
       }
 }
 
+// ---- The launch rules of conv_bf16x3.hip and wide_config as they stood before they moved into tile_sched.h, written
+// out plainly: the split convolution's private dispatch (launch_ws, launch_bf16x3, conv3x3_split_dispatch,
+// conv3x3_ksplit, conv3x3_pair_tail, conv3x3_split_fuses_input) with its
+// environment switches as arguments, and wide_config with its literals.  Frozen: a deliberate change of a rule changes
+// this copy with it.
+namespace frozen {
+static int imin(int a, int b) { return a < b ? a : b; }
+static int imax(int a, int b) { return a > b ? a : b; }
+
+static int pair_tail(int mode, int cin_p, int Ho, int Wo, bool ws_enabled) {
+  if (mode < 0 || mode > 1 || !ws_enabled || Ho * Wo < 256) return 0;
+  const int tail = cin_p - 32 * (cdiv(cin_p, 32) - 1);
+  return tail <= 16 ? 1 : 0;
+}
+static int fuses_input(int mode, int wide, int Ho, int Wo, bool ws_enabled) {
+  return mode == 1 && (wide != 0 || (ws_enabled && Ho * Wo >= 256)) ? 1 : 0;
+}
+
+struct Launch {
+  bool ws;
+  int MF, NF, TR, TC, tilesY, tilesX, gx, coTiles, rows;
+};
+// launch_ws<NF, MODE, MF>: tile of 64 MF pixels in 360 / 180 LDS rows, grid = gx * coTiles * ksplit
+static Launch launch_ws(int NF, int MF, int N, int cout_pad, int Ho, int Wo, int a_ksplit) {
+  Launch l;
+  l.ws = true, l.MF = MF, l.NF = NF;
+  pick_tile_n(Ho, Wo, 64 * MF, MF == 4 ? 360 : 180, &l.TR, &l.TC);
+  l.tilesY = cdiv(Ho, l.TR), l.tilesX = cdiv(Wo, l.TC);
+  const int numTiles = N * l.tilesY * l.tilesX;
+  l.coTiles = cout_pad / (NF * 16);
+  const int kWgPerCU = (MF == 2 && NF <= 2) ? 2 : 1;
+  const int ksplit = a_ksplit > 1 ? a_ksplit : 1;
+  int gx = imax(1, 256 * kWgPerCU / (l.coTiles * ksplit));
+  if (gx > numTiles) gx = numTiles;
+  const int per = cdiv(numTiles, gx);
+  gx = cdiv(numTiles, per);
+  l.rows = gx;
+  l.gx = gx;
+  return l;
+}
+// launch_bf16x3<MF, NF, MODE>: tile of 128 MF pixels in 640 / 360 LDS rows, grid = (tiles, channel tiles)
+static Launch launch_bf16x3(int MF, int NF, int N, int cout_pad, int Ho, int Wo) {
+  Launch l;
+  l.ws = false, l.MF = MF, l.NF = NF;
+  pick_tile_n(Ho, Wo, 8 * MF * 16, MF == 4 ? 640 : 360, &l.TR, &l.TC);
+  l.tilesY = cdiv(Ho, l.TR), l.tilesX = cdiv(Wo, l.TC);
+  l.rows = N * l.tilesY * l.tilesX;
+  l.gx = N * l.tilesY * l.tilesX;
+  l.coTiles = cout_pad / (NF * 16);
+  return l;
+}
+static Launch dispatch(int mode, int N, int cout_pad, int Ho, int Wo, int a_ksplit, bool ws_enabled) {
+  const int nfr = cout_pad / 16;
+  int nf = 4;
+  while (nfr % nf != 0) --nf;
+  if (ws_enabled && Ho * Wo >= 256) {
+    if (a_ksplit <= 1) {
+      int TR, TC;
+      pick_tile_n(Ho, Wo, 256, 360, &TR, &TC);
+      const int numTiles = N * cdiv(Ho, TR) * cdiv(Wo, TC);
+      long best = -1;
+      for (int c = 4; c >= 1; --c) {
+        if (nfr % c) continue;
+        const int gx = imax(1, imin(numTiles, 256 / (nfr / c)));
+        const long cost = (long)cdiv(numTiles, gx) * (1 + c);
+        if (best < 0 || cost < best) best = cost, nf = c;
+      }
+    }
+    const bool mf2 = (mode == 1 || mode == 2 || mode == 4 || mode == 6);
+    switch (nf) {
+      case 4: return launch_ws(4, 4, N, cout_pad, Ho, Wo, a_ksplit);
+      case 3: return launch_ws(3, 4, N, cout_pad, Ho, Wo, a_ksplit);
+      case 2: return launch_ws(2, mf2 ? 2 : 4, N, cout_pad, Ho, Wo, a_ksplit);
+      default: return launch_ws(1, mf2 ? 2 : 4, N, cout_pad, Ho, Wo, a_ksplit);
+    }
+  }
+  const bool use_big_tile = Ho * Wo >= 1024;
+  return launch_bf16x3(use_big_tile && nf >= 3 ? 4 : 2, nf, N, cout_pad, Ho, Wo);
+}
+
+static int ksplit(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, bool ws_enabled, int force) {
+  if (force == 0 || (mode != 0 && mode != 1) || !ws_enabled || Ho * Wo < 256 || cin_p % 32 != 0 || cout_pad % 16 != 0) return 1;
+  const int nchunks = cin_p / 32;
+  if (nchunks < 2) return 1;
+  auto legal = [&](int ks) { return ks >= 2 && cdiv(nchunks, ks) * (ks - 1) < nchunks; };
+  if (force >= 2) {
+    int ks = imin(force, nchunks);
+    while (ks >= 2 && !legal(ks)) --ks;
+    return ks >= 2 ? ks : 1;
+  }
+  int TR, TC;
+  pick_tile_n(Ho, Wo, 256, 360, &TR, &TC);
+  const int numTiles = N * cdiv(Ho, TR) * cdiv(Wo, TC);
+  const int nfr = cout_pad / 16;
+  long unsplit = -1;
+  for (int c = 4; c >= 1; --c) {
+    if (nfr % c) continue;
+    const int gx = imax(1, imin(numTiles, 256 / (nfr / c)));
+    const long cost = (long)cdiv(numTiles, gx) * (1 + c) * nchunks * 3;
+    if (unsplit < 0 || cost < unsplit) unsplit = cost;
+  }
+  int nf = 4;
+  while (nfr % nf != 0) --nf;
+  const int coTiles = nfr / nf;
+  int best = 1;
+  long best_cost = -1;
+  for (int ks = 2; ks <= 8 && ks <= nchunks; ++ks) {
+    if (!legal(ks) || coTiles * ks > 256) continue;
+    const int gx = imax(1, imin(numTiles, 256 / (coTiles * ks)));
+    const long cost = (long)cdiv(numTiles, gx) * (1 + nf) * cdiv(nchunks, ks) * 3 + 14;
+    if (best_cost < 0 || cost < best_cost) best_cost = cost, best = ks;
+  }
+  return (best_cost >= 0 && best_cost * 100 < unsplit * 85) ? best : 1;
+}
+static size_t ksplit_scratch(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, int ldy, bool ws_enabled, int force) {
+  const int ks = ksplit(mode, N, cin_p, cout_pad, Ho, Wo, ws_enabled, force);
+  return ks > 1 ? (size_t)ks * N * Ho * Wo * ldy : 0;
+}
+// rows the plan's cap_partial holds for a layer: max(conv3x3_stat_rows, conv3x3_ws_stat_rows)
+static int stat_rows(int N, int Ho, int Wo) {
+  int TR, TC;
+  pick_tile_n(Ho, Wo, 256, 360, &TR, &TC);
+  return N * cdiv(Ho, TR) * cdiv(Wo, TC);
+}
+static int ws_stat_rows() { return 512 * 4; }
+
+static int wide_grid_x(int numTiles, int cotiles) {
+  int gx = 256 / cotiles;
+  if (gx < 1) gx = 1;
+  if (gx > numTiles) gx = numTiles;
+  const int per = cdiv(numTiles, gx);
+  return cdiv(numTiles, per);
+}
+static WideCfg wide_config(int mode, int N, int cin_p, int rows, int Ho, int Wo, int force) {
+  WideCfg c{0, 0, 0, 0};
+  const bool s16 = mode >= 4 && mode <= 7;
+  if (force < 0 || !(mode == 0 || mode == 1 || s16) || rows < 1 || cin_p < 16 || Ho < 2 || Wo < 2) return c;
+  if (s16 && cin_p % 8 != 0) return c;
+  if (mode == 0 && rows % 8 != 0) return c;
+  if (int64_t(Ho + 2) * int64_t(Wo + 2) * int64_t(cin_p < rows ? rows : cin_p) * 8 > int64_t(INT32_MAX)) return c;
+  int TR, TC;
+  pick_tile_n(Ho, Wo, 512, 640, &TR, &TC);
+  if ((TR + 2) * (TC + 2) > 640) return c;
+  const int tiles = N * cdiv(Ho, TR) * cdiv(Wo, TC);
+  const double eff = double(N) * Ho * Wo / (double(tiles) * 512);
+  const int r32 = cdiv(rows, 32);
+  const int nf = (r32 >= 2 && double(rup(r32, 2)) / r32 <= 1.10 + 1e-9) ? 2 : 1;
+  const int cotiles = cdiv(r32, nf);
+  if (force == 0) {
+    const int k16 = rup(cin_p, s16 ? 32 : 16);
+    int TRo, TCo;
+    pick_tile_n(Ho, Wo, 256, 360, &TRo, &TCo);
+    const double eff_o = double(Ho) * Wo / (double(cdiv(Ho, TRo)) * cdiv(Wo, TCo) * 256);
+    const int tail = cin_p - 32 * (cdiv(cin_p, 32) - 1);
+    const double k_o = 32.0 * (cdiv(cin_p, 32) - 1) + ((tail <= 16 && !s16) ? 64.0 / 3.0 : 32.0);
+    double t_w = double(k16) * (cotiles * nf * 32) / eff * (1.0 + (nf == 2 ? 1.2 : 0.2) / (k16 / (s16 ? 32 : 16)));
+    double t_o = (s16 ? 1.45 : 1.15) * k_o * rup(rows, 16) / eff_o;
+    {
+      const int cu_w = wide_grid_x(tiles, cotiles) * cotiles;
+      const int nf_o = conv_pick_nfrag(rows);
+      const int cot_o = cdiv(cdiv(rows, 16), nf_o);
+      const int tiles_o = N * cdiv(Ho, TRo) * cdiv(Wo, TCo);
+      int gx_o = 256 / cot_o > 0 ? 256 / cot_o : 1;
+      if (gx_o > tiles_o) gx_o = tiles_o;
+      const int cu_o = cdiv(tiles_o, cdiv(tiles_o, gx_o)) * cot_o;
+      if (cu_w < 192) t_w *= 256.0 / cu_w;
+      if (cu_o < 192) t_o *= 256.0 / cu_o;
+    }
+    const int gx = 256 / cotiles < tiles ? (256 / cotiles > 0 ? 256 / cotiles : 1) : tiles;
+    if (tiles * cotiles < 256 || cdiv(tiles, gx) * (k16 / (s16 ? 32 : 16)) < 8 || t_w >= t_o) return c;
+  }
+  c.nf = nf;
+  c.rows_pad = cotiles * nf * 32;
+  c.TR = TR;
+  c.TC = TC;
+  return c;
+}
+}  // namespace frozen
+
+static bool same_wide(const WideCfg& a, const WideCfg& b) { return a.nf == b.nf && a.rows_pad == b.rows_pad && a.TR == b.TR && a.TC == b.TC; }
+
 struct Layer {
   int cin, cout, h;
 };
@@ -113,6 +298,7 @@ static void test_layers() {
           const bool fwd = mode == 1 || mode == 4;
           const int K = fwd ? cin_p : cout_p, R = fwd ? cout_p : cin_p, Ho = fwd ? L.h : L.h + 2;
           const WideCfg c = wide_config(mode, N, K, R, Ho, Ho, force);
+          CHECK(same_wide(c, frozen::wide_config(mode, N, K, R, Ho, Ho, force)), "wide_config mode %d N %d %d->%d @%d force %d", mode, N, K, R, Ho, force);
           if (c.nf == 0) continue;
           CHECK((c.nf == 1 || c.nf == 2) && c.rows_pad >= R && c.rows_pad % (32 * c.nf) == 0 && c.rows_pad < R + 64,
                 "wide rows: %d->%d nf %d rows_pad %d", K, R, c.nf, c.rows_pad);
@@ -147,6 +333,84 @@ static void test_layers() {
           }
         }
     }
+}
+
+// 256-pixel split convolution: every decision equal to the frozen launch code's, and the grid invariants
+static void test_split_rules() {
+  std::vector<std::pair<int, int>> domains;
+  for (int h : {2, 3, 4, 8, 15, 16, 17, 18, 30, 31, 32, 33, 34, 64, 66, 128, 130, 256, 258}) domains.push_back({h, h});
+  for (auto d : {std::pair<int, int>{31, 33}, {33, 31}, {15, 17}, {17, 15}, {16, 18}, {8, 32}, {32, 8}, {2, 128}, {128, 2}, {2, 258},
+                 {258, 2}, {37, 53}, {39, 55}, {64, 96}, {66, 98}, {32, 34}, {130, 258}})
+    domains.push_back(d);
+  std::vector<int> cins;
+  for (int c : {4, 8, 16, 32, 48, 64, 96, 128, 240, 480})
+    for (int d : {0, 4, 8}) cins.push_back(c + d);
+  long cases = 0, splits = 0, paired = 0, ws_launches = 0;
+  for (int mode = 0; mode <= 7; ++mode)
+    for (int ws = 0; ws <= 1; ++ws)
+      for (int N : {1, 2, 4, 32})
+        for (auto [Ho, Wo] : domains) {
+          for (int wide = 0; wide <= 1; ++wide)
+            CHECK(split_fuses_input(mode, wide, Ho, Wo, ws != 0) == frozen::fuses_input(mode, wide, Ho, Wo, ws != 0),
+                  "fuses_input mode %d wide %d %dx%d ws %d", mode, wide, Ho, Wo, ws);
+          for (int cin_p : cins) {
+            const int pair = ws_tail_pairs(mode, cin_p, Ho, Wo, ws != 0);
+            CHECK(pair == frozen::pair_tail(mode, cin_p, Ho, Wo, ws != 0), "pair mode %d cin_p %d %dx%d ws %d: %d", mode, cin_p, Ho, Wo, ws, pair);
+            paired += pair;
+            for (int cout_pad = 16; cout_pad <= 512; cout_pad += 16) {
+              if (ws == 1)  // (wide_config knows no switch of the split kernel: once per geometry)
+                for (int wf = -1; wf <= 1; ++wf)
+                  CHECK(same_wide(wide_config(mode, N, cin_p, cout_pad, Ho, Wo, wf), frozen::wide_config(mode, N, cin_p, cout_pad, Ho, Wo, wf)),
+                        "wide_config mode %d N %d %d->%d %dx%d force %d", mode, N, cin_p, cout_pad, Ho, Wo, wf);
+              for (int force : {-1, 0, 2, 3, 8}) {
+                ++cases;
+                const int ks = split_pick_ksplit(mode, N, cin_p, cout_pad, Ho, Wo, ws != 0, force);
+                CHECK(ks == frozen::ksplit(mode, N, cin_p, cout_pad, Ho, Wo, ws != 0, force), "ksplit mode %d N %d %d->%d %dx%d ws %d force %d: %d",
+                      mode, N, cin_p, cout_pad, Ho, Wo, ws, force, ks);
+                const int ldy = cout_pad - 8;  // (any pixel pitch: the stored channels of the layer)
+                CHECK(ksplit_scratch_floats(ks, N, Ho, Wo, ldy) == frozen::ksplit_scratch(mode, N, cin_p, cout_pad, Ho, Wo, ldy, ws != 0, force),
+                      "ksplit scratch mode %d N %d %d->%d %dx%d", mode, N, cin_p, cout_pad, Ho, Wo);
+                const SplitCfg c = split_config(mode, N, cin_p, cout_pad, Ho, Wo, ks, ws != 0);
+                const frozen::Launch f = frozen::dispatch(mode, N, cout_pad, Ho, Wo, ks, ws != 0);
+                CHECK(c.ws == f.ws && c.MF == f.MF && c.NF == f.NF && c.TR == f.TR && c.TC == f.TC && c.tilesY == f.tilesY && c.tilesX == f.tilesX &&
+                          c.gx == f.gx && c.coTiles == f.coTiles && c.stat_rows == f.rows && c.pair == pair,
+                      "split_config mode %d N %d %d->%d %dx%d ws %d ksplit %d: ws %d MF %d NF %d tile %dx%d gx %d coTiles %d rows %d (frozen: ws %d MF %d "
+                      "NF %d tile %dx%d gx %d coTiles %d rows %d)",
+                      mode, N, cin_p, cout_pad, Ho, Wo, ws, ks, c.ws, c.MF, c.NF, c.TR, c.TC, c.gx, c.coTiles, c.stat_rows, f.ws, f.MF, f.NF, f.TR, f.TC,
+                      f.gx, f.coTiles, f.rows);
+                // --- invariants
+                const int numTiles = N * c.tilesY * c.tilesX;
+                CHECK(c.gx >= 1 && c.gx <= numTiles && (long)c.gx * c.coTiles * ks >= 1, "grid: gx %d of %d tiles, %d channel tiles, ksplit %d", c.gx,
+                      numTiles, c.coTiles, ks);
+                CHECK(c.coTiles * c.NF * 16 == cout_pad && c.TR * c.TC <= split_npix(c.ws, c.MF) && (c.TR + 2) * (c.TC + 2) <= split_maxpix(c.ws, c.MF),
+                      "tile %dx%d, %d x %d channels of %d", c.TR, c.TC, c.coTiles, c.NF * 16, cout_pad);
+                if (c.gx >= 1 && c.gx <= numTiles) {  // column v walks tiles v, v + gx, ...: ceil(numTiles / gx) or one fewer, never none
+                  const int per = cdiv(numTiles, c.gx), last = (numTiles - 1 - (c.gx - 1)) / c.gx + 1;
+                  CHECK((numTiles - 1) / c.gx + 1 == per && (last == per || last == per - 1) && last >= 1, "walk: %d tiles on %d columns", numTiles, c.gx);
+                }
+                if (ks > 1) {
+                  ++splits;
+                  CHECK(c.ws && cin_p % 32 == 0 && ksplit_legal(cin_p / 32, ks) && c.coTiles * ks <= 256 && !pair, "ksplit %d of %d chunks, %d channel tiles",
+                        ks, cin_p / 32, c.coTiles);
+                  // every split has a chunk: the kernel's nck = min(cpk, nchunks - ks' * cpk) >= 1 for the last split
+                  CHECK(cin_p / 32 - (ks - 1) * cdiv(cin_p / 32, ks) >= 1, "ksplit %d: the last split is empty", ks);
+                }
+                CHECK(c.stat_rows <= (c.ws ? kWsStatRows : conv_stat_rows(N, Ho, Wo)), "statistics rows %d > the plan's %d", c.stat_rows,
+                      c.ws ? kWsStatRows : conv_stat_rows(N, Ho, Wo));
+                ws_launches += c.ws;
+              }
+            }
+          }
+        }
+  CHECK(kWsStatRows == frozen::ws_stat_rows(), "ws statistics rows %d", kWsStatRows);
+  for (auto [Ho, Wo] : domains)
+    for (int N : {1, 2, 4, 32}) CHECK(conv_stat_rows(N, Ho, Wo) == frozen::stat_rows(N, Ho, Wo), "conv_stat_rows N %d %dx%d", N, Ho, Wo);
+  // the sweep reached every branch
+  CHECK(cases > 1000000 && splits > 1000 && paired > 100 && ws_launches > 100000 && ws_launches < cases, "sweep: %ld cases, %ld K splits, %ld paired, %ld ws",
+        cases, splits, paired, ws_launches);
+  // the wide kernel's grid is the same rule with one workgroup per CU
+  for (int tiles = 1; tiles <= 3000; tiles += (tiles < 600 ? 1 : 37))
+    for (int cot = 1; cot <= 300; ++cot) CHECK(wide_grid_x(tiles, cot) == frozen::wide_grid_x(tiles, cot), "wide_grid_x(%d, %d)", tiles, cot);
 }
 
 // Dispatch decisions the measurements stand on (profiles/r03/conv_layers_ab.txt): a change of the
@@ -254,6 +518,7 @@ int main() {
   test_wide_offset_guard();
   test_tiles();
   test_layers();
+  test_split_rules();
   test_pinned_decisions();
   if (failures) {
     std::printf("%d check(s) failed\n", failures);

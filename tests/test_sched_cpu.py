@@ -47,12 +47,21 @@ def test_pack_layout_under_asan_ubsan(tmp_path):
 
 
 def test_kernels_use_the_tested_header():
-    """No private copy of a scheduler is left in the .hip sources."""
+    """No private copy of a scheduler is left in the .hip sources.  conv_bf16x3.hip reaches the channel-tile width
+    (sched::split_pick_nf), the tile shape and the grid through sched::split_config alone: it picks no tile, prices nothing
+    and reads its two switches in one place each."""
     csrc = os.path.join(ROOT, "mimo_unet_amd", "csrc")
-    for fn, needles in (("conv_bf16x3.hip", ["using sched::pick_tile_n"]), ("conv3x3.hip", ["sched::pick_tile_n", "sched::conv_cout_pad"]),
+    for fn, needles in (("conv_bf16x3.hip", ["sched::split_config", "sched::split_pick_ksplit", "sched::ws_tail_pairs", "sched::split_fuses_input",
+                                             "sched::ksplit_legal", "sched::ksplit_scratch_floats", "sched::split_maxpix", "sched::kWsStatRows"]), ("conv3x3.hip", ["sched::pick_tile_n", "sched::conv_cout_pad", "sched::conv_stat_rows"]),
                         ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy", "sched::GraphReplayPolicy", "pack::make_job", "pack::image_elems"]),
                         ("ops_api.hip", ["pack::make_job", "pack::image_elems"]),("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
                         ("conv_wide.hip", ["sched::wide_config", "sched::wide_grid_x"])):
         text = open(os.path.join(csrc, fn)).read()
         for n in needles:
             assert n in text, (fn, n)
+    split = open(os.path.join(csrc, "conv_bf16x3.hip")).read()
+    for gone in ("pick_tile_n", "use_big_tile", "kKsplitReduceUnits", "kWgPerCU", "(1 + c)", "(1 + nf)", "tail <= 16"):
+        assert gone not in split, gone
+    assert split.count('getenv("MIMO_CONV_WS")') == 2 and split.count('getenv("MIMO_CONV_KSPLIT")') == 1  # one statement each
+    header = open(os.path.join(csrc, "tile_sched.h")).read()
+    assert "getenv" not in header and "hip/" not in header
