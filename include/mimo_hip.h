@@ -738,6 +738,35 @@ int mimo_monitor_grid_shape(int count, int h, int w, int nrow, int padding, int*
 size_t mimo_monitor_scratch_bytes(int n_panels);
 int mimo_monitor_grids(const mimo_monitor_panel* panels, int n_panels, uint8_t* out, void* scratch, mimo_stream stream);
 
+/* ---- resident data path: a batch gathered on the device from a dataset kept in HBM as the bytes it is stored in.
+ * Replaces, per step, the reference's per-sample __getitem__ (mimo/datasets/nyuv2.py:38-53: index through
+ * shuffle_permutation, `/ 255.0` in float64, torch.tensor, permute(2, 0, 1), .float()), the DataLoader's collate and the
+ * upload of the batch: one launch for all fields (image, label) of the batch.
+ *
+ * Per field f, batch row b, channel k, pixel (y, x):
+ *   i = clamp(index[b], 0, n_samples - 1);  j = remap ? clamp(remap[i], 0, n_samples - 1) : i;
+ *   dst_f[b, k, y, x] = lut_f[src_f[j, y, x, k]]
+ * The clamps are part of the definition: no address is formed from an index outside the store, whatever the caller passes.
+ * The normalisation is the table: (arange(256) / divisor) rounded once to fp32 reproduces the reference's float64 quotient
+ * followed by .float() bit for bit; float(i) is the identity (normalize=False).
+ *
+ * `fields` is a HOST array and travels in the kernel arguments; src, lut, dst, index and remap are device memory.  All
+ * fields share n_samples, batch, h and w.  A field whose src is 4-byte aligned, with h * w a multiple of 4, is read in
+ * dwords, any other in bytes; a destination quad on a 16-byte boundary is written as one float4, any other as scalars.
+ * No allocation, no synchronisation.  MIMO_ERR_INVALID with a message and nothing launched: n_fields outside 1 ... 4, c
+ * outside 1 ... 4, a null fields / index / src / lut / dst, a lut or dst that is not 4-byte aligned, batch, h, w or
+ * n_samples < 1, batch * h * w * 4 >= 2^31, n_samples * h * w * 4 > 2^62. */
+typedef struct mimo_gather_field {
+  const uint8_t* src;    /* [n_samples, h, w, c] bytes, contiguous */
+  const float* lut;      /* 256 floats */
+  float* dst;            /* [batch, c, h, w] fp32, contiguous */
+  int32_t c;             /* 1 ... 4 */
+  int32_t reserved;
+} mimo_gather_field;
+enum { MIMO_GATHER_MAX_FIELDS = 4 };
+int mimo_dataset_gather(const mimo_gather_field* fields, int n_fields, const int64_t* index, const int64_t* remap,
+                        int64_t n_samples, int32_t batch, int32_t h, int32_t w, mimo_stream stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -120,6 +120,11 @@ class MonitorPanel(C.Structure):
     ]
 
 
+class GatherField(C.Structure):
+    """mimo_gather_field (include/mimo_hip.h)"""
+    _fields_ = [("src", C.c_void_p), ("lut", C.c_void_p), ("dst", C.c_void_p), ("c", C.c_int32), ("reserved", C.c_int32)]
+
+
 LOSS_KINDS = {"laplace_nll": 0, "gaussian_nll": 1}
 # "bf16-mixed" / "16-mixed": Lightning's names for bf16 / fp16 autocast training — here 16-bit storage + operands
 PRECISIONS = {"fp32": 0, "split16": 1, "bf16": 2, "bf16-mixed": 3, "16-mixed": 4}
@@ -201,6 +206,7 @@ _SIGNATURES = {
     "mimo_monitor_grid_shape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mimo_monitor_scratch_bytes": (C.c_size_t, [C.c_int]),
     "mimo_monitor_grids": (C.c_int, [C.POINTER(MonitorPanel), C.c_int, _P, _P, _P]),
+    "mimo_dataset_gather": (C.c_int, [C.POINTER(GatherField), C.c_int, _P, _P, _L, _I, _I, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

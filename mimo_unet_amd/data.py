@@ -45,14 +45,24 @@ The layout change NCHW -> NHWC (and the per-subnetwork gather) is not done here:
 engine's first kernel (`pack_input_kernel`) reads the NCHW batch as uploaded.
 
 A yielded batch stays valid until the next one is drawn — the contract of a training loop
-that uses each batch for one step."""
+that uses each batch for one step.
+
+`ResidentDataset` / `ResidentLoader` are the route without a host pipeline, for a dataset that
+fits in HBM as the bytes it is stored in (NYUv2: uint8 ``[N,H,W,3]`` images and ``[N,H,W,1]``
+depth, a few GB): the arrays are uploaded once, and a batch is one `mimo_dataset_gather` launch
+(csrc/data/dataset_gather.hip: gather by index, 256-entry table, HWC -> NCHW) on the training stream
+right in front of the step — no workers, no collation, no pinned staging, no copy per step and
+no host synchronisation inside an epoch.  The table is ``(arange(256) / divisor)`` rounded once
+to fp32, i.e. the reference's float64 quotient followed by ``.float()``, so a resident batch
+equals the collated host batch bit for bit."""
 from __future__ import annotations
 
 import os
 import queue
 import threading
-from typing import Any, Dict, Iterable, Iterator, Optional
+from typing import Any, Dict, Iterable, Iterator, Mapping, Optional, Tuple
 
+import numpy as np
 import torch
 
 
@@ -203,3 +213,120 @@ class DevicePrefetcher:
                 # iteration already owns the ring: it released this slot when it started.)
                 self._release(previous)
             free_q.put(_STOP)  # a consumer that stops early leaves no worker waiting for a slot
+
+
+# ---------------------------------------------------------------------------------------------------- resident data path
+def normalisation_table(divisor: Optional[float]) -> np.ndarray:
+    """The 256 floats a byte maps to: ``byte / divisor`` in float64 rounded once to fp32 (what ``__getitem__``'s
+    ``array / 255.0`` followed by ``.float()`` gives), or the byte as a float for ``divisor=None``.  Not
+    ``float32(byte) * float32(1 / divisor)``: for 255 that differs from the quotient in 126 of the 256 values."""
+    ramp = np.arange(256)
+    return (ramp if divisor is None else ramp / divisor).astype(np.float32)
+
+
+def epoch_indices(n: int, epoch: int, shuffle: bool, seed: int = 0, rank: int = 0, world_size: int = 1) -> torch.Tensor:
+    """Sample order of one rank in one epoch (int64, host): a CPU ``randperm`` from a generator seeded ``seed + epoch`` —
+    the same permutation on every rank — or ``arange(n)``, then the rank's strided share ``order[rank::world_size]``.
+    The shares are disjoint and cover the set; their lengths differ by at most one."""
+    if not 0 <= rank < world_size:
+        raise ValueError(f"epoch_indices: rank {rank} outside [0, {world_size})")
+    if shuffle:
+        order = torch.randperm(n, generator=torch.Generator().manual_seed(seed + epoch))
+    else:
+        order = torch.arange(n)
+    return order[rank::world_size]
+
+
+class ResidentDataset:
+    """Byte arrays of a dataset in HBM, and batches gathered from them by one launch.
+
+    fields: name -> (uint8 array [N,H,W,c] with c in 1..4, divisor or None); all over the same N, H, W.
+    remap: optional int array of sample numbers (a dataset's ``shuffle_permutation``): item i is sample ``remap[i]``.  A
+    remap over all N samples is uploaded and applied by the kernel; a shorter one (``use_fraction < 1``) selects the
+    samples on the host, so only those are uploaded."""
+
+    def __init__(self, fields: Mapping[str, Tuple[Any, Optional[float]]], remap=None, device="cuda") -> None:
+        from . import _lib
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("ResidentDataset keeps the data in the memory of an AMD GPU; got device " + str(device))
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if not 1 <= len(fields) <= 4:
+            raise ValueError(f"ResidentDataset: {len(fields)} fields (1 ... 4 per launch)")
+        arrays = {k: np.asarray(a) for k, (a, _) in fields.items()}
+        shape = next(iter(arrays.values())).shape[:3]
+        for k, a in arrays.items():
+            if a.dtype != np.uint8 or a.ndim != 4 or a.shape[:3] != shape or not 1 <= a.shape[3] <= 4 or a.shape[0] < 1:
+                raise ValueError(f"ResidentDataset: field {k!r} is {a.dtype} {a.shape}; uint8 [N,H,W,c] with c in 1..4 over "
+                                 f"[N,H,W] = {list(shape)} is needed")
+        if remap is not None:
+            remap = np.asarray(remap, dtype=np.int64)
+            if remap.ndim != 1 or len(remap) < 1 or remap.min() < 0 or remap.max() >= shape[0]:
+                raise ValueError(f"ResidentDataset: remap must hold sample numbers in [0, {shape[0]})")
+            if len(remap) != shape[0]:
+                arrays, remap = {k: a[remap] for k, a in arrays.items()}, None
+        self.n_samples, self.h, self.w = (int(v) for v in next(iter(arrays.values())).shape[:3])
+        self.channels = {k: int(a.shape[3]) for k, a in arrays.items()}
+        self.src = {k: torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for k, a in arrays.items()}
+        self.lut = {k: torch.from_numpy(normalisation_table(d)).to(self.device) for k, (_, d) in fields.items()}
+        self.remap = None if remap is None else torch.from_numpy(remap).to(self.device)
+        self._lib = _lib
+
+    def __len__(self) -> int:
+        return self.n_samples
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() for t in self.src.values())
+
+    def gather(self, index: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """name -> fp32 ``[B,c,H,W]`` for the int64 device tensor ``index [B]``: one launch on the current stream, into
+        fresh tensors (step outputs and deferred image logging keep references to batch tensors beyond the step)."""
+        if index.dtype != torch.int64 or index.device != self.device or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError(f"gather: index must be a contiguous int64 [B] tensor on {self.device}, got {index.dtype} "
+                             f"{list(index.shape)} on {index.device}")
+        batch = int(index.shape[0])
+        out = {k: torch.empty((batch, c, self.h, self.w), dtype=torch.float32, device=self.device)
+               for k, c in self.channels.items()}
+        if batch == 0:
+            return out
+        table = (self._lib.GatherField * len(out))(*(
+            self._lib.GatherField(self.src[k].data_ptr(), self.lut[k].data_ptr(), out[k].data_ptr(), c, 0)
+            for k, c in self.channels.items()))
+        with torch.cuda.device(self.device):
+            self._lib.check(self._lib.load().mimo_dataset_gather(
+                table, len(out), index.data_ptr(), self._lib.ptr(self.remap), self.n_samples, batch, self.h, self.w,
+                self._lib.current_stream()), "mimo_dataset_gather")
+        return out
+
+
+class ResidentLoader:
+    """Iterates a `ResidentDataset` like a ``DataLoader`` over the host dataset: dicts name -> fp32 ``[B,c,H,W]``, on the
+    device.  The order of an epoch is `epoch_indices`, uploaded once when the iteration starts; each step's indices are
+    a slice of that device tensor.  ``set_epoch(e)`` selects the epoch of the next iteration; every iteration leaves the
+    epoch advanced by one, so a loop that never calls it still sees a new order per epoch."""
+
+    def __init__(self, dataset: ResidentDataset, batch_size: int, shuffle: bool = False, drop_last: bool = False,
+                 seed: int = 0, rank: int = 0, world_size: int = 1) -> None:
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        if not 0 <= rank < world_size:
+            raise ValueError(f"rank {rank} outside [0, {world_size})")
+        self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), bool(shuffle), bool(drop_last)
+        self.seed, self.rank, self.world_size = int(seed), int(rank), int(world_size)
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def __len__(self) -> int:
+        share = len(range(self.rank, len(self.dataset), self.world_size))
+        return share // self.batch_size if self.drop_last else -(-share // self.batch_size)
+
+    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        order = epoch_indices(len(self.dataset), self.epoch, self.shuffle, self.seed, self.rank, self.world_size)
+        self.epoch += 1
+        order = order.contiguous().to(self.dataset.device)
+        for k in range(len(self)):
+            yield self.dataset.gather(order[k * self.batch_size:(k + 1) * self.batch_size])

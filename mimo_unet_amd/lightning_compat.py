@@ -13,10 +13,27 @@ try:  # pragma: no cover - not installed in the build image
     import lightning.pytorch as pl
 
     LightningModule = pl.LightningModule
+    LightningDataModule = pl.LightningDataModule
     Callback = pl.Callback
     HAVE_LIGHTNING = True
 except Exception:  # ModuleNotFoundError
     HAVE_LIGHTNING = False
+
+    class LightningDataModule:
+        """The hooks of lightning.pytorch.LightningDataModule a hand-written loop calls, in Lightning's order:
+        prepare_data, setup(stage), the *_dataloader methods, teardown(stage)."""
+
+        def __init__(self) -> None:
+            self.trainer = None
+
+        def prepare_data(self) -> None:
+            pass
+
+        def setup(self, stage=None) -> None:
+            pass
+
+        def teardown(self, stage=None) -> None:
+            pass
 
     class Callback:
         """The hooks of lightning.pytorch.Callback that the callbacks of this package implement, as no-ops: a hand-written
