@@ -79,9 +79,7 @@ def _validate(ensemble, epsilons: Sequence[float], mc_dropout: bool = False) -> 
     """Everything that can be refused is refused here, before anything touches the GPU."""
     if _is_evidential(ensemble):  # the model itself, not an ensemble of it
         ensemble.require_eval("fgsm_sweep")
-        if ensemble.model._geom.precision not in ("fp32", "split16"):
-            raise NotImplementedError(f"fgsm_sweep: the input gradient is implemented for the fp32 and split16 precisions, not "
-                                      f"{ensemble.model._geom.precision!r}")
+        ensemble.model._require_gradient_precision("fgsm_sweep: the input gradient is")
         return _validate_epsilons(epsilons)
     if getattr(ensemble, "monte_carlo_steps", 0) > 0 and not mc_dropout:
         raise NotImplementedError("fgsm_sweep: MC-dropout ensembles (monte_carlo_steps > 0) are not supported: the reference "

@@ -80,6 +80,10 @@ class Plan:
         self.double_conv_channels = [int(self.lib.mimo_plan_double_conv_channels(handle, i))
                                      for i in range(self.num_double_convs)]
         self._bound = None
+        # the saved activations belong to the last forward: `generation` counts the forwards, `pending` is the generation
+        # of the autograd graph that may still back-propagate through them (None: the plan is free for the next graph)
+        self.generation = 0
+        self.pending: Optional[int] = None
         self._ext_streams: Dict[int, torch.cuda.Stream] = {}  # the plan's own HIP streams as torch streams (backward(async_stage=True))
 
     def __del__(self):
@@ -90,6 +94,21 @@ class Plan:
             except Exception:
                 pass
             self.handle = None
+
+    def begin_graph(self) -> int:
+        """An autograd graph now owns the saved activations; returns its generation (`release` frees the plan again)."""
+        self.generation += 1
+        self.pending = self.generation
+        return self.generation
+
+    def release(self, generation: int) -> None:
+        """The graph of `generation` has run its backward or was dropped (a newer graph's claim is left alone)."""
+        if self.pending == generation:
+            self.pending = None
+
+    def note_eval_call(self) -> None:
+        """An eval-mode forward outside autograd replaced the saved activations: an older graph's backward must refuse."""
+        self.generation += 1
 
     def _read_specs(self) -> List[TensorSpec]:
         out = []
@@ -214,29 +233,29 @@ class Plan:
         return None
 
     def input_gradient(self, dout: Optional[torch.Tensor], dloss: Optional[torch.Tensor], dimage: torch.Tensor,
-                       accumulate: bool = False) -> None:
+                       accumulate: bool = False, replicas: int = 0) -> None:
         """d loss / d image [N,Ci,H,W] of the image the last eval-mode forward (training=False, no_grad=False, no perm)
         broadcast to the subnetworks: the data-gradient chain only, the subnetworks' gradients summed in the order
-        s = S-1 ... 0; accumulate adds to what `dimage` holds (mimo_input_gradient).  Writes no parameter gradient."""
-        g = self.geom
-        assert dimage.is_cuda and dimage.dtype == torch.float32 and dimage.is_contiguous()
-        assert tuple(dimage.shape) == (self.batch, g.in_channels, self.height, self.width), tuple(dimage.shape)
-        L.check(self.lib.mimo_input_gradient(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
-                                             int(bool(accumulate)), L.current_stream()), "mimo_input_gradient")
-
-    def input_gradient_mc(self, dout: Optional[torch.Tensor], dloss: Optional[torch.Tensor], dimage: torch.Tensor,
-                          accumulate: bool = False, replicas: int = 1) -> None:
-        """`input_gradient` after a forward whose batch holds `replicas` MC-dropout passes of the same batch / replicas
-        images, stacked pass-major (pass m, image b at row m * B + b): dimage [B,Ci,H,W] receives the passes' gradients
-        summed in the fixed order m = 0 ... replicas-1 per subnetwork (mimo_input_gradient_mc)."""
+        s = S-1 ... 0; accumulate adds to what `dimage` holds (mimo_input_gradient).  Writes no parameter gradient.
+        replicas > 0: the batch of that forward holds `replicas` MC-dropout passes of the same batch / replicas images,
+        stacked pass-major (pass m, image b at row m * B + b), and dimage [B,Ci,H,W] receives the passes' gradients summed
+        in the fixed order m = 0 ... replicas-1 per subnetwork (mimo_input_gradient_mc)."""
         g = self.geom
         replicas = int(replicas)
-        if replicas < 1 or self.batch % replicas != 0:
+        if replicas < 0 or (replicas > 0 and self.batch % replicas != 0):
             raise ValueError(f"input_gradient_mc: replicas {replicas} does not divide the plan batch {self.batch}")
         assert dimage.is_cuda and dimage.dtype == torch.float32 and dimage.is_contiguous()
-        assert tuple(dimage.shape) == (self.batch // replicas, g.in_channels, self.height, self.width), tuple(dimage.shape)
-        L.check(self.lib.mimo_input_gradient_mc(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
-                                                int(bool(accumulate)), replicas, L.current_stream()), "mimo_input_gradient_mc")
+        assert tuple(dimage.shape) == (self.batch // max(replicas, 1), g.in_channels, self.height, self.width), tuple(dimage.shape)
+        if replicas > 0:
+            L.check(self.lib.mimo_input_gradient_mc(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
+                                                    int(bool(accumulate)), replicas, L.current_stream()), "mimo_input_gradient_mc")
+        else:
+            L.check(self.lib.mimo_input_gradient(self.handle, L.ptr(dout) or None, L.ptr(dloss) or None, dimage.data_ptr(),
+                                                 int(bool(accumulate)), L.current_stream()), "mimo_input_gradient")
+
+    def input_gradient_mc(self, dout, dloss, dimage, accumulate: bool = False, replicas: int = 1) -> None:
+        """`input_gradient` with `replicas` >= 1 (0 is refused here, not read as "no replicas")."""
+        self.input_gradient(dout, dloss, dimage, accumulate, replicas if int(replicas) > 0 else -1)
 
     PROF_KINDS = ("conv3x3_fwd", "conv3x3_dgrad", "conv3x3_wgrad", "bn_relu_fwd", "bn_bwd_reduce", "bn_bwd_apply",
                   "upcat_fwd", "up_bwd", "pool_bwd", "head_fwd", "head_bwd")

@@ -74,9 +74,7 @@ class EvidentialUnetModel(FlatAdamClipping, LightningModule):
 
     def require_eval(self, what: str) -> None:
         """Evaluation entry points run the network as `model.eval()` leaves it: BatchNorm on running statistics, dropout off."""
-        net = self.model
-        if self.training or net._bn_training() or any(d.p > 0.0 and d.training for d in net._dropout_modules()):
-            raise NotImplementedError(f"{what}: eval mode only (call model.eval(): BatchNorm on running statistics, dropout off)")
+        self.model._require_eval(what, training=self.training, hint="call model.eval(): ")
 
     def predict_uncertainties(self, image: torch.Tensor):
         """image [B,C,H,W] -> (mean, aleatoric_var, epistemic_var), each [B,1,H,W], on the device: the no-grad forward on an
@@ -97,11 +95,8 @@ class EvidentialUnetModel(FlatAdamClipping, LightningModule):
         label [B,1,H,W]; mask [B,H,W] (or the evaluators' [B,1,H,W], of which the [B,H,W] view is taken) or None."""
         self.require_eval("EvidentialUnetModel.image_gradient")
         net = self.model
-        if net._geom.precision not in ("fp32", "split16"):
-            raise NotImplementedError(f"EvidentialUnetModel.image_gradient: implemented for the fp32 and split16 precisions, "
-                                      f"not {net._geom.precision!r}")
-        if image.dim() != 4 or image.shape[1] != self.in_channels:
-            raise ValueError("channel dimension must match in_channels")
+        net._require_gradient_precision("EvidentialUnetModel.image_gradient:")
+        net._require_image(image, "channel dimension must match in_channels")
         b, _, h, w = image.shape
         if tuple(label.shape) != (b, 1, h, w):
             raise ValueError(f"label: expected {(b, 1, h, w)}, got {tuple(label.shape)}")

@@ -122,19 +122,16 @@ class _NetFunction(torch.autograd.Function):
             plan.loss_forward(label, lmask, perm, loss)
         else:
             loss = torch.zeros(0, device=x.device, dtype=torch.float32)
-        plan.generation += 1
-        ctx.net, ctx.plan, ctx.generation = net, plan, plan.generation
         # device memory the plan still points at; the output goes through save_for_backward (keeping it in a plain
         # attribute would tie ctx -> out -> grad_fn -> ctx into a cycle that only the garbage collector breaks)
         ctx.keep = (x, label, lmask, perm, masks, elem_masks)
         ctx.save_for_backward(out)
         # the plan holds the saved activations of THIS graph until its backward has run or the graph is dropped; a
         # forward of the same geometry in between gets another plan (_plan_for), like autograd keeping two graphs alive
-        plan.pending = plan.generation
-        weakref.finalize(ctx, _release_plan, plan, plan.generation)
+        ctx.net, ctx.plan, ctx.generation = net, plan, plan.begin_graph()
+        weakref.finalize(ctx, plan.release, ctx.generation)
         ctx.x_shape = x.shape
         ctx.has_loss = label is not None
-        ctx.mark_non_differentiable(*[])
         return out, loss
 
     @staticmethod
@@ -155,17 +152,26 @@ class _NetFunction(torch.autograd.Function):
         dout_c = None if dout is None else dout.contiguous().float()
         dloss_c = None if (dloss is None or not ctx.has_loss) else dloss.contiguous().float()
         net._run_backward(plan, dout_c, dloss_c, dx)
-        _release_plan(plan, ctx.generation)
+        plan.release(ctx.generation)
         return (None, dx, None, None, None, None, None, None, None) + (None,) * len(net._param_list)
-
-
-def _release_plan(plan, generation: int) -> None:
-    if getattr(plan, "pending", None) == generation:
-        plan.pending = None
 
 
 def _guard_after_load(module, incompatible_keys) -> None:
     module.guard_fp16_range()
+
+
+def _transient_state() -> dict:
+    """The transient attributes of a `MimoUNet` with their empty values (see "copies / pickles" in the class)."""
+    return {
+        "_plans": OrderedDict(),  # (batch, H, W, device, inference-only) [+ (slot,)] -> Plan, least recently used first
+        "_evicted_status": 0,  # numerics status bits of the plans dropped since the last numerics_status()
+        # _ensure_flat: the flat storage the parameters / gradients / BatchNorm buffers are views of, and what goes with it
+        "_flat_params": None, "_flat_grads": None, "_flat_buffers": None, "_flat_counters": None, "_flat_device": None,
+        "_flat_probe": None, "_param_list": [], "_param_views": None, "_versioned": [],
+        "_dc_cache": None, "_drop_cache": None, "_mask_plan": None,  # double_convs(), _dropout_modules(), _dropout_masks()
+        "_inference_keep": None,  # tensors the plan of the last eval-mode call outside autograd still points at
+        # called as hook(flat_grads, begin, end) when gradients [begin, end) are final; the reducer behind it (ddp.py)
+        "grad_ready_hook": None, "grad_sync": None}
 
 
 class MimoUNet(nn.Module):
@@ -199,20 +205,13 @@ class MimoUNet(nn.Module):
         self.engine_rng = os.environ.get("MIMO_ENGINE_RNG", "1") != "0"
         # data-parallel backward: stages without a per-stage join of the engine's two streams (engine.Plan.backward)
         self.async_stages = os.environ.get("MIMO_DDP_ASYNC_STAGES", "1") != "0"
-        # one plan per (batch, H, W, device, inference-only); least recently used plans are dropped beyond
-        # MIMO_PLAN_CACHE entries (a plan owns its whole activation workspace: ragged last batches, separate
-        # train / val batch sizes and variable image sizes would otherwise pile up multi-GB plans)
-        self._plans: "OrderedDict[tuple, Plan]" = OrderedDict()
+        # least recently used plans are dropped beyond MIMO_PLAN_CACHE entries (a plan owns its whole activation workspace:
+        # ragged last batches, separate train / val batch sizes and variable image sizes would otherwise pile up multi-GB plans)
         self._plan_cache_size = max(1, int(os.environ.get("MIMO_PLAN_CACHE", "4")))
-        self._flat_params = self._flat_grads = self._flat_buffers = None
-        self._param_list: List[nn.Parameter] = []
-        self._versioned: List[torch.Tensor] = []
-        self._flat_device = None
+        self._reset_transient()
         self.mask_override: Optional[Dict[int, torch.Tensor]] = None  # tests: {double-conv index: [N,C] multipliers}
         # tests: {"center" | "final{s}": full-shape nn.Dropout multipliers (reference NCHW layout)}
         self.elem_mask_override: Optional[Dict[str, torch.Tensor]] = None
-        # called as hook(flat_grads, begin, end) when gradients [begin, end) are final (see ddp.FlatGradientAllReducer)
-        self.grad_ready_hook = None
         # bumped by everything that rewrites the flat parameter / buffer storage behind torch's back
         # (FlatAdam's HIP kernel, the engine's running-stat update); together with the tensors' own
         # torch version counters it forms mimo_forward_args.param_version
@@ -226,26 +225,21 @@ class MimoUNet(nn.Module):
     # storage the parameters are views of, cached module lists, hooks of a data-parallel reducer.  `copy.deepcopy(model)`
     # (EMA / SWA callbacks) and `torch.save(model)` take the module tree with its parameters and buffers; the copy rebuilds
     # the rest at its first forward.
-    _TRANSIENT = {"_plans": None, "_flat_params": None, "_flat_grads": None, "_flat_buffers": None, "_flat_counters": None,
-                  "_flat_device": None, "_flat_probe": None, "_param_list": None, "_param_views": None, "_versioned": None,
-                  "_dc_cache": None, "_drop_cache": None, "_mask_plan": None, "_inference_keep": None, "grad_ready_hook": None,
-                  "grad_sync": None}
+    _TRANSIENT = tuple(_transient_state())
+
+    def _reset_transient(self) -> None:
+        self.__dict__.update(_transient_state())  # (plain attributes: none of them is a parameter, buffer or submodule)
 
     def __getstate__(self):
-        state = self.__dict__.copy()
-        for k in self._TRANSIENT:
-            state.pop(k, None)
-        return state
+        return {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
 
     def __setstate__(self, state):
         super().__setstate__(state)
-        self.__dict__.update({"_plans": OrderedDict(), "_flat_params": None, "_flat_grads": None, "_flat_buffers": None,
-                              "_flat_device": None, "_param_list": [], "_versioned": [], "grad_ready_hook": None})
+        self._reset_transient()
 
     # ---- execution order of the DoubleConvs == mimo_plan's (engine) order -----------------
     def double_convs(self) -> List[DoubleConv]:
-        dcs = self.__dict__.get("_dc_cache")
-        if dcs is None:  # (a plain attribute, not a registered submodule list: the modules stay owned by the tree above)
+        if self._dc_cache is None:  # (plain attributes, not registered submodule lists: the modules stay owned by the tree above)
             c = self.core
             dcs = ([m for m in self.encoder.in_convs] + [d.conv for d in self.encoder.down1s]
                    + [c.down2.conv, c.down3.conv, c.down4.conv, c.up1.conv, c.up2.conv, c.up3.conv]
@@ -253,12 +247,12 @@ class MimoUNet(nn.Module):
             self.__dict__["_dc_cache"] = dcs
             self.__dict__["_drop_cache"] = ([dc.double_conv[6] for dc in dcs] + [self.core.center_dropout]
                                             + list(self.decoder.final_dropouts))
-        return dcs
+        return self._dc_cache
 
     def _dropout_modules(self) -> List[nn.Module]:
         """Dropout2d of every DoubleConv in engine order, then center_dropout, then final_dropouts[s]"""
         self.double_convs()
-        return self.__dict__["_drop_cache"]
+        return self._drop_cache
 
     # ---- fp16 range guard (round 6) --------------------------------------------------------------------------------------
     # "split16" / "16-mixed" carry activations as fp16 operands: |a| >= 65 520 overflows where the reference's fp32
@@ -299,20 +293,29 @@ class MimoUNet(nn.Module):
         """"fp32" (f32-input MFMA, exact) or "split16" (split-bf16 MFMA, ~1e-5 relative per product)."""
         if precision != self._geom.precision:
             self._geom = NetGeometry(**{**self._geom.__dict__, "precision": precision})
-            for plan in self._plans.values():  # what the dropped plans recorded outlives them (numerics_status ORs it in)
-                self._evicted_status = getattr(self, "_evicted_status", 0) | plan.status(True)
-            self._plans.clear()
+            self._drop_plans()
 
     def set_loss(self, loss: str) -> None:
         if loss != self._geom.loss:
             self._geom = NetGeometry(**{**self._geom.__dict__, "loss": loss})
-            self._plans.clear()
+            self._drop_plans()
+
+    # ---- plan lifetime ----------------------------------------------------------------------
+    def _evict_oldest(self) -> None:
+        """The one way out of the cache (a pending autograd node keeps its own reference to its plan).  The plan's numerics
+        status word (a NaN on a ragged last batch, say) outlives it: numerics_status() ORs it in.  One stream synchronisation."""
+        _, old = self._plans.popitem(last=False)
+        self._evicted_status |= old.status(True)
+
+    def _drop_plans(self) -> None:
+        while self._plans:
+            self._evict_oldest()
 
     # ---- flat storage ---------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
+        self._drop_plans()  # (before the tensors move: the plans are bound to the storage they have now)
         r = super()._apply(fn, *a, **k)
         self._flat_params = None  # .to()/.cuda() re-created the tensors: re-flatten lazily
-        self._plans = OrderedDict()
         return r
 
     def _ensure_flat(self, plan: Plan, device) -> None:
@@ -371,32 +374,27 @@ class MimoUNet(nn.Module):
                                  "to cuda (there is no CPU execution path)")
         n = perm.shape[1] if perm is not None else x.shape[0]
         key = (n, x.shape[-2], x.shape[-1], x.device.index, "input-gradient" if grad_only else bool(inference))
+        if for_autograd:
+            key = self._free_slot(key)
         plan = self._plans.get(key)
-        if for_autograd and plan is not None and getattr(plan, "pending", None) is not None:
-            # an earlier graph of this geometry is still alive and may yet be back-propagated (two forwards, then the
-            # first one's backward — torch's autograd allows it): use further plans of the same geometry (key + slot)
-            slot = 1
-            while True:
-                k2 = key + (slot,)
-                p2 = self._plans.get(k2)
-                if p2 is None or getattr(p2, "pending", None) is None:
-                    key, plan = k2, p2
-                    break
-                slot += 1
         if plan is None:
             while len(self._plans) >= self._plan_cache_size:
-                # a pending autograd node keeps its own reference to its plan.  What the evicted plan recorded in its
-                # numerics status word (a NaN on a ragged last batch, say) outlives it: numerics_status() ORs it in
-                _, old = self._plans.popitem(last=False)
-                self._evicted_status = getattr(self, "_evicted_status", 0) | old.status(True)
-            plan = Plan(self._geom, n, x.shape[-2], x.shape[-1], x.device, inference_only=2 if grad_only else inference)
-            plan.generation = 0
-            plan.pending = None
-            self._plans[key] = plan
+                self._evict_oldest()
+            plan = self._plans[key] = Plan(self._geom, n, x.shape[-2], x.shape[-1], x.device,
+                                           inference_only=2 if grad_only else inference)
         else:
             self._plans.move_to_end(key)
         self._ensure_flat(plan, x.device)
         return plan
+
+    def _free_slot(self, key: tuple) -> tuple:
+        """`key`, or `key + (slot,)` for the first slot >= 1 that no live autograd graph owns: while an earlier graph of this
+        geometry may yet be back-propagated (two forwards, then the first one's backward), a forward uses a further plan."""
+        slot, k = 0, key
+        while (plan := self._plans.get(k)) is not None and plan.pending is not None:
+            slot += 1
+            k = key + (slot,)
+        return k
 
     # ---- dropout masks (Dropout2d: one Bernoulli per (sample, channel), components.py:29) --
     def _dropout_masks(self, n: int, device) -> Optional[List[Optional[torch.Tensor]]]:
@@ -420,7 +418,7 @@ class MimoUNet(nn.Module):
         if not any(p > 0.0 for p in active):
             return None
         key = (n, str(device), active)
-        cache = getattr(self, "_mask_plan", None)
+        cache = self._mask_plan
         if cache is None or cache[0] != key:
             chans = [dc.double_conv[3].out_channels for dc in dcs]
             offs, total = [], 0
@@ -474,9 +472,6 @@ class MimoUNet(nn.Module):
     def _bn_training(self) -> bool:
         return self.double_convs()[0].double_conv[1].training
 
-    def _bump_batch_counters(self) -> None:
-        self._flat_counters.add_(1)  # the 2 x #DoubleConv counters are views of this tensor (_ensure_flat)
-
     # ---- forward ----------------------------------------------------------------------------
     def _call(self, x, label, lmask, perm):
         x = x.contiguous().float()
@@ -491,13 +486,8 @@ class MimoUNet(nn.Module):
         if inference:
             # inference (eval mode under torch.no_grad()): no autograd node, BatchNorm + ReLU folded into the
             # convolution epilogue, packed weights reused while the parameters have not changed
-            out = torch.empty(n, self.num_subnetworks, self.out_channels, plan.height, plan.width, device=x.device,
-                              dtype=torch.float32)
-            plan.bind(self._flat_params, self._flat_grads, self._flat_buffers)
-            plan.forward(x, out, training=False, perm=perm, masks=masks, elem_masks=elem_masks, no_grad=True,
-                         param_version=self._param_version(), rng=rng)
-            plan.generation += 1
-            self._inference_keep = (x, perm, masks, elem_masks)  # the plan still points at the mask tensors
+            out = self._eval_forward(plan, x, grads=self._flat_grads, perm=perm, masks=masks, elem_masks=elem_masks, no_grad=True,
+                                     rng=rng)
             if label is None:
                 return out, torch.zeros(0, device=x.device, dtype=torch.float32)
             loss = torch.empty(self.num_subnetworks, device=x.device, dtype=torch.float32)
@@ -505,9 +495,38 @@ class MimoUNet(nn.Module):
             return out, loss
         out, loss = _NetFunction.apply(self, x, label, lmask, perm, masks, bn_training, elem_masks, rng, *self._param_list)
         if bn_training:
-            self._bump_batch_counters()
+            self._flat_counters.add_(1)  # the 2 x #DoubleConv num_batches_tracked are views of this tensor (_ensure_flat)
             self._param_epoch += 1  # the engine updated the running statistics in place
         return out, loss
+
+    def _eval_forward(self, plan: Plan, x: torch.Tensor, keep: tuple = (), grads: Optional[torch.Tensor] = None,
+                      **forward_args) -> torch.Tensor:
+        """The eval-mode call outside autograd (inference forward, the two input-gradient routes): the logits [N,S,Co,H,W].
+        No autograd node holds the tensors the plan points at afterwards — a loss_forward / input_gradient that follows reads
+        them through the plan — so `_inference_keep` does until the next such call: `x`, the logits, `keep`, the arguments."""
+        out = torch.empty(plan.batch, self.num_subnetworks, self.out_channels, plan.height, plan.width, device=x.device,
+                          dtype=torch.float32)
+        plan.bind(self._flat_params, grads, self._flat_buffers)
+        plan.forward(x, out, training=False, param_version=self._param_version(), **forward_args)
+        plan.note_eval_call()
+        self._inference_keep = (x, out, keep, forward_args)
+        return out
+
+    # ---- what the evaluation entry points refuse (the callers name themselves in the messages) ----
+    def _require_eval(self, who: str, allow_dropout: bool = False, training: bool = False, hint: str = "") -> None:
+        """BatchNorm on running statistics, no active dropout module unless allow_dropout; `training`: the caller's own flag"""
+        if allow_dropout and self._bn_training():
+            raise NotImplementedError(f"{who}: BatchNorm must be in eval mode (running statistics), also with mc_dropout")
+        if training or self._bn_training() or (not allow_dropout and any(d.p > 0.0 and d.training for d in self._dropout_modules())):
+            raise NotImplementedError(f"{who}: eval mode only ({hint}BatchNorm on running statistics, dropout off)")
+
+    def _require_gradient_precision(self, what: str, suffix: str = "") -> None:
+        if self._geom.precision not in ("fp32", "split16"):  # (mimo_input_gradient, include/mimo_hip.h)
+            raise NotImplementedError(f"{what} implemented for the fp32 and split16 precisions, not {self._geom.precision!r}{suffix}")
+
+    def _require_image(self, image: torch.Tensor, message: Optional[str] = None) -> None:
+        if image.dim() != 4 or image.shape[1] != self.in_channels:
+            raise ValueError(message or f"expected [B,{self.in_channels},H,W], got {tuple(image.shape)}")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x [B,S,C_in,H,W] -> predictions [B,S,C_out,H,W]."""
@@ -537,17 +556,12 @@ class MimoUNet(nn.Module):
         come from the engine's generator, or from `mask_override` / `elem_mask_override` with rows for passes * B samples.
         loss[s] is then the mean over the passes * B samples, and `dimage` [B,C,H,W] receives the passes' gradients summed
         in the fixed order m = 0 ... passes-1 (mimo_input_gradient_mc); the logits returned are [passes * B,S,Co,H,W]."""
-        if not mc_dropout and (self._bn_training() or any(d.p > 0.0 and d.training for d in self._dropout_modules())):
-            raise NotImplementedError("MimoUNet.image_gradient: eval mode only (BatchNorm on running statistics, dropout off)")
-        if self._bn_training():
-            raise NotImplementedError("MimoUNet.image_gradient: BatchNorm must be in eval mode (running statistics), also "
-                                      "with mc_dropout")
+        self._require_eval("MimoUNet.image_gradient", allow_dropout=mc_dropout)
         passes = int(passes)
         if passes < 1 or (passes > 1 and not mc_dropout):
             raise ValueError(f"MimoUNet.image_gradient: passes = {passes} needs mc_dropout=True and passes >= 1")
         image = image.contiguous().float()
-        if image.dim() != 4 or image.shape[1] != self.in_channels:
-            raise ValueError(f"expected [B,{self.in_channels},H,W], got {tuple(image.shape)}")
+        self._require_image(image)
         label = label.contiguous().float()
         mask = None if mask is None else mask.contiguous().float()
         dloss = dloss.to(device=image.device, dtype=torch.float32).contiguous()
@@ -567,19 +581,11 @@ class MimoUNet(nn.Module):
                     if m is not None and tuple(m.shape) != (n, plan.double_conv_channels[i]):
                         raise ValueError(f"Dropout2d mask of site {i}: expected {(n, plan.double_conv_channels[i])} "
                                          f"(passes * B rows), got {tuple(m.shape)}")
-        out = torch.empty(n, self.num_subnetworks, self.out_channels, plan.height, plan.width, device=image.device,
-                          dtype=torch.float32)
+        out = self._eval_forward(plan, image, (label, mask, dloss), broadcast_subnetworks=True, masks=masks, elem_masks=elem_masks,
+                                 no_grad=False, rng=rng)
         loss = torch.empty(self.num_subnetworks, device=image.device, dtype=torch.float32)
-        plan.bind(self._flat_params, None, self._flat_buffers)
-        plan.forward(image, out, training=False, broadcast_subnetworks=True, masks=masks, elem_masks=elem_masks, no_grad=False,
-                     param_version=self._param_version(), rng=rng)
         plan.loss_forward(label, mask, None, loss)
-        if mc_dropout:
-            plan.input_gradient_mc(None, dloss, dimage, accumulate, passes)
-        else:
-            plan.input_gradient(None, dloss, dimage, accumulate)
-        plan.generation += 1
-        self._inference_keep = (image, label, mask, dloss, out, masks, elem_masks)  # the plan still points at these
+        plan.input_gradient(None, dloss, dimage, accumulate, replicas=passes if mc_dropout else 0)
         return out, loss
 
     def image_gradient_from_dout(self, image: torch.Tensor, dout_fn, dimage: torch.Tensor, accumulate: bool = False):
@@ -587,24 +593,16 @@ class MimoUNet(nn.Module):
         `image` [B,C,H,W] with its graph kept, `dout_fn(logits [B,S,Co,H,W]) -> dout` of the same shape made by the caller,
         and `mimo_input_gradient(dout, dloss = NULL)` written (accumulate: added) into `dimage` [B,C,H,W] — no
         `mimo_loss_forward`, no `.grad`, no BatchNorm buffer, no autograd graph.  Returns the logits."""
-        if self._bn_training() or any(d.p > 0.0 and d.training for d in self._dropout_modules()):
-            raise NotImplementedError("MimoUNet.image_gradient_from_dout: eval mode only (BatchNorm on running statistics, dropout off)")
-        if self._geom.precision not in ("fp32", "split16"):
-            raise NotImplementedError(f"MimoUNet.image_gradient_from_dout: implemented for the fp32 and split16 precisions, not "
-                                      f"{self._geom.precision!r} (mimo_input_gradient)")
+        self._require_eval("MimoUNet.image_gradient_from_dout")
+        self._require_gradient_precision("MimoUNet.image_gradient_from_dout:", " (mimo_input_gradient)")
         image = image.contiguous().float()
-        if image.dim() != 4 or image.shape[1] != self.in_channels:
-            raise ValueError(f"expected [B,{self.in_channels},H,W], got {tuple(image.shape)}")
+        self._require_image(image)
         plan = self._plan_for(image, None, grad_only=True)
-        out = torch.empty(image.shape[0], self.num_subnetworks, self.out_channels, plan.height, plan.width, device=image.device,
-                          dtype=torch.float32)
-        plan.bind(self._flat_params, None, self._flat_buffers)
-        plan.forward(image, out, training=False, broadcast_subnetworks=True, no_grad=False, param_version=self._param_version())
+        out = self._eval_forward(plan, image, broadcast_subnetworks=True, no_grad=False)
         dout = dout_fn(out).contiguous().float()
         assert dout.shape == out.shape and dout.is_cuda, (tuple(dout.shape), tuple(out.shape))
+        self._inference_keep += (dout,)  # (made from the logits, so only now)
         plan.input_gradient(dout, None, dimage, accumulate)
-        plan.generation += 1
-        self._inference_keep = (image, out, dout)  # the plan still points at these
         return out
 
     def _run_backward(self, plan: Plan, dout, dloss, dx) -> None:
@@ -614,7 +612,7 @@ class MimoUNet(nn.Module):
         # buffer, so keep a copy when a live .grad still aliases it.
         aliased = any(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in views)
         hook = self.grad_ready_hook
-        sync = getattr(self, "grad_sync", None)  # the reducer behind the hook (FlatGradientAllReducer.attach), if any
+        sync = self.grad_sync  # the reducer behind the hook (FlatGradientAllReducer.attach), if any
         announcing = hook is not None and (sync is None or sync.enabled)
         # "Already reduced" = the reducer really took ranges of this buffer (not a one-rank no-op reducer) and nothing has
         # written the .grad tensors through torch since: zero_grad(set_to_none=False) of a stock optimiser zeroes them in
@@ -668,7 +666,7 @@ class MimoUNet(nn.Module):
         clear — a diverged run, or a value outside what the precision mode represents: the default "split16" forward
         carries activations as fp16 (hi, lo) pairs and weights as fp16 pairs x 2^8, so |activation| >= 65520 or
         |weight| >= 256 overflows there where the reference's fp32 path does not ("fp32" mode has fp32 range)."""
-        flags = getattr(self, "_evicted_status", 0)  # recorded by plans the LRU cache has dropped since
+        flags = self._evicted_status  # recorded by plans the cache has dropped since (_evict_oldest)
         if clear:
             self._evicted_status = 0
         for plan in list(self._plans.values()):

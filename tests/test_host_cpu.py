@@ -69,6 +69,27 @@ def test_constructor_contract():
     assert len(drops) == len(net.double_convs()) + 1 + 2  # + center_dropout + S final_dropouts
 
 
+def test_transient_state_is_complete_on_fresh_copied_and_unpickled_models():
+    """Everything the engine derives from the module tree is declared once (`_TRANSIENT`): a fresh, a deep-copied and an
+    unpickled model have every one of these attributes at its empty value, and a pickle carries none of them."""
+    import copy
+    import pickle
+    from mimo.models.mimo_components.model import MimoUNet
+    fresh = MimoUNet(3, 2, 2, 4)
+    assert {"_plans", "_evicted_status", "_mask_plan", "grad_sync", "grad_ready_hook", "_inference_keep", "_flat_params",
+            "_dc_cache"} <= set(MimoUNet._TRANSIENT)
+    fresh.double_convs()  # fills the cached module lists
+    fresh._evicted_status, fresh.grad_sync, fresh._inference_keep = 5, object(), (torch.zeros(1),)
+    assert not set(fresh.__getstate__()) & set(MimoUNet._TRANSIENT)
+    assert "_geom" in fresh.__getstate__() and "_plan_cache_size" in fresh.__getstate__()
+    for net in (MimoUNet(3, 2, 2, 4), copy.deepcopy(fresh), pickle.loads(pickle.dumps(fresh))):
+        assert all(name in net.__dict__ for name in MimoUNet._TRANSIENT)
+        assert len(net._plans) == 0 and net._evicted_status == 0
+        assert net._mask_plan is None and net.grad_sync is None and net._inference_keep is None and net._dc_cache is None
+        assert net.numerics_status() == 0  # (no plan: nothing touches the device)
+        assert [k for k, _ in net.named_parameters()] == [k for k, _ in fresh.named_parameters()]
+
+
 def test_loss_classes_match_reference_golden():
     from mimo.losses import GaussianNLL, LaplaceNLL, UncertaintyLoss
     fx = load_npz("losses.npz")
