@@ -8,11 +8,15 @@ OBJS := $(SRCS:.hip=.o)
 LIB := mimo_unet_amd/libmimo_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 
-all: $(LIB)
+# test-only twin of the library: plan.hip compiled together with tests/host/plan_probe.hip, which copies a layer's input and
+# pre-activation tensor out of a plan (tests/test_plan_entry_gpu.py); same objects otherwise, same version script
+PROBE := mimo_unet_amd/libmimo_plan_probe.so
+
+all: $(LIB) $(PROBE)
 
 # every compile leaves hipcc's per-kernel resource remarks next to the object (csrc/*.res): scripts/check_resources.py
 # fails the build when a kernel that counts its vector-memory operations by hand (LDS-DMA) touches scratch
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/pack_layout.h $(CSRC)/tile_sched.h $(CSRC)/dz_ring.h $(CSRC)/graph_replay.h $(CSRC)/elementwise.h $(CSRC)/adam_update.h $(CSRC)/block_reduce.h $(CSRC)/evidential.h $(CSRC)/philox.h include/mimo_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/pack_layout.h $(CSRC)/conv_recipe.h $(CSRC)/conv_launch.h $(CSRC)/tile_sched.h $(CSRC)/dz_ring.h $(CSRC)/graph_replay.h $(CSRC)/elementwise.h $(CSRC)/adam_update.h $(CSRC)/block_reduce.h $(CSRC)/evidential.h $(CSRC)/philox.h include/mimo_hip.h
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(@:.o=.res) || (grep -v "remark:" $(@:.o=.res) >&2; false)
 	@grep -E "warning:|error:" -A3 $(@:.o=.res) >&2 || true
 
@@ -20,7 +24,13 @@ $(LIB): $(OBJS) $(CSRC)/exports.map
 	python3 scripts/check_resources.py $(OBJS:.o=.res)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--version-script=$(CSRC)/exports.map -o $@ $(OBJS)
 
+$(CSRC)/plan_probe.o: tests/host/plan_probe.hip $(CSRC)/plan.o
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(PROBE): $(CSRC)/plan_probe.o $(OBJS) $(CSRC)/exports.map
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--version-script=$(CSRC)/exports.map -o $@ $(CSRC)/plan_probe.o $(filter-out $(CSRC)/plan.o,$(OBJS))
+
 clean:
-	rm -f $(OBJS) $(OBJS:.o=.res) $(LIB)
+	rm -f $(OBJS) $(OBJS:.o=.res) $(LIB) $(PROBE) $(CSRC)/plan_probe.o
 
 .PHONY: all clean

@@ -338,29 +338,12 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradLaunch a, int tile
     }
 }
 
-static int wgrad_tc(int W) { return W >= 24 ? 32 : (W >= 12 ? 16 : 8); }
-
-static int wgrad_num_tiles(int N, int H, int W) {
-  const int tc = wgrad_tc(W), tr = 256 / tc;
-  return N * ceil_div(H, tr) * ceil_div(W, tc);
-}
-
-int wgrad_pick_splits(int N, int H, int W, int cin_pad, int cout_pad) {
-  const int wtiles = (cin_pad / 32) * (cout_pad / 32);
-  const int tiles = wgrad_num_tiles(N, H, W);
-  int splits = ceil_div(2048, wtiles);
-  if (splits > tiles) splits = tiles;
-  if (splits > 1024) splits = 1024;
-  if (splits < 1) splits = 1;
-  return splits;
-}
-
 int wgrad_launch(const WgradLaunch& a, hipStream_t stream) {
   if (a.cin_pad % 32 || a.cout_pad % 32 || a.cin_p % 4 || a.cout_p % 4 || a.ldx % 4 || a.lddz % 4 || a.H < 2 || a.W < 2) {
     set_error("wgrad: bad geometry");
     return MIMO_ERR_INVALID;
   }
-  const int tc = wgrad_tc(a.W), tr = 256 / tc;
+  const int tc = sched::wg32_tc(a.W), tr = 256 / tc;
   const int tilesY = ceil_div(a.H, tr), tilesX = ceil_div(a.W, tc);
   const int numTiles = a.N * tilesY * tilesX;
   dim3 grid((a.cin_pad / 32) * (a.cout_pad / 32), a.splits);

@@ -377,7 +377,7 @@ constexpr int kWsMaxMF = 4;
 // 0-15 of tap (0, kw) in K lanes 0-15 and of tap (1, kw) in K lanes 16-31, step kw of the second tap (2, kw) in K
 // lanes 0-15 (weights of lanes 16-31 zero); the chunk's third phase is a bare barrier (the producers stage as
 // before).  45 input channels: 15 K steps per tile instead of 18.  The weight image of the chunk is packed accordingly
-// (conv3x3_pair_tail, pack kernels below); the input tile in LDS is unchanged: the lanes of K groups 2-3 read the
+// (sched::ws_tail_pairs through conv_recipe, pack kernels below); the input tile in LDS is unchanged: the lanes of K groups 2-3 read the
 // pixel one tile row further down at slots 0-1 — a per-lane constant, so the fragment addresses keep the form
 // (lane base) + (scalar of the phase) + (immediate of the step), and phases keep their three steps, so the
 // alternation of the two B register sets is the same compile-time pattern as without pairing.
@@ -889,27 +889,22 @@ __global__ __launch_bounds__(512, (MF_ == 2 && NF <= 2) ? 4 : 2) void conv3x3_ws
 
 // Which instance, tile and grid a launch gets: sched::split_config and its rules (tile_sched.h, host-testable).  The
 // environment switches are read here, once, and passed in.
-static bool conv_ws_enabled() {
+bool conv_ws_enabled() {
   static const bool on = !(getenv("MIMO_CONV_WS") && atoi(getenv("MIMO_CONV_WS")) == 0);
   return on;
 }
-static int conv_ksplit_force() {
+int conv_ksplit_force() {
   static const int force = [] { const char* e = getenv("MIMO_CONV_KSPLIT"); return e ? atoi(e) : -1; }();
   return force;
 }
 
 int conv3x3_ws_stat_rows(int, int, int) { return sched::kWsStatRows; }
-int conv3x3_pair_tail(int mode, int cin_p, int Ho, int Wo) { return sched::ws_tail_pairs(mode, cin_p, Ho, Wo, conv_ws_enabled()); }
 int conv3x3_split_fuses_input(int mode, int wide, int Ho, int Wo) {
   return sched::split_fuses_input(mode, wide, Ho, Wo, conv_ws_enabled());
 }
 int conv3x3_ksplit(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo) {
   return sched::split_pick_ksplit(mode, N, cin_p, cout_pad, Ho, Wo, conv_ws_enabled(), conv_ksplit_force());
 }
-size_t conv3x3_ksplit_scratch(int mode, int N, int cin_p, int cout_pad, int Ho, int Wo, int ldy) {
-  return sched::ksplit_scratch_floats(conv3x3_ksplit(mode, N, cin_p, cout_pad, Ho, Wo), N, Ho, Wo, ldy);
-}
-
 template <int NF, int MODE, int MF>
 static int launch_ws(const ConvLaunch& a, const sched::SplitCfg& c, hipStream_t stream) {
   const int ksplit = a.ksplit > 1 ? a.ksplit : 1;
@@ -1069,7 +1064,7 @@ int conv3x3_bf16x3_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t 
 //   transposed == 1 (dgrad):    row -> ci = row_map[row], col -> co = col_map[col], tap = (2-kh)*3+(2-kw)
 // map value -1 = zero padding.
 // ---------------------------------------------------------------------------------------
-// paired last chunk (conv3x3_pair_tail): tap (row, kw) of channel k < 16 -> of the chunk's nine weight slots, slot kw
+// paired last chunk (sched::ws_tail_pairs): tap (row, kw) of channel k < 16 -> of the chunk's nine weight slots, slot kw
 // for rows 0 (K lane k) and 1 (K lane 16 + k), slot 3 + kw for row 2 (K lane k).  K lanes 16-31 of slots 3-5 and
 // slots 6-8 are never written: they keep the zeros of the allocation.
 __device__ __forceinline__ void pair_slot(int tap, int k, int* slot, int* kk) {

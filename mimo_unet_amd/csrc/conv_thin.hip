@@ -365,7 +365,7 @@ static const ThinCaps& thin_caps() {
 }
 
 int conv3x3_thin_ok(int cin, int cout_p) {
-  if (!(thin_enabled() && cin >= 1 && cin <= 4 && cout_p % 4 == 0 && cout_p >= 4 && cout_p <= 256)) return 0;
+  if (!(thin_enabled() && sched::thin_geometry_ok(cin, cout_p))) return 0;
   (void)thin_caps();
   return 1;
 }

@@ -781,7 +781,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(ConvLaunch a, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-static int wide_force() {
+int conv_wide_force() {
   static const int f = [] {
     const char* e = getenv("MIMO_CONV_WIDE");  // 0: never; 2: whenever the geometry is supported; default: cost rule
     const int v = e ? atoi(e) : 1;
@@ -790,10 +790,6 @@ static int wide_force() {
   return f;
 }
 
-// 0 = the layer runs on conv_bf16x3.hip; else the packed weight rows of the wide layout (ConvLaunch::wide)
-int conv3x3_wide_rows(int mode, int N, int cin_p, int rows, int Ho, int Wo) {
-  return sched::wide_config(mode, N, cin_p, rows, Ho, Wo, wide_force()).rows_pad;
-}
 int conv3x3_wide_stat_rows() { return 256; }  // one row per persistent workgroup column
 
 int conv3x3_wide_launch(const ConvLaunch& a, int mode, int* rows, hipStream_t stream) {

@@ -138,28 +138,34 @@ int stage_back(const Stored& s, int precision, hipStream_t st) {
 
 // The weight image of one convolution launch, written by the plan's packer from a table of one job: w is the bound
 // parameter buffer (w_off = 0), the bias lies at its distance from w.  The fp16 kinds get no wmax word: the image keeps
-// the fixed 2^8 (ConvLaunch::wmax == nullptr).  rows: entries of the row map; bias_dst != nullptr: the bias is copied.
-int pack_image(Temp& t, int dir, int precision, bool split, const float* w, const float* bias, float* bias_dst, int cout, int cin,
-               int cin_p, int cout_p, int rows, int wide, int pair, hipStream_t st, ConvLaunch* a) {
-  const int kind = pack::kind(precision, dir, split, wide != 0);
-  const size_t elems = pack::image_elems(kind, wide ? wide : rows, dir == PACK_FWD ? cin_p : cout_p);
+// the fixed 2^8 (ConvLaunch::wmax == nullptr).  bias_dst != nullptr: the bias is copied.
+int pack_image(Temp& t, int dir, int precision, const ConvDir& d, const float* w, const float* bias, float* bias_dst, int cout, int cin,
+               int cin_p, int cout_p, hipStream_t st, ConvLaunch* a) {
+  const int kind = pack::kind(precision, dir, d.split, d.wide != 0);
+  const size_t elems = pack::image_elems(kind, d.wide ? d.wide : d.rows, dir == PACK_FWD ? cin_p : cout_p);
   void* img = kind == PK_F32 ? (void*)t.get<float>(elems) : (void*)t.get<uint16_t>(elems);
-  const int* rm = t.ints(ident_map(rows, dir == PACK_FWD ? cout : cin));
+  const int* rm = t.ints(ident_map(d.rows, dir == PACK_FWD ? cout : cin));
   const int* cm = dir == PACK_FWD ? t.ints(ident_map(cin_p, cin)) : t.ints(ident_map(cout_p, cout));
   PackJob* job_dev = t.get<PackJob>(1);
   MIMO_TRY(t.ok());
   const bool with_bias = bias && bias_dst;
-  const PackJob job = pack::make_job(dir, precision, split, cout, cin, cin_p, cout_p, rows, wide, pair, rm, cm, img, nullptr, 0,
+  const PackJob job = pack::make_job(dir, precision, d.split, cout, cin, cin_p, cout_p, d.rows, d.wide, d.pair, rm, cm, img, nullptr, 0,
                                      with_bias ? (int64_t)(((intptr_t)bias - (intptr_t)w) / (intptr_t)sizeof(float)) : 0,
                                      with_bias ? bias_dst : nullptr);
   MIMO_HIP_CHECK(hipMemcpy(job_dev, &job, sizeof(PackJob), hipMemcpyHostToDevice));
   MIMO_TRY(pack_jobs_launch(job_dev, 1, job.total, w, st));
   a->w = kind == PK_F32 ? static_cast<const float*>(img) : nullptr;
   a->wpk = kind == PK_F32 ? nullptr : img;
-  a->pair = job.pair;
-  a->wide = wide;
   return MIMO_OK;
 }
+
+// The recipe the plan makes for a layer of this geometry whose input channels lie in order (conv_recipe.h).  An entry point
+// has no network to derive sched::wg_side_cus from: its weight gradient is sized for the whole chip (256 CUs).
+ConvRecipe op_recipe(int precision, int n, int h, int w, int cin, int cin_p, int cout, int cout_p) {
+  return conv_recipe(precision, 0, n, h, w, cin, cout, cin_p, cout_p, true, conv_env(256));
+}
+// tensors are 16-bit where the plan's are: the operands and results of the 16-bit storage kernels
+int stored_as(int precision, bool on_16bit_kernels) { return on_16bit_kernels ? precision : (int)MIMO_PREC_FP32; }
 
 }  // namespace
 
@@ -170,55 +176,38 @@ int mimo_op_conv3x3_forward(const float* x, const float* w, const float* bias, f
                             int32_t precision, mimo_stream stream) {
   hipStream_t st = (hipStream_t)stream;
   Temp t("mimo_op_conv3x3_forward");
-  const int cout_pad = conv3x3_cout_pad(cout);
-  const bool mixed = is_mixed(precision);
-  const int fmode = pack::conv_mode(precision, PACK_FWD);
-  // (an image convolution — <= 4 input channels in an 8-channel pixel — runs on the plain-FMA kernel, as in the plan)
-  const bool thin = !mixed && cin_p < 16 && conv3x3_thin_ok(cin, cout_p);
-  const bool split = (precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed) && !thin;
-  // split16: the decomposition the plan would pick for this geometry (conv_wide.hip or conv_bf16x3.hip)
-  const int wide = (split && (precision == MIMO_PREC_SPLIT16 || mixed)) ? conv3x3_wide_rows(fmode, n, cin_p, cout_p, h, wd) : 0;
-  const int pair = (split && !wide) ? conv3x3_pair_tail(fmode, cin_p, h, wd) : 0;
-  float* bp = t.get<float>(cout_pad);
+  const ConvRecipe r = op_recipe(precision, n, h, wd, cin, cin_p, cout, cout_p);
+  const ConvDir& d = r.fwd;
+  float* bp = t.get<float>(d.rows);
   const int rows_cap = std::max(std::max(conv3x3_stat_rows(n, h, wd), conv3x3_ws_stat_rows(n, h, wd)), 2048);
-  float* partial = t.get<float>((size_t)rows_cap * 2 * cout_pad);
-  double* sums = t.get<double>((size_t)kMaxChunks * 2 * cout_pad);
-  // (with the K split the plan would use for this geometry, conv3x3_ksplit: scratch for its partial slabs)
-  const size_t kfl = (!split || mixed || wide) ? 0 : conv3x3_ksplit_scratch(fmode, n, cin_p, cout_pad, h, wd, cout_p);
-  float* kpart = kfl ? t.get<float>(kfl) : nullptr;
+  float* partial = t.get<float>((size_t)rows_cap * 2 * d.rows);
+  double* sums = t.get<double>((size_t)kMaxChunks * 2 * d.rows);
+  float* kpart = d.kpart ? t.get<float>(d.kpart) : nullptr;  // (the slabs of the K split the plan would use)
   MIMO_TRY(t.ok());
   // 16-bit storage modes: the fp32 tensors of this interface are rounded into 16-bit buffers, the storage-mode kernels
   // run on those, the result is widened again (exact)
+  const int sp = stored_as(precision, d.split);
   Stored xs, zs;
-  MIMO_TRY(stage_in(t, x, (int64_t)n * h * wd * cin_p, precision, st, &xs));
-  MIMO_TRY(stage_out(t, z, (int64_t)n * h * wd * cout_p, precision, st, &zs));
-  ConvLaunch a;
-  MIMO_TRY(pack_image(t, PACK_FWD, precision, split, w, bias, bp, cout, cin, cin_p, cout_p, cout_pad, wide, pair, st, &a));
+  MIMO_TRY(stage_in(t, x, (int64_t)n * h * wd * cin_p, sp, st, &xs));
+  MIMO_TRY(stage_out(t, z, (int64_t)n * h * wd * cout_p, sp, st, &zs));
+  ConvLaunch a = fill_conv_launch(r, PACK_FWD, n, h, wd, cin_p, cout_p);
+  MIMO_TRY(pack_image(t, PACK_FWD, precision, d, w, bias, bp, cout, cin, cin_p, cout_p, st, &a));
   a.x = static_cast<const float*>(xs.in);
   a.y = static_cast<float*>(zs.out);
   a.bias = bp;
   a.stats = stats ? partial : nullptr;
-  a.N = n;
-  a.Hi = a.Ho = h;
-  a.Wi = a.Wo = wd;
-  a.ldx = cin_p;
-  a.cin_p = cin_p;
-  a.ldy = cout_p;
-  a.cout_pad = cout_pad;
-  a.cout_store = cout_p;
-  a.off = 1;
   int rows = 0;
-  if (thin)
+  if (d.split)
+    MIMO_TRY(conv3x3_bf16x3_launch_k(a, d.mode, &rows, st, kpart, d.kpart));
+  else if (r.thin)
     MIMO_TRY(conv3x3_thin_launch(a, cin, &rows, st));
-  else if (split)
-    MIMO_TRY(conv3x3_bf16x3_launch_k(a, fmode, &rows, st, kpart, kfl));
   else
     MIMO_TRY(conv3x3_launch(a, &rows, st));
-  MIMO_TRY(stage_back(zs, precision, st));
+  MIMO_TRY(stage_back(zs, sp, st));
   if (stats) {
     int chunks = 0;
-    MIMO_TRY(rowsum_launch(partial, rows, 2 * cout_pad, sums, &chunks, st));
-    hipLaunchKernelGGL(sums_to_stats_kernel, dim3(ceil_div(cout, 64)), dim3(64), 0, st, sums, chunks, cout_pad, cout, stats);
+    MIMO_TRY(rowsum_launch(partial, rows, 2 * d.rows, sums, &chunks, st));
+    hipLaunchKernelGGL(sums_to_stats_kernel, dim3(ceil_div(cout, 64)), dim3(64), 0, st, sums, chunks, d.rows, cout, stats);
     MIMO_KERNEL_CHECK();
   }
   MIMO_HIP_CHECK(hipStreamSynchronize(st));
@@ -229,43 +218,25 @@ int mimo_op_conv3x3_dgrad(const float* dz, const float* w, float* dx, int32_t n,
                           int32_t cin_p, int32_t cout, int32_t cout_p, int32_t precision, mimo_stream stream) {
   hipStream_t st = (hipStream_t)stream;
   Temp t("mimo_op_conv3x3_dgrad");
-  const int rows_pad = conv3x3_cout_pad(cin_p);
-  const bool mixed = is_mixed(precision);
-  const bool split = precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed;
-  const int dmode = pack::conv_mode(precision, PACK_DGRAD);
-  const int wide = (precision == MIMO_PREC_SPLIT16 || mixed) ? conv3x3_wide_rows(dmode, n, cout_p, cin_p, h + 2, wd + 2) : 0;
-  const int pair = (split && !wide) ? conv3x3_pair_tail(dmode, cout_p, h + 2, wd + 2) : 0;
+  const ConvRecipe r = op_recipe(precision, n, h, wd, cin, cin_p, cout, cout_p);
+  const ConvDir& d = r.dgrad;
   const int64_t ndz = (int64_t)n * h * wd * cout_p, ndx = (int64_t)n * h * wd * cin_p;
   // the padded-domain gradient, in the storage type (sized for fp32), folded in that storage and widened at the end
   float* dxpad = t.get<float>((size_t)n * (h + 2) * (wd + 2) * cin_p);
   // the bf16-pair kernel reads dz in split storage (see elementwise.h split_pairs_launch)
-  float* dz_pairs = (split && !mixed) ? t.get<float>(ndz) : nullptr;
-  const size_t kfl = (!split || mixed || wide) ? 0 : conv3x3_ksplit_scratch(dmode, n, cout_p, rows_pad, h + 2, wd + 2, cin_p);
-  float* kpart = kfl ? t.get<float>(kfl) : nullptr;
+  float* dz_pairs = (d.split && !is_mixed(precision)) ? t.get<float>(ndz) : nullptr;
+  float* kpart = d.kpart ? t.get<float>(d.kpart) : nullptr;
   MIMO_TRY(t.ok());
   Stored dzs, dxs;
   MIMO_TRY(stage_in(t, dz, ndz, precision, st, &dzs));
   MIMO_TRY(stage_out(t, dx, ndx, precision, st, &dxs));
   if (dz_pairs) MIMO_TRY(split_pairs_launch(dz, dz_pairs, (int64_t)n * h * wd, cout_p, st));
-  ConvLaunch a;
-  MIMO_TRY(pack_image(t, PACK_DGRAD, precision, split, w, nullptr, nullptr, cout, cin, cin_p, cout_p, rows_pad, wide, pair, st, &a));
+  ConvLaunch a = fill_conv_launch(r, PACK_DGRAD, n, h, wd, cin_p, cout_p);
+  MIMO_TRY(pack_image(t, PACK_DGRAD, precision, d, w, nullptr, nullptr, cout, cin, cin_p, cout_p, st, &a));
   a.x = dz_pairs ? dz_pairs : static_cast<const float*>(dzs.in);
   a.y = dxpad;
-  a.bias = nullptr;
-  a.stats = nullptr;
-  a.N = n;
-  a.Hi = h;
-  a.Wi = wd;
-  a.ldx = cout_p;
-  a.cin_p = cout_p;
-  a.Ho = h + 2;
-  a.Wo = wd + 2;
-  a.ldy = cin_p;
-  a.cout_pad = rows_pad;
-  a.cout_store = cin_p;
-  a.off = 2;
-  if (split)
-    MIMO_TRY(conv3x3_bf16x3_launch_k(a, dmode, nullptr, st, kpart, kfl));
+  if (d.split)
+    MIMO_TRY(conv3x3_bf16x3_launch_k(a, d.mode, nullptr, st, kpart, d.kpart));
   else
     MIMO_TRY(conv3x3_launch(a, nullptr, st));
   MIMO_TRY(fold_slice_launch(dxpad, store_type(precision), cin_p, 0, dxs.out, cin_p, n, h, wd, cin_p, 0, st));
@@ -279,69 +250,38 @@ int mimo_op_conv3x3_wgrad(const float* x, const float* dz, float* dw, float* dbi
                           mimo_stream stream) {
   hipStream_t st = (hipStream_t)stream;
   Temp t("mimo_op_conv3x3_wgrad");
-  const bool mixed = is_mixed(precision), f16s = precision == MIMO_PREC_FP16_MIXED;
-  const bool split = precision == MIMO_PREC_SPLIT16 || precision == MIMO_PREC_BF16 || mixed;
-  const bool bf16 = precision == MIMO_PREC_BF16;
-  if (!mixed && cin_p < 16 && wgrad_thin_ok(cin, cout_p, n, h, wd)) {  // the image convolution's kernel, as in the plan
-    float* part = t.get<float>(wgrad_thin_scratch(cin, cout_p));
-    MIMO_TRY(t.ok());
-    MIMO_TRY(wgrad_thin_launch(x, cin_p, dz, cout_p, n, h, wd, cin, cout, cout_p, part, dw, st));
-    if (dbias) {
-      hipLaunchKernelGGL(colsum_naive_kernel, dim3(cout), dim3(256), 0, st, dz, (int64_t)n * h * wd, cout_p, cout, dbias);
-      MIMO_KERNEL_CHECK();
-    }
-    MIMO_HIP_CHECK(hipStreamSynchronize(st));
-    return MIMO_OK;
-  }
-  WgradLaunch a;
+  const ConvRecipe r = op_recipe(precision, n, h, wd, cin, cin_p, cout, cout_p);
+  const bool thin = r.wg_thin && wgrad_thin_ok(cin, cout_p, n, h, wd);  // the image convolution's kernel, as in the plan
+  WgradLaunch a = fill_wgrad_launch(r, n, h, wd, cin_p, cout_p);
   a.x = x;
   a.dz = dz;
-  a.N = n;
-  a.H = h;
-  a.W = wd;
-  a.ldx = cin_p;
-  a.lddz = cout_p;
-  a.cin_p = cin_p;
-  a.cout_p = cout_p;
-  if (split) {
-    int CI, CO;
-    wgrad_split_tiles(cin_p, cout_p, &CI, &CO);
-    a.cin_pad = round_up(cin_p, CI);
-    a.cout_pad = round_up(cout_p, CO);
-    a.splits = wgrad_split_pick_splits(n, h, wd, a.cin_pad, a.cout_pad, CI, CO, mixed ? (f16s ? 2 : 1) : 0);
-  } else {
-    a.cin_pad = round_up(cin_p, 32);
-    a.cout_pad = round_up(cout_p, 32);
-    a.splits = wgrad_pick_splits(n, h, wd, a.cin_pad, a.cout_pad);
-  }
-  a.partial = t.get<float>((size_t)(a.splits + a.splits / 8 + 2) * 9 * a.cin_pad * a.cout_pad);
+  a.partial = t.get<float>(thin ? wgrad_thin_scratch(cin, cout_p) : (size_t)(a.splits + a.splits / 8 + 2) * 9 * a.cin_pad * a.cout_pad);
   int* cm = t.ints(ident_map(cin_p, cin));
   MIMO_TRY(t.ok());
-  if (mixed) {  // activations and dz as plain 16-bit NHWC tensors
+  if (thin) {
+    MIMO_TRY(wgrad_thin_launch(x, cin_p, dz, cout_p, n, h, wd, cin, cout, cout_p, a.partial, dw, st));
+  } else if (is_mixed(precision)) {  // dz, and the activations of every layer but the image convolution, as plain 16-bit NHWC tensors
     Stored xs, dzs;
-    MIMO_TRY(stage_in(t, x, (int64_t)n * h * wd * cin_p, precision, st, &xs));
+    MIMO_TRY(stage_in(t, x, (int64_t)n * h * wd * cin_p, stored_as(precision, a.store <= 2), st, &xs));
     MIMO_TRY(stage_in(t, dz, (int64_t)n * h * wd * cout_p, precision, st, &dzs));
     a.x = static_cast<const float*>(xs.in);
     a.dz = static_cast<const float*>(dzs.in);
-    a.np = 1;
-    a.store = f16s ? 2 : 1;
     MIMO_TRY(wgrad_split_launch(a, st));
-  } else if (split) {  // split storage of dz, as the BatchNorm-backward kernel writes it in the plan
+  } else if (r.wg_split) {  // split storage of dz, as the BatchNorm-backward kernel writes it in the plan
     float* dzs = t.get<float>((size_t)n * h * wd * cout_p);
-    // as in the plan: two fp16 MFMAs per product where the geometry has that kernel, with max |dz| next to the split
-    float* amax = (!bf16 && wgrad_split_has_np2(cin_p, cout_p)) ? t.get<float>(kDzMaxSlots) : nullptr;
+    // as in the plan: two fp16 MFMAs per product where the recipe has them, with max |dz| next to the split
+    float* amax = r.wg_np2 ? t.get<float>(kDzMaxSlots) : nullptr;
     MIMO_TRY(t.ok());
-    int amax_n = 0;
-    MIMO_TRY(split_pairs_launch(dz, dzs, (int64_t)n * h * wd, cout_p, st, amax, &amax_n));
+    MIMO_TRY(split_pairs_launch(dz, dzs, (int64_t)n * h * wd, cout_p, st, amax, &a.dz_absmax_n));
     a.dz = dzs;
-    a.np = bf16 ? 1 : amax ? 2 : 3;
     a.dz_absmax = amax;
-    a.dz_absmax_n = amax_n;
+    if (amax) a.np = 2;
     MIMO_TRY(wgrad_split_launch(a, st));
   } else {
     MIMO_TRY(wgrad_launch(a, st));
   }
-  MIMO_TRY(wgrad_reduce_launch(a.partial, a.splits, a.cin_pad, a.cout_pad, cm, cin_p, cin, cout, dw, st, a.dz_absmax, a.dz_absmax_n));
+  if (!thin)
+    MIMO_TRY(wgrad_reduce_launch(a.partial, a.splits, a.cin_pad, a.cout_pad, cm, cin_p, cin, cout, dw, st, a.dz_absmax, a.dz_absmax_n));
   if (dbias) {
     hipLaunchKernelGGL(colsum_naive_kernel, dim3(cout), dim3(256), 0, st, dz, (int64_t)n * h * wd, cout_p, cout, dbias);
     MIMO_KERNEL_CHECK();

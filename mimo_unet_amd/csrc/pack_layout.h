@@ -37,7 +37,7 @@ struct PackJob {
   float* bias_dst;
   const int *row_map, *col_map;  // row / column -> logical channel of the OIHW tensor, -1 = zero padding
   int kind, cout, cin, rows_pad, cols, transposed, total, bias_n;  // bias_n > 0: the layer's bias is copied as well
-  int pair;  // PK_F16_PAIR / PK_BF16_PAIR: tap-paired image of the last chunk (conv3x3_pair_tail)
+  int pair;  // PK_F16_PAIR / PK_BF16_PAIR: tap-paired image of the last chunk (ConvDir::pair, conv_recipe.h)
   int map_rows;  // entries of row_map (wide kinds: rows_pad may exceed it)
   unsigned* wmax;  // fp16 kinds: max |w| of the layer at this pack, float bits (wabsmax_jobs_launch); image scale = w16_scale
 };
@@ -84,8 +84,8 @@ static inline int total(int k, int rows_pad, int cols) {
 static inline size_t image_elems(int k, int rows_pad, int cols) { return (size_t)total(k, rows_pad, cols) * (kind_is_pair(k) ? 2 : 1); }
 
 // The job that packs one layer's image for a direction.  rows: padded output channels of the launch = entries of
-// row_map (forward: conv3x3_cout_pad(Cout); data gradient: conv3x3_cout_pad(cin_p)); wide_rows: conv3x3_wide_rows, 0 =
-// none; pair: conv3x3_pair_tail.  bias_dst != nullptr (forward): Cout floats at bias_off are copied there.  wmax is kept
+// row_map (ConvDir::rows: forward conv3x3_cout_pad(Cout); data gradient conv3x3_cout_pad(cin_p)); wide_rows: ConvDir::wide, 0 =
+// none; pair: ConvDir::pair.  bias_dst != nullptr (forward): Cout floats at bias_off are copied there.  wmax is kept
 // for the fp16 kinds only.
 static inline PackJob make_job(int dir, int precision, bool split, int Cout, int Cin, int cin_p, int cout_p, int rows, int wide_rows,
                                int pair, const int* row_map, const int* col_map, void* dst, unsigned* wmax, int64_t w_off,

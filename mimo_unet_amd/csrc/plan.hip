@@ -81,21 +81,18 @@ struct Act {
 struct ConvBN {
   std::string conv_name, bn_name;
   int Cin = 0, Cout = 0, cin_p = 0, cout_p = 0;
-  int cout_pad = 0;             // forward packed rows
-  int dg_rows = 0;              // dgrad packed rows (covers cin_p)
-  int wg_cin_pad = 0, wg_cout_pad = 0, wg_splits = 1;
   int N = 0, H = 0, W = 0;
+  ConvRecipe r;  // which kernels run this layer and on what packed rows, tiles and splits (conv_recipe.h)
+  // the launches of the three directions, ready-made by fill_launches at the end of build(): a call copies one and sets what
+  // varies per call
+  ConvLaunch fwd, dgrad;
+  WgradLaunch wgrad;
   int64_t off_w = 0, off_b = 0, off_gamma = 0, off_beta = 0, off_rm = 0, off_rv = 0;
   float *wf = nullptr, *wd = nullptr, *bias_p = nullptr;
   void *wf16 = nullptr, *wd16 = nullptr;  // split-bf16 packed weights (MIMO_PREC_SPLIT16)
-  bool fwd_split = false, dg_split = false, wg_split = false;
   unsigned* wmax = nullptr;  // fp16 forward weight image: max |w| of the layer AT ITS LAST PACK, float bits (w16_scale: the image's power-of-two scale)
-  bool wg_np2 = false;  // the weight gradient runs two fp16 MFMAs per product (wgrad_split.hip NP == 2)
-  bool thin = false;  // image convolution (<= 4 input channels) on the plain-FMA kernels of conv_thin.hip
-  int fwd_wide = 0, dg_wide = 0;  // != 0: the launch runs on conv_wide.hip, value = packed weight rows (conv3x3_wide_rows)
   int *cin_map = nullptr, *fwd_row_map = nullptr, *dg_row_map = nullptr, *dg_col_map = nullptr;
-  float* z = nullptr;
-  int dtz = ST_F32;  // element type of z: the plan's storage type, fp32 where the fp32 kernel family writes it
+  float* z = nullptr;  // (element type: r.dtz)
   float *mean = nullptr, *invstd = nullptr, *scale = nullptr, *shift = nullptr, *c1 = nullptr, *c2 = nullptr;
   const float* in = nullptr;
   int ld_in = 0;
@@ -396,7 +393,9 @@ struct mimo_plan {
   // (Measured and removed in round 3: per-layer dz buffers without back-pressure, 3-4 ping-pong buffers with a wait per
   // layer, releasing a weight gradient only after its layer's data gradient — none faster)
   bool wg_async = false;
-  int wg_cus = 256;  // CUs the weight-gradient launches are sized for (sched::wg_side_cus; MIMO_WGRAD_CUS overrides)
+  // the switches and the device as conv_recipe takes them, read once by build(); env.wg_cus: the CUs the weight-gradient launches
+  // are sized for (sched::wg_side_cus; MIMO_WGRAD_CUS overrides)
+  ConvEnv env;
   // test hook (MIMO_DEBUG_WGRAD_DELAY_US, read per plan): an idle kernel of that many microseconds in front of every weight
   // gradient, on the stream it runs on — the consumer of dz and its max |dz| slots arrives late (tests/test_streams_gpu.py)
   int wg_delay_us = 0;
@@ -549,6 +548,7 @@ struct mimo_plan {
     return t.offset;
   }
 
+  // A layer in three steps: what it runs (conv_recipe), its parameters, its buffers and its share of the scratch capacities
   int init_convbn(ConvBN& L, const std::string& prefix, int conv_idx, int bn_idx, int Cin, int Cout,
                   const std::vector<int>& in_chmap, int n, int h, int w) {
     L.conv_name = prefix + "." + std::to_string(conv_idx);
@@ -557,65 +557,37 @@ struct mimo_plan {
     L.Cout = Cout;
     L.cin_p = (int)in_chmap.size();
     L.cout_p = pad_channels(Cout);
-    L.cout_pad = conv3x3_cout_pad(Cout);
-    L.dg_rows = conv3x3_cout_pad(L.cin_p);
     L.N = n;
     L.H = h;
     L.W = w;
-    const bool mfma16 = cfg.precision != MIMO_PREC_FP32;
-    L.wg_split = mfma16;
-    if (L.wg_split) {
-      int CI, CO;
-      wgrad_split_tiles(L.cin_p, L.cout_p, &CI, &CO);
-      L.wg_cin_pad = round_up(L.cin_p, CI);
-      L.wg_cout_pad = round_up(L.cout_p, CO);
-      // operand storage of this layer's weight gradient (= WgradLaunch::store in convbn_backward: fwd_split below)
-      const int wg_store = !mixed ? 0 : (L.cin_p >= 8 ? (f16 ? 2 : 1) : (f16 ? 4 : 3));
-      L.wg_splits = wgrad_split_pick_splits(n, h, w, L.wg_cin_pad, L.wg_cout_pad, CI, CO, wg_store, wg_cus);
-    } else {
-      L.wg_cin_pad = round_up(L.cin_p, 32);
-      L.wg_cout_pad = round_up(L.cout_p, 32);
-      L.wg_splits = wgrad_pick_splits(n, h, w, L.wg_cin_pad, L.wg_cout_pad);
-    }
-    L.off_w = add_tensor(L.conv_name + ".weight", {Cout, Cin, 3, 3}, 0);
-    L.off_b = add_tensor(L.conv_name + ".bias", {Cout}, 0);
-    L.off_gamma = add_tensor(L.bn_name + ".weight", {Cout}, 0);
-    L.off_beta = add_tensor(L.bn_name + ".bias", {Cout}, 0);
-    L.off_rm = add_tensor(L.bn_name + ".running_mean", {Cout}, 1);
-    L.off_rv = add_tensor(L.bn_name + ".running_var", {Cout}, 1);
+    bool ident = true;  // (the packed image: logical channel i in padded channel i)
+    for (int i = 0; i < Cin; ++i) ident = ident && i < L.cin_p && in_chmap[i] == i;
+    L.r = conv_recipe(cfg.precision, cfg.inference_only, n, h, w, Cin, Cout, L.cin_p, L.cout_p, ident, env);
+    register_convbn(L);
+    return alloc_convbn(L, in_chmap);
+  }
+
+  void register_convbn(ConvBN& L) {
+    L.off_w = add_tensor(L.conv_name + ".weight", {L.Cout, L.Cin, 3, 3}, 0);
+    L.off_b = add_tensor(L.conv_name + ".bias", {L.Cout}, 0);
+    L.off_gamma = add_tensor(L.bn_name + ".weight", {L.Cout}, 0);
+    L.off_beta = add_tensor(L.bn_name + ".bias", {L.Cout}, 0);
+    L.off_rm = add_tensor(L.bn_name + ".running_mean", {L.Cout}, 1);
+    L.off_rv = add_tensor(L.bn_name + ".running_var", {L.Cout}, 1);
+  }
+
+  int alloc_convbn(ConvBN& L, const std::vector<int>& in_chmap) {
+    const ConvRecipe& r = L.r;
+    const int n = L.N, h = L.H, w = L.W;
     const bool train_bufs = cfg.inference_only != 1;  // everything only a backward reads or writes
     const bool wgrad_bufs = cfg.inference_only == 0;  // ... only a weight gradient (inference_only = 2: input gradient only)
-    MIMO_TRY(dalloc(&L.wf, pack::image_elems(PK_F32, L.cout_pad, L.cin_p)));
-    if (train_bufs) MIMO_TRY(dalloc(&L.wd, pack::image_elems(PK_F32, L.dg_rows, L.cout_p)));
-    MIMO_TRY(dalloc(&L.bias_p, L.cout_pad));
-    // split-bf16 MFMA needs a K chunk of 32 channels; the 2..4-channel image conv stays on the fp32 kernel
-    // (16-bit storage: every layer but the image convolution runs on the 16-bit kernels, whose loaders move 8-channel units)
-    L.fwd_split = mfma16 && L.cin_p >= (mixed ? 8 : 16);
-    L.dg_split = mfma16 && (mixed || L.cout_p >= 16);
-    L.dtz = L.fwd_split ? st : ST_F32;
-    {
-      bool ident = true;  // (the packed image: logical channel i in padded channel i)
-      for (int i = 0; i < Cin; ++i) ident = ident && i < (int)in_chmap.size() && in_chmap[i] == i;
-      L.thin = !L.fwd_split && ident && conv3x3_thin_ok(Cin, L.cout_p);
-      if (L.thin && wgrad_bufs) cap_slab = std::max(cap_slab, wgrad_thin_scratch(Cin, L.cout_p));
-    }
-    if (L.wg_split && !L.dg_split) any_mixed_dz = true;
-    // two fp16 MFMAs per product: not for the image convolution (raw inputs need not fit fp16: its forward runs on the fp32
-    // kernels), and only while the launch that writes dz has a max |dz| slot for each of its workgroups
-    // (<= 2048 x ceil(Cp / 1024); wider layers keep the three-MFMA arithmetic)
-    L.wg_np2 = cfg.precision == MIMO_PREC_SPLIT16 && L.wg_split && wgrad_bufs && L.fwd_split && wgrad_split_has_np2(L.cin_p, L.cout_p) &&
-               2048 * ceil_div(L.cout_p / 4, 256) <= kDzMaxSlots;
-    if (cfg.precision == MIMO_PREC_SPLIT16 || mixed) {  // decomposition per layer and direction (sched::wide_config)
-      if (L.fwd_split) L.fwd_wide = conv3x3_wide_rows(fwd_mode(), n, L.cin_p, L.cout_p, h, w);
-      if (L.dg_split) L.dg_wide = conv3x3_wide_rows(dgrad_mode(), n, L.cout_p, L.cin_p, h + 2, w + 2);
-    }
-    if (cfg.precision == MIMO_PREC_SPLIT16) {  // K split of the few-tile / long-K launches (conv3x3_ksplit): scratch for the slabs
-      if (L.fwd_split && !L.fwd_wide && !cfg.inference_only)
-        cap_kpart = std::max(cap_kpart, conv3x3_ksplit_scratch(fwd_mode(), n, L.cin_p, L.cout_pad, h, w, L.cout_p));
-      if (L.dg_split && !L.dg_wide && train_bufs)
-        cap_kpart = std::max(cap_kpart, conv3x3_ksplit_scratch(dgrad_mode(), n, L.cout_p, L.dg_rows, h + 2, w + 2, L.cin_p));
-    }
-    if (L.fwd_split && (cfg.precision == MIMO_PREC_SPLIT16 || cfg.precision == MIMO_PREC_FP16_MIXED)) {
+    MIMO_TRY(dalloc(&L.wf, pack::image_elems(PK_F32, r.fwd.rows, L.cin_p)));
+    if (train_bufs) MIMO_TRY(dalloc(&L.wd, pack::image_elems(PK_F32, r.dgrad.rows, L.cout_p)));
+    MIMO_TRY(dalloc(&L.bias_p, r.fwd.rows));
+    if (r.thin && wgrad_bufs) cap_slab = std::max(cap_slab, wgrad_thin_scratch(L.Cin, L.cout_p));
+    if (r.wg_split && !r.dgrad.split) any_mixed_dz = true;
+    cap_kpart = std::max(cap_kpart, std::max(r.fwd.kpart, r.dgrad.kpart));  // the slabs of the K-split launches
+    if (r.fwd.split && (cfg.precision == MIMO_PREC_SPLIT16 || cfg.precision == MIMO_PREC_FP16_MIXED)) {
       // one array for all layers' words: every pack zeroes it in one memset and takes the maxima afresh (pack_all)
       if (!wmax_pool) MIMO_TRY(dalloc(&wmax_pool, kMaxWmaxWords));
       if (wmax_used >= kMaxWmaxWords) {
@@ -624,46 +596,65 @@ struct mimo_plan {
       }
       L.wmax = wmax_pool + wmax_used++;
     }
-    if (L.fwd_split) {
+    if (r.fwd.split) {
       uint16_t* q = nullptr;
-      MIMO_TRY(dalloc(&q, pack::image_elems(pack::kind(cfg.precision, PACK_FWD, true, L.fwd_wide != 0),
-                                            L.fwd_wide ? L.fwd_wide : L.cout_pad, L.cin_p)));
+      MIMO_TRY(dalloc(&q, pack::image_elems(pack::kind(cfg.precision, PACK_FWD, true, r.fwd.wide != 0),
+                                            r.fwd.wide ? r.fwd.wide : r.fwd.rows, L.cin_p)));
       L.wf16 = q;
     }
-    if (L.dg_split && train_bufs) {
+    if (r.dgrad.split && train_bufs) {
       uint16_t* q = nullptr;
-      MIMO_TRY(dalloc(&q, pack::image_elems(pack::kind(cfg.precision, PACK_DGRAD, true, L.dg_wide != 0),
-                                            L.dg_wide ? L.dg_wide : L.dg_rows, L.cout_p)));
+      MIMO_TRY(dalloc(&q, pack::image_elems(pack::kind(cfg.precision, PACK_DGRAD, true, r.dgrad.wide != 0),
+                                            r.dgrad.wide ? r.dgrad.wide : r.dgrad.rows, L.cout_p)));
       L.wd16 = q;
     }
     MIMO_TRY(upload_ints(&L.cin_map, in_chmap));
-    std::vector<int> frm(L.cout_pad), drm(L.dg_rows), dcm(L.cout_p);
-    for (int i = 0; i < L.cout_pad; ++i) frm[i] = i < Cout ? i : -1;
-    for (int i = 0; i < L.dg_rows; ++i) drm[i] = i < L.cin_p ? in_chmap[i] : -1;
-    for (int i = 0; i < L.cout_p; ++i) dcm[i] = i < Cout ? i : -1;
+    std::vector<int> frm(r.fwd.rows), drm(r.dgrad.rows), dcm(L.cout_p);
+    for (int i = 0; i < r.fwd.rows; ++i) frm[i] = i < L.Cout ? i : -1;
+    for (int i = 0; i < r.dgrad.rows; ++i) drm[i] = i < L.cin_p ? in_chmap[i] : -1;
+    for (int i = 0; i < L.cout_p; ++i) dcm[i] = i < L.Cout ? i : -1;
     MIMO_TRY(upload_ints(&L.fwd_row_map, frm));
     MIMO_TRY(upload_ints(&L.dg_row_map, drm));
     MIMO_TRY(upload_ints(&L.dg_col_map, dcm));
     // (16-bit storage: the image convolution runs on the fp32 kernels and always goes through an fp32 z)
-    if (train_bufs || (mixed && !L.fwd_split)) MIMO_TRY(alloc_act(&L.z, (size_t)n * h * w * L.cout_p, L.dtz));
+    if (train_bufs || (mixed && !r.fwd.split)) MIMO_TRY(alloc_act(&L.z, (size_t)n * h * w * L.cout_p, r.dtz));
     MIMO_TRY(dalloc(&L.mean, L.cout_p));
     MIMO_TRY(dalloc(&L.invstd, L.cout_p));
     MIMO_TRY(dalloc(&L.scale, L.cout_p + kFinSlack));  // (+ zero slack: the next convolution's loaders read whole K chunks)
     MIMO_TRY(dalloc(&L.shift, L.cout_p + kFinSlack));
     MIMO_TRY(dalloc(&L.c1, L.cout_p));
     MIMO_TRY(dalloc(&L.c2, L.cout_p));
-    const size_t act = (size_t)n * h * w * L.cout_p;
-    const size_t padv = (size_t)n * (h + 2) * (w + 2) * L.cin_p;
-    cap_act = std::max(cap_act, act);
-    cap_pad = std::max(cap_pad, padv);
+    cap_act = std::max(cap_act, (size_t)n * h * w * L.cout_p);
+    cap_pad = std::max(cap_pad, (size_t)n * (h + 2) * (w + 2) * L.cin_p);
     cap_cout = std::max(cap_cout, (size_t)L.cout_p);
     // slabs + the reduction's group-sum levels (geometric: < splits/15 extra slabs)
-    cap_slab = std::max(cap_slab, (size_t)(L.wg_splits + L.wg_splits / 8 + 2) * 9 * L.wg_cin_pad * L.wg_cout_pad);
+    cap_slab = std::max(cap_slab, (size_t)(r.wg_splits + r.wg_splits / 8 + 2) * 9 * r.wg_cin_pad * r.wg_cout_pad);
     const size_t stat_rows = std::max(conv3x3_stat_rows(n, h, w), conv3x3_ws_stat_rows(n, h, w));
-    cap_partial = std::max(cap_partial, stat_rows * 2 * L.cout_pad);
+    cap_partial = std::max(cap_partial, stat_rows * 2 * r.fwd.rows);
     cap_partial = std::max(cap_partial, (size_t)kBnReduceMaxBlocks * 2 * L.cout_p);
-    cap_sums = std::max(cap_sums, (size_t)kMaxChunks * 2 * round_up(std::max(L.cout_pad, L.cout_p), 64));
+    cap_sums = std::max(cap_sums, (size_t)kMaxChunks * 2 * round_up(std::max(r.fwd.rows, L.cout_p), 64));
     return MIMO_OK;
+  }
+
+  // The ready-made launches of a layer, once build() has settled where its tensors live (rehome_skip, elide_output, the pool fusion)
+  void fill_launches(ConvBN& L) {
+    L.fwd = fill_conv_launch(L.r, PACK_FWD, L.N, L.H, L.W, L.cin_p, L.cout_p);
+    L.fwd.x = L.in;
+    L.fwd.ldx = L.ld_in;
+    L.fwd.y = L.z;
+    L.fwd.w = L.wf;
+    L.fwd.wpk = L.wf16;
+    L.fwd.bias = L.bias_p;
+    L.fwd.wmax = L.wmax;
+    L.dgrad = fill_conv_launch(L.r, PACK_DGRAD, L.N, L.H, L.W, L.cin_p, L.cout_p);
+    L.dgrad.w = L.wd;
+    L.dgrad.wpk = L.wd16;
+    L.wgrad = fill_wgrad_launch(L.r, L.N, L.H, L.W, L.cin_p, L.cout_p);
+    L.wgrad.x = L.fuse_in ? L.in_z : L.in;
+    L.wgrad.ldx = L.fuse_in ? L.ld_in_z : L.ld_in;
+    L.wgrad.in_scale = L.in_scale;  // (null without fuse_in)
+    L.wgrad.in_shift = L.in_shift;
+    L.wgrad.partial = s_wslab;
   }
 
   // Create a DoubleConv whose input has channel map in_chmap at resolution (h, w).
@@ -706,8 +697,8 @@ struct mimo_plan {
       // activated tensor — the second convolution's forward and its weight gradient — run on kernels that can (the
       // wide / 256-pixel wave-specialised forward, the wave-specialised weight gradient).  MIMO_FUSE_BN_IN=0: materialise.
       ConvBN& c2 = dc->c2;
-      if (fuse_bn_in && cfg.precision == MIMO_PREC_SPLIT16 && !cfg.inference_only && c2.fwd_split && c2.wg_split && dc->c1.dtz == ST_F32 &&
-          conv3x3_split_fuses_input(fwd_mode(), c2.fwd_wide, h, w) && wgrad_split_fuses_input(c2.cin_p, c2.cout_p, 0, 3)) {
+      if (fuse_bn_in && cfg.precision == MIMO_PREC_SPLIT16 && !cfg.inference_only && c2.r.fwd.split && c2.r.wg_split && dc->c1.r.dtz == ST_F32 &&
+          conv3x3_split_fuses_input(fwd_mode(), c2.r.fwd.wide, h, w) && wgrad_split_fuses_input(c2.cin_p, c2.cout_p, 0, 3)) {
         c2.fuse_in = true;
         c2.in_z = dc->c1.z;
         c2.ld_in_z = dc->c1.cout_p;
@@ -803,7 +794,7 @@ struct mimo_plan {
       // launches, so the two modes stay bit-identical)
       const char* e = getenv("MIMO_WGRAD_CUS");
       const int v = e ? atoi(e) : 0;
-      wg_cus = (v >= 8 && v <= 256) ? v : sched::wg_side_cus((long)N * H * W, S * f);
+      env = conv_env((v >= 8 && v <= 256) ? v : sched::wg_side_cus((long)N * H * W, S * f));
       const char* d = getenv("MIMO_DEBUG_WGRAD_DELAY_US");
       wg_delay_us = d ? std::max(0, std::min(atoi(d), 5000)) : 0;
     }
@@ -986,12 +977,12 @@ struct mimo_plan {
       for (auto& dc : dcs)
         for (ConvBN* L : {&dc->c1, &dc->c2}) {
           // (fp16 forward images follow the layer's max |w|, L->wmax; the data gradient's keep the fixed 2^8)
-          jobs.push_back(pack::make_job(PACK_FWD, cfg.precision, L->fwd_split, L->Cout, L->Cin, L->cin_p, L->cout_p, L->cout_pad,
-                                        L->fwd_wide, conv3x3_pair_tail(fwd_mode(), L->cin_p, L->H, L->W), L->fwd_row_map, L->cin_map,
-                                        L->fwd_split ? L->wf16 : (void*)L->wf, L->wmax, L->off_w, L->off_b, L->bias_p));
-          dg.push_back(pack::make_job(PACK_DGRAD, cfg.precision, L->dg_split, L->Cout, L->Cin, L->cin_p, L->cout_p, L->dg_rows,
-                                      L->dg_wide, conv3x3_pair_tail(dgrad_mode(), L->cout_p, L->H + 2, L->W + 2), L->dg_row_map,
-                                      L->dg_col_map, L->dg_split ? L->wd16 : (void*)L->wd, nullptr, L->off_w));
+          const ConvDir &fw = L->r.fwd, &dg_ = L->r.dgrad;
+          jobs.push_back(pack::make_job(PACK_FWD, cfg.precision, fw.split, L->Cout, L->Cin, L->cin_p, L->cout_p, fw.rows, fw.wide, fw.pair,
+                                        L->fwd_row_map, L->cin_map, fw.split ? L->wf16 : (void*)L->wf, L->wmax, L->off_w, L->off_b, L->bias_p));
+          dg.push_back(pack::make_job(PACK_DGRAD, cfg.precision, dg_.split, L->Cout, L->Cin, L->cin_p, L->cout_p, dg_.rows, dg_.wide, dg_.pair,
+                                      L->dg_row_map, L->dg_col_map, dg_.split ? L->wd16 : (void*)L->wd, nullptr, L->off_w));
+          fill_launches(*L);
         }
       n_fwd_jobs = (int)jobs.size();
       if (cfg.inference_only != 1) jobs.insert(jobs.end(), dg.begin(), dg.end());
@@ -1057,7 +1048,7 @@ struct mimo_plan {
     const bool training = call.training;
     // inference: BN(eval) + ReLU (+ channel-dropout) in the conv epilogue — not for the fp32-kernel image convolution
     // of the 16-bit storage modes, whose output type differs from the activation type
-    const bool fused = call.no_grad && !(mixed && !L.fwd_split);
+    const bool fused = call.no_grad && !(mixed && !L.r.fwd.split);
     if (!training && call.need_derive)
       MIMO_TRY(bn_eval_prepare_launch(L.Cout, L.cout_p, params + L.off_gamma, params + L.off_beta, bnbuf + L.off_rm,
                                       bnbuf + L.off_rv, cfg.bn_eps, L.mean, L.invstd, L.scale, L.shift, st, d_status));
@@ -1065,55 +1056,42 @@ struct mimo_plan {
     // eval-mode forward WITH a graph — FGSM — keeps the separate pass, whose finiteness test feeds the numerics status word:
     // the activated tensors exist in both.  The weight gradient applies scale / shift to z either way: identical values.)
     const bool fin = L.fuse_in && training && !call.no_grad;
-    ConvLaunch a;
-    a.x = fin ? L.in_z : L.in;
+    ConvLaunch a = L.fwd;
     if (fin) {
+      a.x = L.in_z;
+      a.ldx = L.ld_in_z;
       a.in_scale = L.in_scale;
       a.in_shift = L.in_shift;
     }
-    a.y = fused ? L.a : L.z;  // fused: the activation type; else z (fp32 on the fp32 kernel family)
-    if (fused) {
+    if (fused) {  // the activation and its type instead of z
+      a.y = L.a;
+      a.ldy = L.ld_a;
       a.ep_scale = L.scale;
       a.ep_shift = L.shift;
       a.ep_mask = mask;
       a.ep_mask_ld = L.Cout;
       a.status = d_status;
     }
-    a.w = L.wf;
-    a.bias = L.bias_p;
     a.stats = training ? s_partial : nullptr;
-    a.N = L.N;
-    a.Hi = a.Ho = L.H;
-    a.Wi = a.Wo = L.W;
-    a.ldx = fin ? L.ld_in_z : L.ld_in;
-    a.cin_p = L.cin_p;
-    a.ldy = fused ? L.ld_a : L.cout_p;
-    a.cout_pad = L.cout_pad;
-    a.cout_store = L.cout_p;
-    a.off = 1;
     int rows = 0;
     const int64_t P = (int64_t)L.N * L.H * L.W;
-    a.wpk = L.wf16;
-    a.wmax = L.fwd_split ? L.wmax : nullptr;
-    a.pair = (L.fwd_split && !L.fwd_wide) ? conv3x3_pair_tail(fwd_mode(), L.cin_p, L.H, L.W) : 0;
-    a.wide = L.fwd_wide;
     int pr = prof.begin(MIMO_PROF_CONV_FWD, st);
-    if (L.fwd_split)  // (training forward: with the K split of conv3x3_ksplit where that pays — few tiles, a long K walk)
+    if (L.r.fwd.split)  // (training forward: with the K split of conv3x3_ksplit where that pays — few tiles, a long K walk)
       MIMO_TRY(conv3x3_bf16x3_launch_k(a, fwd_mode(), &rows, st, (training && !fused) ? s_kpart : nullptr, cap_kpart));
-    else if (L.thin)
+    else if (L.r.thin)
       MIMO_TRY(conv3x3_thin_launch(a, L.Cin, &rows, st));
     else
       MIMO_TRY(conv3x3_launch(a, &rows, st));
     prof.end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), st);
     if (training) {
       if (rows <= kColsumMaxRows) {
-        MIMO_TRY(bn_fwd_stats_launch(s_partial, rows, L.cout_pad, L.Cout, L.cout_p, P, params + L.off_gamma,
+        MIMO_TRY(bn_fwd_stats_launch(s_partial, rows, L.r.fwd.rows, L.Cout, L.cout_p, P, params + L.off_gamma,
                                      params + L.off_beta, bnbuf + L.off_rm, bnbuf + L.off_rv, cfg.bn_momentum, cfg.bn_eps,
                                      L.mean, L.invstd, L.scale, L.shift, d_status, st));
       } else {
         int chunks = 0;
-        MIMO_TRY(rowsum_launch(s_partial, rows, 2 * L.cout_pad, s_sums, &chunks, st));
-        MIMO_TRY(bn_fwd_finalize_launch(s_sums, chunks, L.cout_pad, L.Cout, L.cout_p, P, params + L.off_gamma,
+        MIMO_TRY(rowsum_launch(s_partial, rows, 2 * L.r.fwd.rows, s_sums, &chunks, st));
+        MIMO_TRY(bn_fwd_finalize_launch(s_sums, chunks, L.r.fwd.rows, L.Cout, L.cout_p, P, params + L.off_gamma,
                                         params + L.off_beta, bnbuf + L.off_rm, bnbuf + L.off_rv, cfg.bn_momentum,
                                         cfg.bn_eps, L.mean, L.invstd, L.scale, L.shift, st));
       }
@@ -1121,10 +1099,10 @@ struct mimo_plan {
     if (!fused && !elide) {
       pr = prof.begin(MIMO_PROF_BN_RELU_FWD, st);
       if (L.pool_out)
-        MIMO_TRY(bn_relu_pool_fwd_launch(L.z, L.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, L.N,
+        MIMO_TRY(bn_relu_pool_fwd_launch(L.z, L.r.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, L.N,
                                          L.H, L.W, L.pool_out, L.pool_ld, st, training ? nullptr : d_status));
       else
-        MIMO_TRY(bn_relu_fwd_launch(L.z, L.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, P,
+        MIMO_TRY(bn_relu_fwd_launch(L.z, L.r.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, P,
                                     L.H * L.W, st, training ? nullptr : d_status));
       prof.end(pr, 0.0, (L.pool_out ? 9.0 : 8.0) * (double)P * L.cout_p, st);
     }
@@ -1136,7 +1114,7 @@ struct mimo_plan {
   // additionally need the element-wise final dropout off (checked where they are built).
   void elide_output(DoubleConv* dc) {
     if (!fuse_bn_in || cfg.precision != MIMO_PREC_SPLIT16 || cfg.inference_only || dc->drop_p > 0.f || dc->c2.pool_out ||
-        dc->c2.dtz != ST_F32)
+        dc->c2.r.dtz != ST_F32)
       return;
     dc->c2.act_elided = true;
     dc->out.z = dc->c2.z;
@@ -1441,28 +1419,11 @@ struct mimo_plan {
   // data gradient of layer L on the reflect-padded domain: dxpad_out [N,H+2,W+2,cin_p] from dz
   int dgrad_conv(ConvBN& L, const float* dz, float* dxpad_out, hipStream_t st) {
     const int64_t P = (int64_t)L.N * L.H * L.W;
-    ConvLaunch a;
+    ConvLaunch a = L.dgrad;
     a.x = dz;
     a.y = dxpad_out;
-    a.w = L.wd;
-    a.bias = nullptr;
-    a.stats = nullptr;
-    a.N = L.N;
-    a.Hi = L.H;
-    a.Wi = L.W;
-    a.ldx = L.cout_p;
-    a.cin_p = L.cout_p;
-    a.Ho = L.H + 2;
-    a.Wo = L.W + 2;
-    a.ldy = L.cin_p;
-    a.cout_pad = L.dg_rows;
-    a.cout_store = L.cin_p;
-    a.off = 2;
-    a.wpk = L.wd16;
-    a.pair = (L.dg_split && !L.dg_wide) ? conv3x3_pair_tail(dgrad_mode(), L.cout_p, L.H + 2, L.W + 2) : 0;
-    a.wide = L.dg_wide;
     int pr = prof.begin(MIMO_PROF_CONV_DGRAD, st);
-    if (L.dg_split)
+    if (L.r.dgrad.split)
       MIMO_TRY(conv3x3_bf16x3_launch_k(a, dgrad_mode(), nullptr, st, s_kpart, cap_kpart));
     else
       MIMO_TRY(conv3x3_launch(a, nullptr, st));
@@ -1482,7 +1443,7 @@ struct mimo_plan {
                float* partial, int* rows, hipStream_t st, float* absmax = nullptr, int* absmax_n = nullptr, hipEvent_t done = nullptr) {
     const int64_t P = (int64_t)L.N * L.H * L.W;
     const int pr = prof.begin(MIMO_PROF_BN_BWD_APPLY, st);
-    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, c1, c2,
+    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.r.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, c1, c2,
                                  L.cout_p, L.N, L.H, L.W, dz, split_out ? 1 : 0, partial, rows, st, absmax, absmax_n, done));
     prof.end(pr, 0.0, (8.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     return MIMO_OK;
@@ -1495,7 +1456,7 @@ struct mimo_plan {
   int convbn_input_grad(ConvBN& L, const GradSrc& src, const float* mask, float* dxpad_out, hipStream_t st) {
     float* dz = ring.dz[0];
     int rows = 0;
-    MIMO_TRY(bn_apply(L, src, mask, s_zero, s_zero, dz, L.dg_split && !mixed, nullptr, &rows, st));
+    MIMO_TRY(bn_apply(L, src, mask, s_zero, s_zero, dz, L.r.dgrad.split && !mixed, nullptr, &rows, st));
     return dgrad_conv(L, dz, dxpad_out, st);
   }
 
@@ -1507,7 +1468,7 @@ struct mimo_plan {
     int rows = 0;
     const int64_t P = (int64_t)L.N * L.H * L.W;
     const int pr = prof.begin(MIMO_PROF_BN_BWD_REDUCE, st);
-    MIMO_TRY(bnrelu_bwd_reduce_launch(src, this->st, L.z, L.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd,
+    MIMO_TRY(bnrelu_bwd_reduce_launch(src, this->st, L.z, L.r.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd,
                                       mask, L.Cout, L.cout_p, L.N, L.H, L.W, s_partial, &rows, st));
     prof.end(pr, 0.0, (4.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     if (src.kind == GS_HEAD) head_rows = rows;
@@ -1517,9 +1478,9 @@ struct mimo_plan {
     float* dz = ring.dz[s.b];
     // dz storage: bf16 hi|lo pairs when the data-gradient kernel is the bf16-pair one (then the weight
     // gradient is too); fp32 otherwise, with a split copy for a bf16-pair weight gradient
-    const bool needs_split_copy = L.wg_split && !L.dg_split && !thin_wg;
-    if (L.wg_np2 && !thin_wg) s.absmax = ring.dzmax[s.b];  // (travels with the dz buffer it describes: same slot, same events)
-    MIMO_TRY(bn_apply(L, src, mask, L.c1, L.c2, dz, L.dg_split && !mixed && !thin_wg, training ? nullptr : s_partial, &rows, st,
+    const bool needs_split_copy = L.r.wg_split && !L.r.dgrad.split && !thin_wg;
+    if (L.r.wg_np2 && !thin_wg) s.absmax = ring.dzmax[s.b];  // (travels with the dz buffer it describes: same slot, same events)
+    MIMO_TRY(bn_apply(L, src, mask, L.c1, L.c2, dz, L.r.dgrad.split && !mixed && !thin_wg, training ? nullptr : s_partial, &rows, st,
                       s.absmax, &s.absmax_n, ring.dz_event_on_launch(s, capturing, needs_split_copy)));
     s.dz_wg = dz;
     if (needs_split_copy) {
@@ -1536,43 +1497,24 @@ struct mimo_plan {
   // weight gradient of layer L and its reduction on `ws`; release != nullptr: recorded when the reduction completes
   int wgrad_issue(ConvBN& L, const DzRing::Slot& o, bool thin_wg, hipStream_t ws, hipEvent_t release) {
     const int64_t P = (int64_t)L.N * L.H * L.W;
-    WgradLaunch wg;
-    wg.x = L.fuse_in ? L.in_z : L.in;
-    if (L.fuse_in) {
-      wg.in_scale = L.in_scale;
-      wg.in_shift = L.in_shift;
-    }
+    WgradLaunch wg = L.wgrad;
     wg.dz = o.dz_wg;
-    wg.partial = s_wslab;
-    wg.N = L.N;
-    wg.H = L.H;
-    wg.W = L.W;
-    wg.ldx = L.fuse_in ? L.ld_in_z : L.ld_in;
-    wg.lddz = L.cout_p;
-    wg.cin_p = L.cin_p;
-    wg.cout_p = L.cout_p;
-    wg.cin_pad = L.wg_cin_pad;
-    wg.cout_pad = L.wg_cout_pad;
-    wg.splits = L.wg_splits;
-    wg.np = (cfg.precision == MIMO_PREC_BF16 || mixed) ? 1 : 3;
-    if (o.absmax && wg.np == 3) {  // two fp16 MFMAs per product (wgrad_split.hip NP == 2)
+    if (o.absmax) {  // two fp16 MFMAs per product (wgrad_split.hip NP == 2; bn_backward hands the slots out where r.wg_np2)
       wg.np = 2;
       wg.dz_absmax = o.absmax;
       wg.dz_absmax_n = o.absmax_n;
     }
-    // 16-bit storage: activations and dz plain NHWC 16-bit; the image convolution's input stays fp32
-    wg.store = !mixed ? 0 : (L.fwd_split ? (f16 ? 2 : 1) : (f16 ? 4 : 3));
     if (wg_delay_us > 0) MIMO_TRY(debug_delay_launch(wg_delay_us, ws));  // test hook: a late consumer
     const int pr = prof.begin(MIMO_PROF_CONV_WGRAD, ws);
     if (thin_wg)  // (dz as fp32, straight from the BatchNorm backward)
       MIMO_TRY(wgrad_thin_launch(L.in, L.ld_in, o.dz_wg, L.cout_p, L.N, L.H, L.W, L.Cin, L.Cout, L.cout_p, s_wslab, grads + L.off_w, ws));
-    else if (L.wg_split)
+    else if (L.r.wg_split)
       MIMO_TRY(wgrad_split_launch(wg, ws));
     else
       MIMO_TRY(wgrad_launch(wg, ws));
     prof.end(pr, 18.0 * L.Cin * L.Cout * (double)P, 4.0 * (double)P * (L.Cin + L.Cout), ws);
     if (!thin_wg)  // (the plain-FMA kernel's launch reduces its own partials)
-      MIMO_TRY(wgrad_reduce_launch(s_wslab, L.wg_splits, L.wg_cin_pad, L.wg_cout_pad, L.cin_map, L.cin_p, L.Cin, L.Cout,
+      MIMO_TRY(wgrad_reduce_launch(s_wslab, wg.splits, wg.cin_pad, wg.cout_pad, L.cin_map, L.cin_p, L.Cin, L.Cout,
                                    grads + L.off_w, ws, wg.dz_absmax, wg.dz_absmax_n, release));
     return MIMO_OK;
   }
@@ -1582,7 +1524,7 @@ struct mimo_plan {
     if (call.ig) return need_dgrad ? convbn_input_grad(L, src, mask, dxpad_out, st) : MIMO_OK;
     // the image convolution's weight gradient on the plain-FMA kernel reads dz as fp32 (no data gradient wanted: nothing
     // else reads this dz)
-    const bool thin_wg = L.thin && !mixed && !need_dgrad && wgrad_thin_ok(L.Cin, L.cout_p, L.N, L.H, L.W);
+    const bool thin_wg = L.r.wg_thin && !need_dgrad && wgrad_thin_ok(L.Cin, L.cout_p, L.N, L.H, L.W);
     // (with the profiler armed everything runs on the caller's stream: per-kernel times, not overlapped times)
     DzRing::Slot s = ring.acquire(wg_async && !prof.on);
     MIMO_TRY(bn_backward(L, src, mask, s, fwd_training, thin_wg, st));

@@ -212,6 +212,19 @@ static inline SplitCfg split_config(int mode, int N, int cin_p, int cout_pad, in
   return c;
 }
 
+// ---- image convolution on the plain-FMA kernels (conv_thin.hip) and the fp32 weight gradient (conv3x3.hip) -----------
+static inline bool thin_geometry_ok(int cin, int cout_p) { return cin >= 1 && cin <= 4 && cout_p % 4 == 0 && cout_p >= 4 && cout_p <= 256; }
+static inline int wg32_tc(int W) { return W >= 24 ? 32 : (W >= 12 ? 16 : 8); }  // pixel-tile width; 256-pixel tiles
+static inline int wg32_pick_splits(int N, int H, int W, int cin_pad, int cout_pad) {
+  const int wtiles = (cin_pad / 32) * (cout_pad / 32), tc = wg32_tc(W);
+  const int tiles = N * cdiv(H, 256 / tc) * cdiv(W, tc);
+  int splits = cdiv(2048, wtiles);
+  if (splits > tiles) splits = tiles;
+  if (splits > 1024) splits = 1024;
+  if (splits < 1) splits = 1;
+  return splits;
+}
+
 // ---- split weight gradient (wgrad_split.hip) --------------------------------------------------------------------
 constexpr int kWgTC = 32;  // pixel-tile width of the weight-gradient kernels
 // channel tile (32 / 48 / 64) that pads least; 48 only where it saves >= 30 % of padded work

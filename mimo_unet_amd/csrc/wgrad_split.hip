@@ -672,24 +672,16 @@ __global__ __launch_bounds__(512, 2) void wgrad_split_ws_kernel(WgradLaunch a, i
 }
 
 // host-side choices (channel tiles, split counts): tile_sched.h, host-testable
-static bool wgrad_ws_enabled() {
+bool wgrad_ws_enabled() {
   static const bool on = !(getenv("MIMO_WGRAD_WS") && atoi(getenv("MIMO_WGRAD_WS")) == 0);
   return on;
 }
-void wgrad_split_tiles(int cin_p, int cout_p, int* CI, int* CO) { sched::wg_tiles(cin_p, cout_p, wgrad_ws_enabled(), CI, CO); }
+// (the plan sizes a launch with the same rule and sched::wg_pick_splits: conv_recipe.h)
+static void wgrad_split_tiles(int cin_p, int cout_p, int* CI, int* CO) { sched::wg_tiles(cin_p, cout_p, wgrad_ws_enabled(), CI, CO); }
 static bool wgrad_use_ws(int CI, int CO) { return sched::wg_use_ws(CI, CO, wgrad_ws_enabled()); }
-int wgrad_split_pick_splits(int N, int H, int W, int cin_pad, int cout_pad, int CI, int CO, int store, int cus) {
-  return sched::wg_pick_splits(N, H, W, cin_pad, cout_pad, CI, CO, wgrad_ws_enabled(), wgrad_s16(store),
-                               cus >= 8 && cus <= 256 ? cus : 256);
-}
-
-// 1 when this geometry runs on the kernel that has the two-MFMA (fp16) instances: WgradLaunch::np = 2
-int wgrad_split_has_np2(int cin_p, int cout_p) {
-  const bool on = !(getenv("MIMO_WGRAD_NP") && atoi(getenv("MIMO_WGRAD_NP")) == 3);  // =3: three bf16 MFMAs (rounds 1-4); read per plan / call
-  int CI, CO;
-  wgrad_split_tiles(cin_p, cout_p, &CI, &CO);
-  return on && wgrad_use_ws(CI, CO) ? 1 : 0;
-}
+// two fp16 MFMAs per product on the wave-specialised kernel (WgradLaunch::np = 2); MIMO_WGRAD_NP=3: three bf16 MFMAs
+// (rounds 1-4); read per plan / call
+bool wgrad_np2_enabled() { return !(getenv("MIMO_WGRAD_NP") && atoi(getenv("MIMO_WGRAD_NP")) == 3); }
 
 int wgrad_split_fuses_input(int cin_p, int cout_p, int store, int np) {
   int CI, CO;

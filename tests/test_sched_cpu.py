@@ -46,6 +46,14 @@ def test_pack_layout_under_asan_ubsan(tmp_path):
     _run_host_test(tmp_path, "pack_layout_test")
 
 
+def test_conv_recipe_under_asan_ubsan(tmp_path):
+    """mimo_unet_amd/csrc/conv_recipe.h: the launch decisions of every convolution of cfg2, cfg3 and cfg4 at the benchmark's
+    batches and of the per-operator test geometries, in the five precisions and with the image kernels and the
+    wave-specialised kernels on and off, against a table of what the code it replaced decided; and the pack job of every
+    row carries the pair tail and wide rows its launch gets (tests/host/conv_recipe_test.cpp)."""
+    _run_host_test(tmp_path, "conv_recipe_test")
+
+
 def test_kernels_use_the_tested_header():
     """No private copy of a scheduler is left in the .hip sources.  conv_bf16x3.hip reaches the channel-tile width
     (sched::split_pick_nf), the tile shape and the grid through sched::split_config alone: it picks no tile, prices nothing
@@ -53,8 +61,12 @@ def test_kernels_use_the_tested_header():
     csrc = os.path.join(ROOT, "mimo_unet_amd", "csrc")
     for fn, needles in (("conv_bf16x3.hip", ["sched::split_config", "sched::split_pick_ksplit", "sched::ws_tail_pairs", "sched::split_fuses_input",
                                              "sched::ksplit_legal", "sched::ksplit_scratch_floats", "sched::split_maxpix", "sched::kWsStatRows"]), ("conv3x3.hip", ["sched::pick_tile_n", "sched::conv_cout_pad", "sched::conv_stat_rows"]),
-                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits"]), ("plan.hip", ["sched::wg_side_cus", "sched::DzRingPolicy", "sched::GraphReplayPolicy", "pack::make_job", "pack::image_elems"]),
-                        ("ops_api.hip", ["pack::make_job", "pack::image_elems"]),("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
+                        ("wgrad_split.hip", ["sched::wg_tiles", "sched::wg_pick_splits", "sched::wg_use_ws"]),
+                        # the per-layer decisions (pair tail, wide rows, K-split scratch, weight-gradient tiles and splits) are taken in one place
+                        ("conv_recipe.h", ["sched::ws_tail_pairs", "sched::wide_config", "sched::split_pick_ksplit", "sched::ksplit_scratch_floats",
+                                           "sched::wg_tiles", "sched::wg_pick_splits", "sched::wg32_pick_splits", "sched::thin_geometry_ok"]),
+                        ("plan.hip", ["conv_recipe(", "fill_conv_launch", "fill_wgrad_launch", "sched::wg_side_cus", "sched::DzRingPolicy", "sched::GraphReplayPolicy", "pack::make_job", "pack::image_elems"]),
+                        ("ops_api.hip", ["conv_recipe(", "fill_conv_launch", "fill_wgrad_launch", "pack::make_job", "pack::image_elems"]),("common.h", ["sched::xcd_virtual_index", "sched::w16_scale", "sched::wg_dz_scale"]),
                         ("conv_wide.hip", ["sched::wide_config", "sched::wide_grid_x"])):
         text = open(os.path.join(csrc, fn)).read()
         for n in needles:
@@ -63,5 +75,11 @@ def test_kernels_use_the_tested_header():
     for gone in ("pick_tile_n", "use_big_tile", "kKsplitReduceUnits", "kWgPerCU", "(1 + c)", "(1 + nf)", "tail <= 16"):
         assert gone not in split, gone
     assert split.count('getenv("MIMO_CONV_WS")') == 2 and split.count('getenv("MIMO_CONV_KSPLIT")') == 1  # one statement each
-    header = open(os.path.join(csrc, "tile_sched.h")).read()
-    assert "getenv" not in header and "hip/" not in header
+    for h in ("tile_sched.h", "conv_recipe.h", "conv_launch.h"):
+        header = open(os.path.join(csrc, h)).read()
+        assert "getenv" not in header and "hip/" not in header, h
+    # ... and nowhere else: the plan and the entry points decide nothing about a convolution launch themselves
+    for fn in ("plan.hip", "ops_api.hip"):
+        text = open(os.path.join(csrc, fn)).read()
+        for gone in ("ws_tail_pairs", "pair_tail", "wide_config", "wide_rows", "wg_tiles", "wgrad_split_tiles", "pick_splits", "pick_ksplit"):
+            assert gone not in text, (fn, gone)
