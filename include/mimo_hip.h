@@ -767,6 +767,60 @@ enum { MIMO_GATHER_MAX_FIELDS = 4 };
 int mimo_dataset_gather(const mimo_gather_field* fields, int n_fields, const int64_t* index, const int64_t* remap,
                         int64_t n_samples, int32_t batch, int32_t h, int32_t w, mimo_stream stream);
 
+/* ---- whole-scene inference: tiles gathered from a scene kept in HBM, and per-tile results stitched back into scene maps.
+ * The reference only knows patches (SEN12TP scenes are cut into 256-pixel patches at a stride of 249 by the dataset,
+ * scripts/test/test_ndvi.py:152-160, sen12tp_datamodule.py:54-66); the cutting, the overlaps and the seams are these two.
+ *
+ * Geometry.  Along an axis of length L with patch P and stride s, 1 <= s <= P <= L:
+ *   tiles        n = 1 + ceil((L - P) / s)
+ *   origins      o_k = min(k s, L - P)            (the last tile is shifted inwards, never padded)
+ *   covering     K(p) = {k : o_k <= p < o_k + P}  (a contiguous range, never empty)
+ * Tiles of a scene [h, w] are numbered row-major, t = ky nx + kx, T = ny nx, with origin (oy(t), ox(t)) = (o_ky, o_kx).
+ *
+ * Windows, for i in [0, P):  MIMO_WINDOW_UNIFORM w(i) = 1;  MIMO_WINDOW_LINEAR w(i) = min(i + 1, P - i);
+ * MIMO_WINDOW_CROP: weight 1 for the owner of p and 0 for every other tile, the owner being the k in K(p) with the largest
+ * linear weight w(p - o_k), ties to the lowest k ("keep the centre of each tile").
+ * Normalised 1-D weight (uniform, linear), in fp32:  a_k(p) = w(p - o_k) / sum over ascending j in K(p) of w(p - o_j) — the
+ * terms are small integers, the sum is exact, the division is the one correctly rounded operation.  The 2-D weight of tile
+ * t at (y, x) is fl(a_ky(y) a_kx(x)).  The normalisation is separable: no weight-sum buffer, no finalising pass.
+ *
+ * mimo_scene_gather_tiles: scene [c, h, w] fp32 -> dst [n, c, P, P] fp32, both contiguous device memory,
+ *   dst[b, k, y, x] = scene[k, oy(t) + y, ox(t) + x],  t = min(t0 + b, T - 1).
+ * The clamp is part of the definition: the last, short batch of a scene repeats the last tile and keeps the call shape of
+ * all the others.  Quads of a tile row move as one float4 where they lie on a 16-byte boundary (source and destination
+ * judged separately), as scalars otherwise.  MIMO_ERR_INVALID with a message and nothing launched: a null or not 4-byte
+ * aligned scene / dst, c, h, w, patch, stride or n < 1, patch > h or w, stride > patch, t0 outside [0, T),
+ * n * c * P * P >= 2^31, c * h * w > 2^60.
+ *
+ * mimo_scene_stitch: adds tiles t0 ... t0 + n_valid - 1 into up to 4 scene maps at once.  `fields` is a HOST array and
+ * travels in the kernel arguments; field f has a source [n, c_f, P, P] (row b is tile t0 + b; rows >= n_valid are not read)
+ * and a destination [c_f, h, w], fp32, contiguous device memory.  For every pixel (y, x) of every channel that at least
+ * one tile of the launch covers, with the covering tiles of the launch taken in ascending t:
+ *   uniform, linear:  acc = (lowest covering tile overall < t0) ? dst : nothing;
+ *                     per tile:  term = fl(a_t v_t);  acc = acc is nothing ? term : fl(acc + term);   dst = acc
+ *   crop:             dst = v_owner where the owner is a tile of the launch, untouched otherwise
+ * Every multiply and add rounds to nearest on its own (no fused multiply-add).  A pixel whose lowest covering tile lies in
+ * the launch is STORED, any other is read, added to and stored: the destination needs no memset, provided the launches of
+ * a scene cover 0 ... T - 1 in ascending order on one stream.  The per-pixel order is ascending t whatever the batch
+ * size, so the stitched scene is bit-identical for any batching of the same tile values.  Pixels covered by no tile of
+ * the launch are not touched.  No allocation, no synchronisation, no atomics.  MIMO_ERR_INVALID with a message and
+ * nothing launched: n_fields outside 1 ... 4, a null table / src / dst, a src or dst not 4-byte aligned, c_f outside
+ * 1 ... 65535, h, w, patch or stride < 1, patch > h or w, stride > patch, patch > 4096 (the window sums stay exact in
+ * fp32), an unknown window, t0 < 0, n_valid < 1, t0 + n_valid > T, h * w >= 2^31,
+ * n_valid * c_f * P * P > 2^60. */
+enum { MIMO_WINDOW_UNIFORM = 0, MIMO_WINDOW_LINEAR = 1, MIMO_WINDOW_CROP = 2 };
+int mimo_scene_gather_tiles(const float* scene, float* dst, int32_t c, int32_t h, int32_t w, int32_t patch, int32_t stride,
+                            int32_t t0, int32_t n, mimo_stream stream);
+typedef struct mimo_stitch_field {
+  const float* src;      /* [n, c, P, P] fp32, contiguous */
+  float* dst;            /* [c, h, w] fp32, contiguous */
+  int32_t c;             /* 1 ... 65535 */
+  int32_t reserved;
+} mimo_stitch_field;
+enum { MIMO_STITCH_MAX_FIELDS = 4 };
+int mimo_scene_stitch(const mimo_stitch_field* fields, int n_fields, int32_t h, int32_t w, int32_t patch, int32_t stride,
+                      int32_t window, int32_t t0, int32_t n_valid, mimo_stream stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -125,9 +125,15 @@ class GatherField(C.Structure):
     _fields_ = [("src", C.c_void_p), ("lut", C.c_void_p), ("dst", C.c_void_p), ("c", C.c_int32), ("reserved", C.c_int32)]
 
 
+class StitchField(C.Structure):
+    """mimo_stitch_field (include/mimo_hip.h)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("c", C.c_int32), ("reserved", C.c_int32)]
+
+
 LOSS_KINDS = {"laplace_nll": 0, "gaussian_nll": 1}
 # "bf16-mixed" / "16-mixed": Lightning's names for bf16 / fp16 autocast training — here 16-bit storage + operands
 PRECISIONS = {"fp32": 0, "split16": 1, "bf16": 2, "bf16-mixed": 3, "16-mixed": 4}
+WINDOWS = {"uniform": 0, "linear": 1, "crop": 2}  # MIMO_WINDOW_*
 
 _lib = None
 
@@ -207,6 +213,8 @@ _SIGNATURES = {
     "mimo_monitor_scratch_bytes": (C.c_size_t, [C.c_int]),
     "mimo_monitor_grids": (C.c_int, [C.POINTER(MonitorPanel), C.c_int, _P, _P, _P]),
     "mimo_dataset_gather": (C.c_int, [C.POINTER(GatherField), C.c_int, _P, _P, _L, _I, _I, _I, _P]),
+    "mimo_scene_gather_tiles": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mimo_scene_stitch": (C.c_int, [C.POINTER(StitchField), C.c_int, _I, _I, _I, _I, _I, _I, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

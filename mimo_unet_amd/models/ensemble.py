@@ -67,6 +67,12 @@ class EnsembleModule(LightningModule):
     def forward(self, x: torch.Tensor):
         """x [B,C_in,H,W] -> (mean, aleatoric_variance, epistemic_variance) [B,C_out,H,W], or the raw
         (p1, p2) [B,S_total,C_out,H,W] when `return_raw_predictions`."""
+        res = self.forward_on_device(x)
+        return res if self.keep_on_device else tuple(t.cpu() for t in res)
+
+    def forward_on_device(self, x: torch.Tensor):
+        """What `forward` returns, still on the device whatever `keep_on_device` says (`inference.predict_scene` stitches
+        the results of a batch without a trip through host memory)."""
         passes = max(1, self.monte_carlo_steps)
         b = x.shape[0]
         p1_list, p2_list = [], []
@@ -106,4 +112,4 @@ class EnsembleModule(LightningModule):
                 res = (p1, p2)
             else:
                 res = compute_uncertainties(self.loss_fn, y_preds=p1, log_params=p2)
-        return res if self.keep_on_device else tuple(t.cpu() for t in res)
+        return res
