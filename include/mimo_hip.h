@@ -489,7 +489,7 @@ int mimo_op_maxpool2x2(const float* x, float* y, int32_t n, int32_t h, int32_t w
 int mimo_op_upsample_cat(const float* skip, const float* low, float* out, int32_t n, int32_t hs, int32_t ws,
                          int32_t cs_p, int32_t hl, int32_t wl, int32_t cl_p, mimo_stream stream);
 
-/* ---- single-operator entry points of the backward element-wise kernels (elementwise.hip) -------
+/* ---- single-operator entry points of the backward element-wise kernels (ew_bn_bwd.hip, ew_head_loss.hip) -------
  * NHWC fp32 tensors whose channel count c_p is a multiple of 8; "ld*" = elements per pixel of the buffer a pointer indexes
  * (a tensor may be a channel slice of a wider buffer; pitches and channel offsets are multiples of 4).  "dxpad" is a
  * gradient on the reflect-padded domain [n, h + 2, w + 2, ldp], as the data-gradient convolution leaves it; fold = the
@@ -583,7 +583,7 @@ typedef struct mimo_op_head_backward_args {
 } mimo_op_head_backward_args;
 int mimo_op_head_backward(const mimo_op_head_backward_args* args, mimo_stream stream);
 
-/* ---- single-operator entry points of the forward element-wise kernels (elementwise.hip) -------
+/* ---- single-operator entry points of the forward element-wise kernels (ew_bn_fwd.hip, ew_resample.hip, ew_dropout.hip, ew_head_loss.hip) -------
  * The conventions of the backward block above: fp32 NHWC tensors at the interface, c_p a multiple of 8, pitches multiples of
  * 4; MIMO_PREC_BF16_MIXED / MIMO_PREC_FP16_MIXED round whole activation-like buffers (at their pitch) into 16-bit copies,
  * run the 16-bit storage kernels and widen the outputs again (an output buffer makes the round trip as a whole: what the

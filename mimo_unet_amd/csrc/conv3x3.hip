@@ -485,7 +485,7 @@ int wgrad_reduce_launch(const float* partial, int splits, int cin_pad, int cout_
     src = out;
     n = groups;
   }
-  // (`done`: recorded when the last kernel of the reduction completes, attached to its launch — elementwise.hip bn_bwd_apply_launch)
+  // (`done`: recorded when the last kernel of the reduction completes, attached to its launch — ew_bn_bwd.hip bn_bwd_apply_launch)
   hipExtLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, nullptr, done, 0, src, n, cin_pad, cout_pad,
                         cin_map, cin_p, cin, cout, dw, dz_absmax, dz_absmax_n);
   MIMO_KERNEL_CHECK();

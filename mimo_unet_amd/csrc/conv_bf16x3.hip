@@ -10,7 +10,7 @@
 //   * F16 = false (data gradient): bf16 hi/lo keep fp32's exponent range for the tiny dz values;
 //     ~1e-5 per product on the gradient side is harmless (gradient error 2e-5, same emulation).
 //     The input (dz) arrives PRE-SPLIT — per pixel and 32-channel chunk [hi 32 | lo 32] bf16, written
-//     by the BatchNorm-backward kernel (elementwise.hip st_split4) — which is this kernel's LDS row
+//     by the BatchNorm-backward kernel (ew_bn_bwd.hip st_split4) — which is this kernel's LDS row
 //     image: the loader is a plain copy of one 128-byte line per (pixel, chunk).
 //
 // Same implicit GEMM as conv3x3.hip (M = TRxTC output pixels of one image, N = output channels,

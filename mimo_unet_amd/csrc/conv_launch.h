@@ -11,7 +11,7 @@ namespace mimo {
 //   sum_{kh,kw,ci} w[kh,kw][co][ci] * X(n, oy+kh-off, ox+kw-off, ci)
 // off == 1: Ho==Hi, X is reflect-padded (forward conv, components.py:23,26)
 // off == 2: Ho==Hi+2, X is zero outside the image (transposed conv producing the gradient on
-//           the reflect-PADDED domain; consumers fold the border back, see fold_* in elementwise.hip)
+//           the reflect-PADDED domain; consumers fold the border back, see fold_read in ew_device.h)
 constexpr int kFinSlack = 32;  // zero floats behind ConvLaunch::in_scale / in_shift (a 32-channel chunk may start at cin_p - 8)
 struct ConvLaunch {
   const float* x;

@@ -7,7 +7,7 @@
 // With <= 4 input channels the layer is 18..36 multiply-adds per output value next to 4 bytes written (forward) or read
 // (weight gradient): it is bound by the HBM pass over the 30-channel tensor, not by arithmetic, and padding its K
 // dimension to an MFMA chunk (16 / 32 channels) only added staging and zero products in front of that pass.  One thread
-// owns one pixel x four output channels (the mapping of the bandwidth kernels in elementwise.hip): its 9 x CIN x 4 weights
+// owns one pixel x four output channels (the mapping of the bandwidth kernels, pixquad in ew_device.h): its 9 x CIN x 4 weights
 // (forward) or weight-gradient accumulators (backward) live in registers, the 3x3 neighbourhoods come from a
 // reflect-padded halo tile of the image in LDS (loaded once per 8 x 32-pixel tile, double-buffered), the 30-channel tensor
 // is touched once with 16-byte accesses.  (A first version read the neighbourhood straight from global memory: nine loads

@@ -1,4 +1,4 @@
-// Launch wrappers of the bandwidth-class kernels (elementwise.hip).  All tensors NHWC, channel count padded to a
+// Launch wrappers of the bandwidth-class kernels (ew_*.hip, one file per operator group).  All tensors NHWC, channel count padded to a
 // multiple of 8; "ld" = ELEMENTS per pixel of the buffer a pointer indexes (a tensor may be a channel slice of a
 // wider concat buffer).  Activation-like tensors (conv outputs z, activations a, their gradients da / dxpad / dz)
 // are fp32, or — in the 16-bit storage modes (mimo_precision *_MIXED) — bf16 / fp16: such pointers are passed
@@ -61,15 +61,23 @@ int bn_fwd_finalize_launch(const double* sums, int chunks, int cout_pad, int C, 
 int bn_eval_prepare_launch(int C, int Cp, const float* gamma, const float* beta, const float* running_mean,
                            const float* running_var, float eps, float* mean, float* invstd, float* scale,
                            float* shift, hipStream_t st, int* status = nullptr);
+// What every pass over one ConvBN's pre-activation tensor z needs, forward and backward; filled once per layer (the plan:
+// fill_launches; the mimo_op_* entry points: from their argument struct).  Per call vary only the Dropout2d mask, the
+// gradient source and the outputs.  (mean / invstd: read by the backward passes only.)
+struct BnReluLayer {
+  const void* z;  // pre-activation tensor,
+  int dtz, ldz;   // its StoreType and elements per pixel
+  int dta;        // StoreType of the activation-like tensors (a, da, dxpad, dz)
+  const float *scale, *shift, *mean, *invstd;
+  int C, Cp, N, H, W;
+};
 // a = relu(z*scale+shift) * mask[n][c]
 // status != nullptr (eval mode): kStatusFwdStats is OR-ed into it when an input element is not finite (fmaxf would drop it)
-int bn_relu_fwd_launch(const void* z, int dtz, int ldz, void* a, int dta, int lda, const float* scale, const float* shift,
-                       const float* mask, int C, int Cp, int64_t P, int HW, hipStream_t st, int* status = nullptr);
+int bn_relu_fwd_launch(const BnReluLayer& L, const float* mask, void* a, int lda, int* status, hipStream_t st);
 
 // same, for a tensor that feeds MaxPool2d(2): also writes pool[N,H/2,W/2] = maxpool2x2(a) (one pass, 2x2 window per thread)
-int bn_relu_pool_fwd_launch(const void* z, int dtz, int ldz, void* a, int dta, int lda, const float* scale, const float* shift,
-                            const float* mask, int C, int Cp, int N, int H, int W, void* pool, int ldpool, hipStream_t st,
-                            int* status = nullptr);
+int bn_relu_pool_fwd_launch(const BnReluLayer& L, const float* mask, void* a, int lda, void* pool, int ldpool, int* status,
+                            hipStream_t st);
 
 // ---- pooling / upsampling ---------------------------------------------------------------
 int maxpool_fwd_launch(const void* a, int dt, int lda, int N, int H, int W, int Cp, void* out, int ldo, hipStream_t st);
@@ -166,17 +174,20 @@ struct GradSrc {
   }
 };
 // pass 1: partial rows of (sum dy, sum dy*xhat)
-int bnrelu_bwd_reduce_launch(const GradSrc& src, int dta, const void* z, int dtz, int ldz,
-                             const float* scale, const float* shift, const float* mean, const float* invstd,
-                             const float* mask, int C, int Cp, int N, int H, int W, float* partial, int* rows,
+int bnrelu_bwd_reduce_launch(const BnReluLayer& L, const GradSrc& src, const float* mask, float* partial, int* rows,
                              hipStream_t st);
 // pass 2: dz = scale * (dy - c1 - xhat*c2); partial rows of sum dz (conv bias gradient)
-int bn_bwd_apply_launch(const GradSrc& src, int dta, const void* z, int dtz, int ldz,
-                        const float* scale, const float* shift, const float* mean, const float* invstd, const float* mask,
-                        int C, const float* c1, const float* c2, int Cp, int N, int H, int W, void* dz, int split_out,
-                        float* partial, int* rows, hipStream_t st, float* absmax = nullptr,
-                        int* absmax_n = nullptr,  // absmax: *absmax_n per-workgroup maxima of |dz| (WgradLaunch::dz_absmax, <= kDzMaxSlots)
-                        hipEvent_t done = nullptr);  // != nullptr: recorded when the kernel completes (attached to the launch)
+struct BnBwdApplyOut {
+  const float *c1, *c2;  // bn_bwd_stats_launch's vectors (input of the pass; zeros: dz = scale * dy)
+  void* dz;              // [N,H,W,Cp], element type BnReluLayer::dta
+  int split_out;         // != 0: dz as bf16 (hi, lo) pair records (split_pairs_launch's form; fp32 storage only)
+  float* partial;        // nullptr: no partial rows of sum dz wanted
+  int* rows;             // workgroups along x = partial rows
+  float* absmax;         // nullptr, or *absmax_n per-workgroup maxima of |dz| are left here (WgradLaunch::dz_absmax,
+  int* absmax_n;         //   <= kDzMaxSlots; absmax_n may be nullptr)
+  hipEvent_t done;       // != nullptr: recorded when the kernel completes (attached to the launch)
+};
+int bn_bwd_apply_launch(const BnReluLayer& L, const GradSrc& src, const float* mask, const BnBwdApplyOut& out, hipStream_t st);
 // dst[p] = [hi Cp bf16 | lo Cp bf16] of src[p][Cp] — the storage the bf16-pair convolution kernels read
 // (split_out != 0 above writes dz in this form directly)
 // absmax != nullptr: *absmax_n per-workgroup maxima of |src| are left there (WgradLaunch::dz_absmax; capacity kDzMaxSlots floats)

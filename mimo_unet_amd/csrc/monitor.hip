@@ -308,7 +308,7 @@ extern "C" int mimo_monitor_grids(const mimo_monitor_panel* panels, int n_panels
     hipLaunchKernelGGL(monitor_range_kernel, dim3(kMonPartials, n_panels), dim3(kMonThreads), 0, st, tab, (float*)scratch);
     MIMO_KERNEL_CHECK();
   }
-  // grid-stride over quads, 2048 workgroups at most over all panels (8 per CU): elementwise.hip's and fgsm.hip's rule
+  // grid-stride over quads, 2048 workgroups at most over all panels (8 per CU): the ew_*.hip kernels' and fgsm.hip's rule
   const int per_panel = std::max(1, 2048 / n_panels);
   const int blocks = (int)std::min<int64_t>(ceil_div64(ceil_div64(max_pix, 4), kMonThreads), per_panel);
   hipLaunchKernelGGL(monitor_grid_kernel, dim3(blocks, n_panels), dim3(kMonThreads), 0, st, tab, (const float*)scratch);

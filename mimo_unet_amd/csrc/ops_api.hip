@@ -418,7 +418,7 @@ int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* p, mimo_stream
   GradSrc src;
   src.kind = a.kind;
   Temp t(who);
-  Stored gsrc, sk, zs, dzs;
+  Stored gsrc, zs, dzs;
   float* head_partial = nullptr;
   if (a.kind == GS_PLAIN) {
     if (!a.da || bad_slice(who, "da", a.ldda, 0, Cp)) return MIMO_ERR_INVALID;
@@ -480,15 +480,15 @@ int mimo_op_bn_relu_backward(const mimo_op_bn_relu_backward_args* p, mimo_stream
   int* status = t.get<int>(1);
   MIMO_TRY(t.ok());
   const int dt = store_type(prec);
+  const BnReluLayer L = {zs.in, dt, a.ldz, dt, a.scale, a.shift, a.mean, a.invstd, a.c, Cp, N, H, W};
   int rows = 0;
-  MIMO_TRY(bnrelu_bwd_reduce_launch(src, dt, zs.in, dt, a.ldz, a.scale, a.shift, a.mean, a.invstd, a.mask, a.c, Cp, N, H, W, partial,
-                                    &rows, st));
+  MIMO_TRY(bnrelu_bwd_reduce_launch(L, src, a.mask, partial, &rows, st));
   MIMO_TRY(bn_bwd_stats_launch(partial, rows, a.c, Cp, (int64_t)N * H * W, a.training ? 1 : 0, a.c1, a.c2, a.dgamma, a.dbeta,
                                a.training ? a.dbias : nullptr, status, st));
   if (a.kind == GS_HEAD) MIMO_TRY(head_bwd_stats_launch(head_partial, rows, a.c, Cp, 2, a.head_dw, a.head_db, st));
   int absmax_n = 0;
-  MIMO_TRY(bn_bwd_apply_launch(src, dt, zs.in, dt, a.ldz, a.scale, a.shift, a.mean, a.invstd, a.mask, a.c, a.c1, a.c2, Cp, N, H, W,
-                               dzs.out, a.split_out ? 1 : 0, a.training ? nullptr : partial, &rows, st, a.absmax, &absmax_n));
+  MIMO_TRY(bn_bwd_apply_launch(L, src, a.mask, BnBwdApplyOut{a.c1, a.c2, dzs.out, a.split_out ? 1 : 0, a.training ? nullptr : partial,
+                                                             &rows, a.absmax, &absmax_n, nullptr}, st));
   if (!a.training) MIMO_TRY(colsum_vec_launch(partial, rows, Cp, a.c, a.dbias, st));
   MIMO_TRY(stage_back(dzs, prec, st));
   MIMO_HIP_CHECK(hipStreamSynchronize(st));
@@ -641,14 +641,14 @@ int mimo_op_bn_relu_forward(const mimo_op_bn_relu_forward_args* p, mimo_stream s
   MIMO_TRY(t.ok());
   MIMO_TRY(stage_in(t, a.z, P * a.ldz, zprec, st, &zs));
   MIMO_TRY(stage_out(t, a.a, P * a.lda, prec, st, &as));
+  // (the forward passes read neither mean nor invstd)
+  const BnReluLayer L = {zs.in, store_type(zprec), a.ldz, store_type(prec), a.scale, a.shift, nullptr, nullptr, a.c, Cp, a.n, a.h, a.w};
   if (a.pool) {
     MIMO_TRY(stage_out(t, a.pool, (int64_t)a.n * (a.h / 2) * (a.w / 2) * a.ldpool, prec, st, &ps));
-    MIMO_TRY(bn_relu_pool_fwd_launch(zs.in, store_type(zprec), a.ldz, as.out, store_type(prec), a.lda, a.scale, a.shift, a.mask, a.c, Cp,
-                                     a.n, a.h, a.w, ps.out, a.ldpool, st, status));
+    MIMO_TRY(bn_relu_pool_fwd_launch(L, a.mask, as.out, a.lda, ps.out, a.ldpool, status, st));
     MIMO_TRY(stage_back(ps, prec, st));
   } else {
-    MIMO_TRY(bn_relu_fwd_launch(zs.in, store_type(zprec), a.ldz, as.out, store_type(prec), a.lda, a.scale, a.shift, a.mask, a.c, Cp, P,
-                                a.h * a.w, st, status));
+    MIMO_TRY(bn_relu_fwd_launch(L, a.mask, as.out, a.lda, status, st));
   }
   MIMO_TRY(stage_back(as, prec, st));
   MIMO_HIP_CHECK(hipStreamSynchronize(st));

@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): the counter-based generator torch's
-// CUDA / HIP dropout uses.  One definition for every in-engine draw — the dropout multipliers (elementwise.hip) and the
+// CUDA / HIP dropout uses.  One definition for every in-engine draw — the dropout multipliers (ew_dropout.hip) and the
 // subnetwork permutations (perm_draw.hip) — keyed by the (seed, offset) pair the caller takes from its generator.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // mimo_plan: the MIMO U-Net network executor behind the C ABI.  Owns packed weights, saved
 // activations, BatchNorm statistics and scratch; sequences the HIP kernels of conv3x3.hip /
-// elementwise.hip for forward, loss and backward on the caller's stream.
+// the ew_*.hip operator files for forward, loss and backward on the caller's stream.
 //
 // Topology restated from the reference (relative to /root/reference):
 //   MimoUNet.forward ........... mimo/models/mimo_components/model.py:94-117
@@ -87,6 +87,7 @@ struct ConvBN {
   // varies per call
   ConvLaunch fwd, dgrad;
   WgradLaunch wgrad;
+  BnReluLayer bn = {};  // what the BatchNorm + ReLU passes over z take, forward and backward (elementwise.h): fill_launches too
   int64_t off_w = 0, off_b = 0, off_gamma = 0, off_beta = 0, off_rm = 0, off_rv = 0;
   float *wf = nullptr, *wd = nullptr, *bias_p = nullptr;
   void *wf16 = nullptr, *wd16 = nullptr;  // split-bf16 packed weights (MIMO_PREC_SPLIT16)
@@ -655,6 +656,7 @@ struct mimo_plan {
     L.wgrad.in_scale = L.in_scale;  // (null without fuse_in)
     L.wgrad.in_shift = L.in_shift;
     L.wgrad.partial = s_wslab;
+    L.bn = BnReluLayer{L.z, L.r.dtz, L.cout_p, st, L.scale, L.shift, L.mean, L.invstd, L.Cout, L.cout_p, L.N, L.H, L.W};
   }
 
   // Create a DoubleConv whose input has channel map in_chmap at resolution (h, w).
@@ -1099,11 +1101,9 @@ struct mimo_plan {
     if (!fused && !elide) {
       pr = prof.begin(MIMO_PROF_BN_RELU_FWD, st);
       if (L.pool_out)
-        MIMO_TRY(bn_relu_pool_fwd_launch(L.z, L.r.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, L.N,
-                                         L.H, L.W, L.pool_out, L.pool_ld, st, training ? nullptr : d_status));
+        MIMO_TRY(bn_relu_pool_fwd_launch(L.bn, mask, L.a, L.ld_a, L.pool_out, L.pool_ld, training ? nullptr : d_status, st));
       else
-        MIMO_TRY(bn_relu_fwd_launch(L.z, L.r.dtz, L.cout_p, L.a, this->st, L.ld_a, L.scale, L.shift, mask, L.Cout, L.cout_p, P,
-                                    L.H * L.W, st, training ? nullptr : d_status));
+        MIMO_TRY(bn_relu_fwd_launch(L.bn, mask, L.a, L.ld_a, training ? nullptr : d_status, st));
       prof.end(pr, 0.0, (L.pool_out ? 9.0 : 8.0) * (double)P * L.cout_p, st);
     }
     return MIMO_OK;
@@ -1443,8 +1443,7 @@ struct mimo_plan {
                float* partial, int* rows, hipStream_t st, float* absmax = nullptr, int* absmax_n = nullptr, hipEvent_t done = nullptr) {
     const int64_t P = (int64_t)L.N * L.H * L.W;
     const int pr = prof.begin(MIMO_PROF_BN_BWD_APPLY, st);
-    MIMO_TRY(bn_bwd_apply_launch(src, this->st, L.z, L.r.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd, mask, L.Cout, c1, c2,
-                                 L.cout_p, L.N, L.H, L.W, dz, split_out ? 1 : 0, partial, rows, st, absmax, absmax_n, done));
+    MIMO_TRY(bn_bwd_apply_launch(L.bn, src, mask, BnBwdApplyOut{c1, c2, dz, split_out ? 1 : 0, partial, rows, absmax, absmax_n, done}, st));
     prof.end(pr, 0.0, (8.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     return MIMO_OK;
   }
@@ -1468,8 +1467,7 @@ struct mimo_plan {
     int rows = 0;
     const int64_t P = (int64_t)L.N * L.H * L.W;
     const int pr = prof.begin(MIMO_PROF_BN_BWD_REDUCE, st);
-    MIMO_TRY(bnrelu_bwd_reduce_launch(src, this->st, L.z, L.r.dtz, L.cout_p, L.scale, L.shift, L.mean, L.invstd,
-                                      mask, L.Cout, L.cout_p, L.N, L.H, L.W, s_partial, &rows, st));
+    MIMO_TRY(bnrelu_bwd_reduce_launch(L.bn, src, mask, s_partial, &rows, st));
     prof.end(pr, 0.0, (4.0 + src_bytes(src)) * (double)P * L.cout_p, st);
     if (src.kind == GS_HEAD) head_rows = rows;
     MIMO_TRY(bn_bwd_stats_launch(s_partial, rows, L.Cout, L.cout_p, P, training ? 1 : 0, L.c1, L.c2, grads + L.off_gamma,

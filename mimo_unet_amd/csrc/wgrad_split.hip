@@ -5,7 +5,7 @@
 //   dW[tap][ci][co] = sum_pixels A(pixel + tap, ci) * dz(pixel, co)      (components.py:23,26 autograd)
 //
 // dz arrives PRE-SPLIT from the BatchNorm-backward kernel — per pixel and 32-channel chunk
-// [hi 32 | lo 32] bf16 (elementwise.hip st_split4) — so its staging is a 16-byte copy; the activation operand A is fp32 in
+// [hi 32 | lo 32] bf16 (ew_bn_bwd.hip st_split4) — so its staging is a 16-byte copy; the activation operand A is fp32 in
 // HBM (it also feeds the fp16-pair forward and the bandwidth-class kernels) and is split on the way in.
 //
 // GEMM view: M = input channels, N = output channels, K = pixels (32 per v_mfma_f32_16x16x32_bf16).

@@ -3,6 +3,7 @@
 
     python scripts/kernel_isa_diff.py <tree A> <tree B> <file under mimo_unet_amd/csrc> [...]
     python scripts/kernel_isa_diff.py ../parent . optim.hip evidential_eval.hip optim_clip/grad_clip.hip
+    python scripts/kernel_isa_diff.py <tree A> <tree B> <files of tree A> -- <files of tree B>
 
 Each file is compiled to device assembly in both trees with the Makefile's flags (no GPU needed).  Kernels are matched by
 their unqualified name, so a kernel may move between files and namespaces.  Of each kernel the instruction stream and the
@@ -100,9 +101,12 @@ def main():
     if len(sys.argv) < 4:
         sys.exit(__doc__)
     tree_a, tree_b, files = sys.argv[1], sys.argv[2], sys.argv[3:]
+    files_a = files_b = files
+    if "--" in files:  # the kernels moved between files: one list per tree
+        files_a, files_b = files[:files.index("--")], files[files.index("--") + 1:]
     with tempfile.TemporaryDirectory() as tmpdir:
-        a = compile_tree(tree_a, files, tmpdir, "a")
-        b = compile_tree(tree_b, files, tmpdir, "b")
+        a = compile_tree(tree_a, files_a, tmpdir, "a")
+        b = compile_tree(tree_b, files_b, tmpdir, "b")
     bad = 0
     diffs = []
     print("%-44s %-10s %-22s %-22s %s" % ("kernel", "", "A vgpr/sgpr/lds/scr", "B vgpr/sgpr/lds/scr", "file A -> B"))

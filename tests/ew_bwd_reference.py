@@ -1,4 +1,4 @@
-"""Plain torch references of the backward element-wise operators (mimo_unet_amd/csrc/elementwise.hip: fold_slice, pool_bwd,
+"""Plain torch references of the backward element-wise operators (mimo_unet_amd/csrc/ew_bn_bwd.hip, ew_head_loss.hip: fold_slice, pool_bwd,
 up_bwd, the BatchNorm + ReLU backward chain with its four gradient sources, head_bwd), the input generators of their tests and
 the geometries both test files run: tests/test_ew_bwd_reference_cpu.py proves every function against fp64 autograd through
 the torch modules the model composes, tests/test_ew_bwd_kernels_gpu.py runs the kernels against them.

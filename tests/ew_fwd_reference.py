@@ -1,4 +1,4 @@
-"""Plain torch references of the forward element-wise operators (mimo_unet_amd/csrc/elementwise.hip: the BatchNorm statistics,
+"""Plain torch references of the forward element-wise operators (mimo_unet_amd/csrc/ew_bn_fwd.hip, ew_resample.hip, ew_dropout.hip, ew_head_loss.hip: the BatchNorm statistics,
 BatchNorm + ReLU (+ pooling), max pooling, up-sampling + concat, the 1x1 head, the NLL losses and the layout kernels), the input
 generators of their tests and the geometries both test files run: tests/test_ew_fwd_reference_cpu.py proves every function
 against the torch modules the model composes in fp64, tests/test_ew_fwd_kernels_gpu.py runs the kernels against them.
@@ -109,7 +109,7 @@ def pre_activation(z, scale, shift):
 # ---- bilinear x2 align_corners up-sampling -----------------------------------------------------------------------------------
 
 def lerp_src32(dst, n_in, n_out, clamp_i1=True):
-    """lerp_src of elementwise.hip restated in fp32 (numpy scalars round every operation; scale * dst is a separate, rounded
+    """lerp_src of ew_device.h restated in fp32 (numpy scalars round every operation; scale * dst is a separate, rounded
     product as the kernel pins it): (i0, i1, l0, l1)"""
     one = np.float32(1.0)
     scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0.0)

@@ -1,4 +1,4 @@
-"""fp64 numpy model of `fold_image_grad_mc_kernel` (csrc/elementwise.hip): the transpose of `reflect-pad -> repeat over
+"""fp64 numpy model of `fold_image_grad_mc_kernel` (csrc/ew_layout.hip): the transpose of `reflect-pad -> repeat over
 the passes`, shared by tests/test_mc_adversarial_cpu.py (which checks it against torch autograd) and
 tests/test_mc_adversarial_gpu.py (which checks the kernel against it)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The backward element-wise kernels (elementwise.hip), one operator at a time through mimo_op_fold_slice / _pool_backward /
+"""The backward element-wise kernels (csrc/ew_bn_bwd.hip, ew_head_loss.hip), one operator at a time through mimo_op_fold_slice / _pool_backward /
 _up_backward / _bn_relu_backward / _head_backward, per element against the fp64 references of tests/ew_bwd_reference.py
 (proven against autograd by tests/test_ew_bwd_reference_cpu.py) at the geometries listed there.
 
@@ -80,7 +80,7 @@ def check_elem(kernel, name, got, ref64, y, prec="fp32", floor=None):
     return ratio
 
 
-# ---- summation structure of the kernels (elementwise.hip) ------------------------------------------------------------------
+# ---- summation structure of the kernels (ew_bn_bwd.hip) ------------------------------------------------------------------
 # A per-channel sum is formed as: each thread adds its n_t terms in sequence (pixels p, p + stride, ...); quad_block_sum adds
 # the PPI threads of a workgroup that share a channel quad — in sequence for PPI <= 32, else 16 lanes of PPI / 16 and then those
 # 16; the per-workgroup rows are summed in fp64 (grid_colsum2) and converted to float once.  Every fp32 addition errs by at

@@ -1,4 +1,4 @@
-"""The forward element-wise kernels (elementwise.hip), one operator at a time through mimo_op_bn_stats / _bn_relu_forward /
+"""The forward element-wise kernels (csrc/ew_bn_fwd.hip, ew_resample.hip, ew_dropout.hip, ew_head_loss.hip), one operator at a time through mimo_op_bn_stats / _bn_relu_forward /
 _maxpool2x2_ex / _upsample_cat_ex / _head_forward / _loss_forward / _pack_input / _unpack_dx / _fold_image_grad, against the
 fp64 references of tests/ew_fwd_reference.py (proven against the torch modules by tests/test_ew_fwd_reference_cpu.py).
 
