@@ -447,7 +447,7 @@ int mimo_training_epilogue(const float* out, const float* label, const int64_t* 
  * workspace: device memory of mimo_eval_workspace_bytes() bytes, 16-byte aligned, zeroed by the caller to reset the
  * running sums; the calls that share a workspace must be issued on ONE stream (its partial rows and the record store are
  * ordered by nothing else); records: the caller's device record store, one uint64 per pixel fed so far
- * (low word: bit pattern of combined_std, high word: |error|; 0xFFFFFFFF in the low word marks a skipped pixel). */
+ * (low word: bit pattern of combined_std, high word: |error|; 0xFFFFFFFF in both words marks a skipped pixel). */
 size_t mimo_eval_workspace_bytes(void);
 /* One batch (make_predictions' clip + `[:, 0]`, test_nyuv2_depth.py:73-74,85-89; convert_to_pandas' two square roots,
  * :97-99; `error`, :129; `below = y_true < ppf`, :149,166).  mean / aleatoric_var / epistemic_var / label
@@ -473,6 +473,32 @@ int mimo_eval_select(const uint64_t* records, int64_t num_records, const double*
  * them that survive. */
 int mimo_eval_interval_sums(const uint64_t* records, int64_t num_records, int32_t num_percentiles, int32_t num_thresholds,
                             void* workspace, double* out, mimo_stream stream);
+/* ---- sparsification error (Ilg et al. 2018, Poggi et al. 2020): the same curve per uncertainty source and the oracle
+ * curve (pixels dropped by their own error), from which the host forms AUSE and AURG.
+ * mimo_eval_accumulate with a second store, written at the same slot from the one read of the maps:
+ * source_records: one uint64 per pixel (low word: bit pattern of sqrtf(aleatoric_var), high word: of sqrtf(epistemic_var),
+ * both with -0 canonicalised to +0).  Records, counters and running sums are those of mimo_eval_accumulate, bit for bit.
+ * A skipped pixel has 0xFFFFFFFF in EVERY word of both of its records (written by both entry points), so any of the four
+ * words can serve as a key: the later passes step over a slot whose key is that pattern and never read its error. */
+int mimo_eval_accumulate_sources(const float* mean, const float* aleatoric_var, const float* epistemic_var,
+                                 const float* label, const float* mask, int32_t batch, int32_t channels, int32_t channel,
+                                 int32_t mask_channels, int64_t hw, int32_t clip, float clip_lo, float clip_hi,
+                                 const float* thresholds, int32_t num_thresholds, uint64_t* records,
+                                 uint64_t* source_records, void* workspace, mimo_stream stream);
+/* mimo_eval_select over any key word: record i's key is keys[i * key_stride_words], the bit pattern of a non-negative
+ * float or 0xFFFFFFFF (skipped).  The four orderings: combined = (uint32*)records, aleatoric = (uint32*)source_records,
+ * epistemic = (uint32*)source_records + 1, oracle = (uint32*)records + 1, each with a stride of 2 words.  The workspace must
+ * hold the counters of the accumulate passes that wrote the records; every call resets the select state it uses, so the
+ * orderings run one after another on one workspace and one stream (select, then interval sums, per ordering). */
+int mimo_eval_select_by(const uint32_t* keys, int32_t key_stride_words, int64_t num_records, const double* percentiles,
+                        int32_t num_percentiles, void* workspace, mimo_stream stream);
+/* mimo_eval_interval_sums after mimo_eval_select_by on the same keys; record i's error is errors[i * error_stride_words]
+ * ((uint32*)records + 1, stride 2, in all four orderings).  num_thresholds > 0: out as for mimo_eval_interval_sums;
+ * num_thresholds == 0: out is doubles [3 * num_percentiles] = mae | rmse | threshold key only.  One output buffer of the
+ * caller holds [3 P + K + 6] of the combined ordering followed by one [3 P] slice per further ordering. */
+int mimo_eval_interval_sums_by(const uint32_t* keys, int32_t key_stride_words, const uint32_t* errors,
+                               int32_t error_stride_words, int64_t num_records, int32_t num_percentiles,
+                               int32_t num_thresholds, void* workspace, double* out, mimo_stream stream);
 
 /* ---- single-operator entry points (NHWC, channel-padded) used by the parity tests -------
  * They run the same kernels the plan runs.  x [N,H,W,cin_p], w OIHW [cout][cin][3][3]. */

@@ -1,2 +1,2 @@
-from mimo_unet_amd.evaluation import (UncertaintyEvaluator, cutoff_indices, standard_quantiles,  # noqa: F401
-                                     write_tables_csv)
+from mimo_unet_amd.evaluation import (SOURCES, UncertaintyEvaluator, check_sources, cutoff_indices,  # noqa: F401
+                                     sparsification_areas, standard_quantiles, write_sparsification_csv, write_tables_csv)

@@ -3,18 +3,32 @@
 //
 //   mimo_eval_accumulate    one streaming pass per batch: per pixel 16-20 B in, one 8-byte record (bit pattern of
 //                           combined_std, |error|) out, a 65-bin calibration counter and the running n / sum e / sum e^2
-//   mimo_eval_select        exact simultaneous selection of the <= 128 cutoff ranks over the record store: a count-only
+//   mimo_eval_accumulate_sources  the same pass, which also writes a second 8-byte record per pixel (bit patterns of
+//                           aleatoric_std, epistemic_std) from the one read of the maps: 16 B out instead of 8
+//   mimo_eval_select_by     exact simultaneous selection of the <= 128 cutoff ranks over ANY strided key word: a count-only
 //                           radix select on the key bits, 11 / 11 / 10 bits per pass, integer counters only
-//   mimo_eval_interval_sums one more pass: (count, sum e, sum e^2) of every interval between / on the threshold keys, then
-//                           the suffix sums, the tie rule and the calibration shares into one small output buffer
+//   mimo_eval_interval_sums_by  one more pass: (count, sum e, sum e^2) of every interval between / on the threshold keys,
+//                           then the suffix sums, the tie rule and (on request) the calibration shares into an output slice
+//   mimo_eval_select / mimo_eval_interval_sums  the two above over the record store's own words (key: low, error: high)
+//
+// The four orderings of the sparsification error are four key words: combined = low word of the first record, aleatoric /
+// epistemic = low / high word of the second record, oracle = the first record's error word as its own key.  They run one
+// after another on the one workspace and stream: the select clears its histograms and its per-cutoff state on entry, the
+// interval pass overwrites every partial row it later folds, so a run leaves nothing the next one has to undo.
 //
 // Every sum of floating-point values is formed in a FIXED order (per lane group -> per wave -> per workgroup row -> a
 // tree over the rows): no float atomics, so the same records give the same bits.  Counts use integer atomics (LDS inside
 // a workgroup, device scope where a histogram crosses workgroups), which are order-independent.
 //
-// A skipped pixel (mask == 0, or a non-finite value / negative variance) still owns its record slot: the slot gets the
-// sentinel key 0xFFFFFFFF (a NaN pattern no finite standard deviation has) and the later passes step over it.  The
+// A skipped pixel (mask == 0, or a non-finite value / negative variance) still owns its record slot: EVERY word of its
+// records gets the sentinel 0xFFFFFFFF (a NaN pattern no finite standard deviation or error has), so whichever word serves
+// as the key, the later passes step over the slot; no pass reads the error of a slot whose key is the sentinel.  (The
+// alternative, a separate pointer to the one word that holds the sentinel, costs every ordering a second load.)  The
 // record store therefore needs no cross-workgroup prefix and every store of the hot kernel stays coalesced.
+//
+// Keys are compared as unsigned integers, so a key must be the bit pattern of a non-negative float.  The keys of the
+// second record are canonicalised (-0 -> +0: sqrtf(-0.0f) is -0.0f = 0x80000000, above every finite value, and a variance
+// of -0.0f passes the >= 0 test); the combined key is stored as sqrtf gives it.
 #include "../common.h"
 
 #include <algorithm>
@@ -62,14 +76,15 @@ __device__ __forceinline__ u64 as_u64(double v) { return (u64)__double_as_longlo
 
 // ------------------------------------------------------------------------------------------------ accumulate
 struct PixelOut {
-  u32 key, err;
+  u32 key, err;    // first record: combined_std, |error|
+  u32 akey, ekey;  // second record (mimo_eval_accumulate_sources): aleatoric_std, epistemic_std
 };
 
 // One pixel: clamp, error, the two standard deviations, the calibration bin; what is skipped is only counted.
 __device__ __forceinline__ PixelOut eval_pixel(float mu, float av, float ev, float y, float m, bool has_mask, int clip,
                                                float lo, float hi, const float* __restrict__ zt, int K, u32* __restrict__ bins,
                                                u32& n, u32& n_masked, u32& n_nonfinite, double& se, double& se2) {
-  PixelOut r{kSentinel, 0u};
+  PixelOut r{kSentinel, kSentinel, kSentinel, kSentinel};
   if (has_mask && m == 0.f) {
     ++n_masked;
     return r;
@@ -84,7 +99,8 @@ __device__ __forceinline__ PixelOut eval_pixel(float mu, float av, float ev, flo
     y = fminf(fmaxf(y, lo), hi);
   }
   const float e = fabsf(__fsub_rn(y, mu));
-  const float s = __fmul_rn(sqrtf(av), 0.70710678118654752f);  // scale = aleatoric_std / sqrt(2)
+  const float astd = sqrtf(av);
+  const float s = __fmul_rn(astd, 0.70710678118654752f);  // scale = aleatoric_std / sqrt(2)
   // first threshold j with y < mu + s z_j (monotone in j): lower bound over the table padded to 64 with +inf
   int j = 0;
 #pragma unroll
@@ -101,17 +117,20 @@ __device__ __forceinline__ PixelOut eval_pixel(float mu, float av, float ev, flo
   se2 += (double)e * (double)e;
   r.key = __float_as_uint(sqrtf(var));
   r.err = __float_as_uint(e);
+  r.akey = __float_as_uint(astd) & 0x7FFFFFFFu;  // -0 -> +0
+  r.ekey = __float_as_uint(sqrtf(ev)) & 0x7FFFFFFFu;
   return r;
 }
 
 // VEC: hw % 4 == 0 and every pointer 16-byte aligned -> one float4 of pixels per thread per step; otherwise the same
-// walk with scalar loads and a bounds test per pixel (the last quad of an image may be partial).
-template <bool VEC>
+// walk with scalar loads and a bounds test per pixel (the last quad of an image may be partial).  SRC: the second record
+// goes to srec at the same slot (rec_vec then covers both stores).
+template <bool VEC, bool SRC>
 __global__ __launch_bounds__(256) void eval_accumulate_kernel(
     const float* __restrict__ mean, const float* __restrict__ avar, const float* __restrict__ evar,
     const float* __restrict__ label, const float* __restrict__ mask, int B, int C, int channel, int MC, int64_t hw,
-    int clip, float lo, float hi, const float* __restrict__ z, int K, uint2* __restrict__ rec, int rec_vec,
-    u64* __restrict__ part) {
+    int clip, float lo, float hi, const float* __restrict__ z, int K, uint2* __restrict__ rec, uint2* __restrict__ srec,
+    int rec_vec, u64* __restrict__ part) {
   __shared__ float zt[kMaxK + 1];
   __shared__ u32 bins[4][kBins + 3];
   __shared__ double red[2][256];
@@ -155,10 +174,18 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(
       uint4* d = (uint4*)(rec + dst);
       d[0] = make_uint4(o[0].key, o[0].err, o[1].key, o[1].err);
       d[1] = make_uint4(o[2].key, o[2].err, o[3].key, o[3].err);
+      if (SRC) {
+        uint4* sd = (uint4*)(srec + dst);
+        sd[0] = make_uint4(o[0].akey, o[0].ekey, o[1].akey, o[1].ekey);
+        sd[1] = make_uint4(o[2].akey, o[2].ekey, o[3].akey, o[3].ekey);
+      }
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (k < cnt) rec[dst + k] = make_uint2(o[k].key, o[k].err);
+        if (k < cnt) {
+          rec[dst + k] = make_uint2(o[k].key, o[k].err);
+          if (SRC) srec[dst + k] = make_uint2(o[k].akey, o[k].ekey);
+        }
     }
   }
   // one partial row per workgroup: counts as integers, sums in double, a fixed-order tree
@@ -266,8 +293,11 @@ __global__ void eval_select_init_kernel(const u64* __restrict__ acc, const doubl
 
 // LEVEL 1: every record by its top 11 bits (LDS histogram, flushed with one device-scope add per non-empty bin).
 // LEVEL 2 / 3: only records whose upper 11 / 22 bits are in the table the previous level left, by their next 11 / 10 bits.
-template <int LEVEL>
-__global__ __launch_bounds__(256) void eval_hist_kernel(const uint2* __restrict__ rec, int64_t total, int P, Workspace* ws) {
+// Record i's key is keys[i * stride].  WORD 0 / 1: the key is that word of an 8-byte record in a 16-byte aligned store
+// `keys` (stride 2): two records per 16-byte load.  WORD < 0: any stride, scalar loads.
+template <int LEVEL, int WORD>
+__global__ __launch_bounds__(256) void eval_hist_kernel(const u32* __restrict__ keys, int stride, int64_t total, int P,
+                                                        Workspace* ws) {
   __shared__ u32 sh[LEVEL == 1 ? kL1 : kMaxP];
   const int tid = threadIdx.x;
   if (LEVEL == 1) {
@@ -279,12 +309,19 @@ __global__ __launch_bounds__(256) void eval_hist_kernel(const uint2* __restrict_
   const int64_t pairs = (total + 1) >> 1;
   for (int64_t q = (int64_t)blockIdx.x * 256 + tid; q < pairs; q += (int64_t)gridDim.x * 256) {
     u32 key[2] = {kSentinel, kSentinel};
-    if (2 * q + 1 < total) {
-      const uint4 v = *(const uint4*)(rec + 2 * q);
-      key[0] = v.x;
-      key[1] = v.z;
+    if (WORD >= 0) {
+      const uint2* rec = (const uint2*)keys;
+      if (2 * q + 1 < total) {
+        const uint4 v = *(const uint4*)(rec + 2 * q);
+        key[0] = WORD ? v.y : v.x;
+        key[1] = WORD ? v.w : v.z;
+      } else {
+        const uint2 v = rec[2 * q];
+        key[0] = WORD ? v.y : v.x;
+      }
     } else {
-      key[0] = rec[2 * q].x;
+      key[0] = keys[2 * q * stride];
+      if (2 * q + 1 < total) key[1] = keys[(2 * q + 1) * stride];
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -398,7 +435,10 @@ __global__ void eval_sort_kernel(int P, Workspace* ws) {
 // (one readfirstlane + ballot per distinct interval), every lane sums its group's errors in lane order from an LDS
 // staging row, and the group's first lane adds the result to the wave's PRIVATE slot row: plain read-modify-write on
 // distinct addresses, a fixed order of additions, no float atomic.
-__global__ __launch_bounds__(256) void eval_interval_kernel(const uint2* __restrict__ rec, int64_t total, int P, Workspace* ws) {
+// Record i: key keys[i * kstride], error errors[i * estride].  REC: the two are the words of one 8-byte record at `keys`.
+template <bool REC>
+__global__ __launch_bounds__(256) void eval_interval_kernel(const u32* __restrict__ keys, int kstride, const u32* __restrict__ errors,
+                                                            int estride, int64_t total, int P, Workspace* ws) {
   __shared__ u32 tab[kMaxP];
   __shared__ float stage[4][64];
   __shared__ double sse[4][kSlots], sse2[4][kSlots];
@@ -417,7 +457,13 @@ __global__ __launch_bounds__(256) void eval_interval_kernel(const uint2* __restr
     int slot = -1;
     float e = 0.f;
     if (i < total) {
-      const uint2 r = rec[i];
+      uint2 r;
+      if (REC) {
+        r = ((const uint2*)keys)[i];
+      } else {
+        r.x = keys[i * kstride];
+        r.y = r.x != kSentinel ? errors[i * estride] : 0u;
+      }
       if (r.x != kSentinel) {
         const int lb = lower_bound_u32(tab, P, r.x);
         slot = 2 * lb + ((lb < P && tab[lb] == r.x) ? 1 : 0);
@@ -484,7 +530,7 @@ __global__ void eval_interval_fold_kernel(int rows, Workspace* ws) {
   if (lane == 0) ws->isum[k][s] = k == 0 ? a : as_u64(d);
 }
 
-// out (doubles): [0,P) mae | [P,2P) rmse | [2P,3P) threshold value of combined_std | [3P,3P+K) observed share |
+// out (doubles): [0,P) mae | [P,2P) rmse | [2P,3P) threshold value of the key | and, when K > 0, [3P,3P+K) observed share |
 //                n, n_masked, n_nonfinite, mae, mse, rmse of the whole set
 __global__ void eval_tables_kernel(int P, int K, Workspace* ws, double* __restrict__ out) {
   __shared__ double cse[kSlots + 1], cse2[kSlots + 1];
@@ -523,7 +569,7 @@ __global__ void eval_tables_kernel(int P, int K, Workspace* ws, double* __restri
     out[P + c] = rmse;
     out[2 * P + c] = keyv;
   }
-  if (c == 0) {
+  if (c == 0 && K > 0) {
     const u64 n = ws->acc[65];
     u64 run = 0;
     for (int k = 0; k < K; ++k) {
@@ -546,84 +592,136 @@ __global__ void eval_tables_kernel(int P, int K, Workspace* ws, double* __restri
 
 extern "C" size_t mimo_eval_workspace_bytes(void) { return sizeof(mimo::eval::Workspace); }
 
-extern "C" int mimo_eval_accumulate(const float* mean, const float* aleatoric_var, const float* epistemic_var,
-                                    const float* label, const float* mask, int32_t batch, int32_t channels, int32_t channel,
-                                    int32_t mask_channels, int64_t hw, int32_t clip, float clip_lo, float clip_hi,
-                                    const float* thresholds, int32_t num_thresholds, uint64_t* records, void* workspace,
-                                    mimo_stream stream) {
+// the accumulate pass of both entry points; source_records == nullptr: the first record only
+static int eval_accumulate(const char* what, const float* mean, const float* aleatoric_var, const float* epistemic_var,
+                           const float* label, const float* mask, int32_t batch, int32_t channels, int32_t channel,
+                           int32_t mask_channels, int64_t hw, int32_t clip, float clip_lo, float clip_hi, const float* thresholds,
+                           int32_t num_thresholds, uint64_t* records, uint64_t* source_records, void* workspace,
+                           mimo_stream stream) {
   using namespace mimo;
   using namespace mimo::eval;
   if (!mean || !aleatoric_var || !epistemic_var || !label || !thresholds || !records || !workspace || batch < 1 ||
       channels < 1 || channel < 0 || channel >= channels || hw < 1 || num_thresholds < 1 || num_thresholds > kMaxK ||
-      (mask && mask_channels != 1 && mask_channels != channels) || ((uintptr_t)records & 7) || ((uintptr_t)workspace & 15)) {
-    set_error("mimo_eval_accumulate: invalid argument");
+      (mask && mask_channels != 1 && mask_channels != channels) || ((uintptr_t)records & 7) ||
+      ((uintptr_t)source_records & 7) || ((uintptr_t)workspace & 15)) {
+    set_error("%s: invalid argument", what);
     return MIMO_ERR_INVALID;
   }
   Workspace* ws = (Workspace*)workspace;
   const uintptr_t al = (uintptr_t)mean | (uintptr_t)aleatoric_var | (uintptr_t)epistemic_var | (uintptr_t)label | (uintptr_t)mask;
   const bool vec = (hw % 4 == 0) && (al & 15) == 0;
-  const int rec_vec = ((uintptr_t)records & 15) == 0;
+  const int rec_vec = (((uintptr_t)records | (uintptr_t)source_records) & 15) == 0;
   const int64_t quads = (int64_t)batch * ((hw + 3) / 4);
   const int blocks = (int)std::min<int64_t>(ceil_div64(quads, 256), kAccBlocks);
   const int mc = mask ? mask_channels : 1;
-  if (vec)
-    hipLaunchKernelGGL(eval_accumulate_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mean, aleatoric_var,
-                       epistemic_var, label, mask, batch, channels, channel, mc, hw, clip, clip_lo, clip_hi, thresholds,
-                       num_thresholds, (uint2*)records, rec_vec, &ws->part[0][0]);
-  else
-    hipLaunchKernelGGL(eval_accumulate_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mean, aleatoric_var,
-                       epistemic_var, label, mask, batch, channels, channel, mc, hw, clip, clip_lo, clip_hi, thresholds,
-                       num_thresholds, (uint2*)records, rec_vec, &ws->part[0][0]);
+  auto kernel = source_records ? (vec ? eval_accumulate_kernel<true, true> : eval_accumulate_kernel<false, true>)
+                               : (vec ? eval_accumulate_kernel<true, false> : eval_accumulate_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mean, aleatoric_var, epistemic_var, label, mask,
+                     batch, channels, channel, mc, hw, clip, clip_lo, clip_hi, thresholds, num_thresholds, (uint2*)records,
+                     (uint2*)source_records, rec_vec, &ws->part[0][0]);
   MIMO_KERNEL_CHECK();
   hipLaunchKernelGGL(eval_fold_kernel, dim3(70), dim3(256), 0, (hipStream_t)stream, &ws->part[0][0], blocks, ws->acc);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
 
-extern "C" int mimo_eval_select(const uint64_t* records, int64_t num_records, const double* percentiles,
-                                int32_t num_percentiles, void* workspace, mimo_stream stream) {
+extern "C" int mimo_eval_accumulate(const float* mean, const float* aleatoric_var, const float* epistemic_var,
+                                    const float* label, const float* mask, int32_t batch, int32_t channels, int32_t channel,
+                                    int32_t mask_channels, int64_t hw, int32_t clip, float clip_lo, float clip_hi,
+                                    const float* thresholds, int32_t num_thresholds, uint64_t* records, void* workspace,
+                                    mimo_stream stream) {
+  return eval_accumulate("mimo_eval_accumulate", mean, aleatoric_var, epistemic_var, label, mask, batch, channels, channel,
+                         mask_channels, hw, clip, clip_lo, clip_hi, thresholds, num_thresholds, records, nullptr, workspace, stream);
+}
+
+extern "C" int mimo_eval_accumulate_sources(const float* mean, const float* aleatoric_var, const float* epistemic_var,
+                                            const float* label, const float* mask, int32_t batch, int32_t channels,
+                                            int32_t channel, int32_t mask_channels, int64_t hw, int32_t clip, float clip_lo,
+                                            float clip_hi, const float* thresholds, int32_t num_thresholds, uint64_t* records,
+                                            uint64_t* source_records, void* workspace, mimo_stream stream) {
+  if (!source_records) {
+    mimo::set_error("mimo_eval_accumulate_sources: invalid argument");
+    return MIMO_ERR_INVALID;
+  }
+  return eval_accumulate("mimo_eval_accumulate_sources", mean, aleatoric_var, epistemic_var, label, mask, batch, channels, channel,
+                         mask_channels, hw, clip, clip_lo, clip_hi, thresholds, num_thresholds, records, source_records, workspace,
+                         stream);
+}
+
+extern "C" int mimo_eval_select_by(const uint32_t* keys, int32_t key_stride_words, int64_t num_records,
+                                   const double* percentiles, int32_t num_percentiles, void* workspace, mimo_stream stream) {
   using namespace mimo;
   using namespace mimo::eval;
-  if (!records || !percentiles || !workspace || num_records < 1 || num_percentiles < 1 || num_percentiles > kMaxP ||
-      num_records >= ((int64_t)1 << 32) || ((uintptr_t)records & 15) || ((uintptr_t)workspace & 15)) {  // the histogram counters are 32-bit
-    set_error("mimo_eval_select: invalid argument");
+  if (!keys || key_stride_words < 1 || !percentiles || !workspace || num_records < 1 || num_percentiles < 1 ||
+      num_percentiles > kMaxP || num_records >= ((int64_t)1 << 32) || ((uintptr_t)keys & 3) || ((uintptr_t)workspace & 15)) {  // the histogram counters are 32-bit
+    set_error("mimo_eval_select_by: invalid argument");
     return MIMO_ERR_INVALID;
   }
   Workspace* ws = (Workspace*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  const uint2* rec = (const uint2*)records;
-  const int P = num_percentiles;
+  const int P = num_percentiles, stride = key_stride_words;
+  // a word of an 8-byte record in a 16-byte aligned store: the kernels load whole record pairs from the store's base
+  const int word = (int)(((uintptr_t)keys >> 2) & 1);
+  const bool pair = stride == 2 && (((uintptr_t)keys - 4 * word) & 15) == 0;
+  const u32* base = pair ? keys - word : keys;
   const int blocks = (int)std::min<int64_t>(ceil_div64((num_records + 1) / 2, 256), kHistBlocks);
+  auto hist1 = !pair ? eval_hist_kernel<1, -1> : word ? eval_hist_kernel<1, 1> : eval_hist_kernel<1, 0>;
+  auto hist2 = !pair ? eval_hist_kernel<2, -1> : word ? eval_hist_kernel<2, 1> : eval_hist_kernel<2, 0>;
+  auto hist3 = !pair ? eval_hist_kernel<3, -1> : word ? eval_hist_kernel<3, 1> : eval_hist_kernel<3, 0>;
   MIMO_HIP_CHECK(hipMemsetAsync(ws->hist1, 0, sizeof(ws->hist1) + sizeof(ws->hist2) + sizeof(ws->hist3), s));
   hipLaunchKernelGGL(eval_select_init_kernel, dim3(1), dim3(kMaxP), 0, s, ws->acc, percentiles, P, ws);
-  hipLaunchKernelGGL(eval_hist_kernel<1>, dim3(blocks), dim3(256), 0, s, rec, num_records, P, ws);
+  hipLaunchKernelGGL(hist1, dim3(blocks), dim3(256), 0, s, base, stride, num_records, P, ws);
   hipLaunchKernelGGL(eval_resolve_kernel<1>, dim3(1), dim3(256), 0, s, P, ws);
   hipLaunchKernelGGL(eval_sort_kernel, dim3(1), dim3(kMaxP), 0, s, P, ws);
-  hipLaunchKernelGGL(eval_hist_kernel<2>, dim3(blocks), dim3(256), 0, s, rec, num_records, P, ws);
+  hipLaunchKernelGGL(hist2, dim3(blocks), dim3(256), 0, s, base, stride, num_records, P, ws);
   hipLaunchKernelGGL(eval_resolve_kernel<2>, dim3(P), dim3(256), 0, s, P, ws);
   hipLaunchKernelGGL(eval_sort_kernel, dim3(1), dim3(kMaxP), 0, s, P, ws);
-  hipLaunchKernelGGL(eval_hist_kernel<3>, dim3(blocks), dim3(256), 0, s, rec, num_records, P, ws);
+  hipLaunchKernelGGL(hist3, dim3(blocks), dim3(256), 0, s, base, stride, num_records, P, ws);
   hipLaunchKernelGGL(eval_resolve_kernel<3>, dim3(P), dim3(256), 0, s, P, ws);
   hipLaunchKernelGGL(eval_sort_kernel, dim3(1), dim3(kMaxP), 0, s, P, ws);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
 
-extern "C" int mimo_eval_interval_sums(const uint64_t* records, int64_t num_records, int32_t num_percentiles,
-                                       int32_t num_thresholds, void* workspace, double* out, mimo_stream stream) {
+extern "C" int mimo_eval_interval_sums_by(const uint32_t* keys, int32_t key_stride_words, const uint32_t* errors,
+                                          int32_t error_stride_words, int64_t num_records, int32_t num_percentiles,
+                                          int32_t num_thresholds, void* workspace, double* out, mimo_stream stream) {
   using namespace mimo;
   using namespace mimo::eval;
-  if (!records || !workspace || !out || num_records < 1 || num_percentiles < 1 || num_percentiles > kMaxP ||
-      num_thresholds < 1 || num_thresholds > kMaxK || num_records >= ((int64_t)1 << 32) || ((uintptr_t)workspace & 15)) {
-    set_error("mimo_eval_interval_sums: invalid argument");
+  if (!keys || key_stride_words < 1 || !errors || error_stride_words < 1 || !workspace || !out || num_records < 1 ||
+      num_percentiles < 1 || num_percentiles > kMaxP || num_thresholds < 0 || num_thresholds > kMaxK ||
+      num_records >= ((int64_t)1 << 32) || (((uintptr_t)keys | (uintptr_t)errors) & 3) || ((uintptr_t)workspace & 15)) {
+    set_error("mimo_eval_interval_sums_by: invalid argument");
     return MIMO_ERR_INVALID;
   }
   Workspace* ws = (Workspace*)workspace;
   hipStream_t s = (hipStream_t)stream;
   const int blocks = (int)std::min<int64_t>(ceil_div64(num_records, 256), kIntBlocks);
-  hipLaunchKernelGGL(eval_interval_kernel, dim3(blocks), dim3(256), 0, s, (const uint2*)records, num_records, num_percentiles, ws);
+  const bool rec = key_stride_words == 2 && error_stride_words == 2 && errors == keys + 1 && ((uintptr_t)keys & 7) == 0;
+  hipLaunchKernelGGL(rec ? eval_interval_kernel<true> : eval_interval_kernel<false>, dim3(blocks), dim3(256), 0, s, keys,
+                     key_stride_words, errors, error_stride_words, num_records, num_percentiles, ws);
   hipLaunchKernelGGL(eval_interval_fold_kernel, dim3(kSlots, 3), dim3(64), 0, s, blocks, ws);
   hipLaunchKernelGGL(eval_tables_kernel, dim3(1), dim3(kMaxP), 0, s, num_percentiles, num_thresholds, ws, out);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }
+
+extern "C" int mimo_eval_select(const uint64_t* records, int64_t num_records, const double* percentiles,
+                                int32_t num_percentiles, void* workspace, mimo_stream stream) {
+  if (!records || ((uintptr_t)records & 15)) {
+    mimo::set_error("mimo_eval_select: invalid argument");
+    return MIMO_ERR_INVALID;
+  }
+  return mimo_eval_select_by((const uint32_t*)records, 2, num_records, percentiles, num_percentiles, workspace, stream);
+}
+
+extern "C" int mimo_eval_interval_sums(const uint64_t* records, int64_t num_records, int32_t num_percentiles,
+                                       int32_t num_thresholds, void* workspace, double* out, mimo_stream stream) {
+  if (!records || ((uintptr_t)records & 7) || num_thresholds < 1) {
+    mimo::set_error("mimo_eval_interval_sums: invalid argument");
+    return MIMO_ERR_INVALID;
+  }
+  return mimo_eval_interval_sums_by((const uint32_t*)records, 2, (const uint32_t*)records + 1, 2, num_records, num_percentiles,
+                                    num_thresholds, workspace, out, stream);
+}
+

@@ -12,6 +12,11 @@ one small buffer to the host.  No pandas, no scipy, no CPU path.
     for batch in loader:
         ev.update_from(ensemble, batch["image"].cuda(), batch["label"].cuda())
     ev.write_csv(result_dir)
+
+Opt-in, `sources=("combined", "aleatoric", "epistemic")`: the same sparsification curve per uncertainty source and the
+oracle curve (pixels dropped by their own error), and their areas AUSE / AURG (`sparsification_areas`).  The pass then
+writes a second 8-byte record per pixel (`mimo_eval_accumulate_sources`) and `compute()` runs the selection once per
+ordering over the word that holds its key (`mimo_eval_select_by`, `mimo_eval_interval_sums_by`), still ending in one copy.
 """
 from __future__ import annotations
 
@@ -28,6 +33,8 @@ MAX_PERCENTILES = 128  # eval_stats.hip: kMaxP
 MAX_THRESHOLDS = 64    # eval_stats.hip: kMaxK
 PRECISION_RECALL_HEADER = ("percentile", "mae", "rmse")       # test_nyuv2_depth.py:142
 CALIBRATION_HEADER = ("Expected Conf.", "Observed Conf.")     # test_nyuv2_depth.py:169
+# orderings of the sparsification curve -> (store, word) that holds the key; store 0 = records, 1 = source records
+SOURCES = {"combined": (0, 0), "aleatoric": (1, 0), "epistemic": (1, 1), "oracle": (0, 1)}
 
 _NDTRI_P0 = (-5.99633501014107895267E1, 9.80010754185999661536E1, -5.66762857469070293439E1, 1.39312609387279679503E1,
              -1.23916583867381258016E0)
@@ -86,6 +93,61 @@ def write_tables_csv(tables: dict, directory: str) -> Tuple[str, str]:
     return paths
 
 
+def check_sources(sources) -> Tuple[str, ...]:
+    """The requested orderings, in the order given, without repeats; an unknown name raises ValueError."""
+    names = (sources,) if isinstance(sources, str) else tuple(sources)
+    for name in names:
+        if name not in SOURCES:
+            raise ValueError(f"unknown uncertainty source {name!r}: choose from {tuple(SOURCES)}")
+    return tuple(dict.fromkeys(names))
+
+
+def sparsification_areas(percentiles, curve, oracle, normalize: bool = False) -> Tuple[float, float]:
+    """(AUSE, AURG) of one sparsification curve: float64, trapezoid rule on the grid `percentiles` (the share of pixels
+    dropped), over the rows where both curves are finite (a row that drops every pixel is NaN); NaN with fewer than two.
+
+        AUSE = integral of (curve - oracle)      area of the sparsification error: 0 for an uncertainty that ranks the
+                                                 pixels as their errors do
+        AURG = integral of (curve[0] - curve)    gain over random removal, whose expected curve is the constant whole-set
+                                                 value, i.e. row 0 (nothing dropped)
+
+    so that AUSE + AURG = integral of (curve[0] - oracle), the most any ordering can gain.  `normalize=False` (the default)
+    integrates the curves in the unit of the metric, as Poggi et al. 2020 ("On the uncertainty of self-supervised monocular
+    depth estimation") report AUSE and AURG; `normalize=True` divides both curves by row 0 first, as Ilg et al. 2018
+    ("Uncertainty estimates and multi-hypotheses networks for optical flow") do, whose curves start at 1."""
+    x = np.asarray(percentiles, dtype=np.float64)
+    c, o = np.asarray(curve, dtype=np.float64), np.asarray(oracle, dtype=np.float64)
+    if not (x.shape == c.shape == o.shape and x.ndim == 1):
+        raise ValueError("percentiles, curve and oracle must be one-dimensional and of one length")
+    ok = np.isfinite(c) & np.isfinite(o)
+    if ok.sum() < 2:
+        return float("nan"), float("nan")
+    x, c, o = x[ok], c[ok], o[ok]
+    if normalize:
+        c, o = c / c[0], o / o[0]
+    w = np.diff(x)
+    area = lambda y: float(np.sum(0.5 * (y[1:] + y[:-1]) * w))
+    return area(c - o), area(c[0] - c)
+
+
+def write_sparsification_csv(tables: dict, directory: str) -> Tuple[str, str]:
+    """`sparsification.csv` (percentile, then mae_<source> and rmse_<source> per source) and `ause.csv` (one row per
+    source) of tables computed with extra sources."""
+    os.makedirs(directory, exist_ok=True)
+    sp, names = tables["sparsification"], list(tables["sparsification"])
+    paths = (os.path.join(directory, "sparsification.csv"), os.path.join(directory, "ause.csv"))
+    with open(paths[0], "w") as f:
+        f.write(",".join(["percentile"] + [f"{m}_{s}" for s in names for m in ("mae", "rmse")]) + "\n")
+        for i, q in enumerate(tables["precision_recall"]["percentile"]):
+            f.write(",".join(repr(float(v)) for v in [q] + [sp[s][m][i] for s in names for m in ("mae", "rmse")]) + "\n")
+    with open(paths[1], "w") as f:
+        f.write("source,ause_mae,ause_rmse,aurg_mae,aurg_rmse\n")
+        for s in names:
+            row = [tables[a][s][m] for a in ("ause", "aurg") for m in ("mae", "rmse")]
+            f.write(s + "," + ",".join(repr(float(v)) for v in row) + "\n")
+    return paths
+
+
 class UncertaintyEvaluator:
     """Streaming reducer of `(mean, aleatoric_var, epistemic_var, label)` batches into the reference's two tables.
 
@@ -96,7 +158,13 @@ class UncertaintyEvaluator:
 
     def __init__(self, expected_p: Optional[Sequence[float]] = None, percentiles: Optional[Sequence[float]] = None,
                  distribution: str = "norm", clip: Optional[Tuple[float, float]] = (0.0, 1.0), channel: int = 0,
-                 device=None):
+                 device=None, sources: Sequence[str] = ("combined",)):
+        self.sources = check_sources(sources)
+        # the orderings compute() runs: combined first (the reference's table), the oracle last, and only with extra sources
+        extra = self.sources != ("combined",)
+        self._orderings = ("combined",) + tuple(s for s in self.sources if s not in ("combined", "oracle")) + (("oracle",) if extra else ())
+        self._reported = (self.sources + (() if "oracle" in self.sources else ("oracle",))) if extra else ()
+        self._two_stores = any(SOURCES[s][0] == 1 for s in self._orderings)
         self.expected_p = np.arange(41) / 40.0 if expected_p is None else np.asarray(expected_p, dtype=np.float64)
         self.percentiles = np.arange(100) / 100.0 if percentiles is None else np.asarray(percentiles, dtype=np.float64)
         if not 1 <= self.expected_p.size <= MAX_THRESHOLDS or not 1 <= self.percentiles.size <= MAX_PERCENTILES:
@@ -115,9 +183,11 @@ class UncertaintyEvaluator:
             self._z_dev = torch.from_numpy(self.z.astype(np.float32)).to(self.device)
             self._pct_dev = torch.from_numpy(np.ascontiguousarray(self.percentiles)).to(self.device)
             self._ws = torch.zeros(int(self._lib.mimo_eval_workspace_bytes()) // 8 + 1, dtype=torch.int64, device=self.device)
-            self._out = torch.empty(3 * self.percentiles.size + self.expected_p.size + 6, dtype=torch.float64,
-                                    device=self.device)
+            # [3 P + K + 6] of the combined ordering, then one [3 P] slice (mae | rmse | key) per further ordering
+            self._out = torch.empty(3 * self.percentiles.size * len(self._orderings) + self.expected_p.size + 6,
+                                    dtype=torch.float64, device=self.device)
         self._records = None  # int64 [capacity]: one record per pixel fed
+        self._source_records = None  # the second record per pixel (aleatoric_std, epistemic_std), only when asked for
         self._used = 0
 
     # ------------------------------------------------------------------ feeding
@@ -130,10 +200,11 @@ class UncertaintyEvaluator:
         cap = 0 if self._records is None else self._records.numel()
         if need <= cap:
             return
-        grown = torch.empty(max(need, 2 * cap, 1 << 20), dtype=torch.int64, device=self.device)
-        if self._used:
-            grown[: self._used].copy_(self._records[: self._used])  # device to device, on the current stream
-        self._records = grown
+        for store in ("_records", "_source_records")[: 2 if self._two_stores else 1]:
+            grown = torch.empty(max(need, 2 * cap, 1 << 20), dtype=torch.int64, device=self.device)
+            if self._used:
+                grown[: self._used].copy_(getattr(self, store)[: self._used])  # device to device, on the current stream
+            setattr(self, store, grown)
 
     def update(self, mean, aleatoric_var, epistemic_var, label, mask=None) -> None:
         """Device tensors [B,C,H,W] (mask [B,1,H,W] or [B,C,H,W]).  Enqueues one pass; returns without synchronising."""
@@ -159,10 +230,17 @@ class UncertaintyEvaluator:
         with torch.cuda.device(self.device):
             self._reserve(b * hw)
             lo, hi = self.clip if self.clip is not None else (0.0, 0.0)
-            L.check(self._lib.mimo_eval_accumulate(
-                ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(), L.ptr(mask) or None, b, c,
-                self.channel, mc, hw, int(self.clip is not None), lo, hi, self._z_dev.data_ptr(), self.z.size,
-                self._records.data_ptr() + 8 * self._used, self._ws.data_ptr(), L.current_stream()), "mimo_eval_accumulate")
+            if self._two_stores:
+                L.check(self._lib.mimo_eval_accumulate_sources(
+                    ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(), L.ptr(mask) or None, b, c,
+                    self.channel, mc, hw, int(self.clip is not None), lo, hi, self._z_dev.data_ptr(), self.z.size,
+                    self._records.data_ptr() + 8 * self._used, self._source_records.data_ptr() + 8 * self._used,
+                    self._ws.data_ptr(), L.current_stream()), "mimo_eval_accumulate_sources")
+            else:
+                L.check(self._lib.mimo_eval_accumulate(
+                    ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(), L.ptr(mask) or None, b, c,
+                    self.channel, mc, hw, int(self.clip is not None), lo, hi, self._z_dev.data_ptr(), self.z.size,
+                    self._records.data_ptr() + 8 * self._used, self._ws.data_ptr(), L.current_stream()), "mimo_eval_accumulate")
         self._used += b * hw
 
     def update_from(self, ensemble, image, label, mask=None) -> None:
@@ -186,7 +264,7 @@ class UncertaintyEvaluator:
     def compute(self) -> dict:
         p, k = self.percentiles.size, self.expected_p.size
         if self._used == 0:
-            o = np.full(3 * p + k + 6, np.nan)
+            o = np.full(self._out.numel(), np.nan)
             o[3 * p + k: 3 * p + k + 3] = 0.0
         else:
             with torch.cuda.device(self.device):
@@ -195,18 +273,41 @@ class UncertaintyEvaluator:
                                                    self._ws.data_ptr(), s), "mimo_eval_select")
                 L.check(self._lib.mimo_eval_interval_sums(self._records.data_ptr(), self._used, p, k, self._ws.data_ptr(),
                                                           self._out.data_ptr(), s), "mimo_eval_interval_sums")
+                stores = (self._records, self._source_records)
+                errors = self._records.data_ptr() + 4
+                for j, name in enumerate(self._orderings[1:]):  # one after another on the one workspace and stream
+                    store, word = SOURCES[name]
+                    keys = stores[store].data_ptr() + 4 * word
+                    L.check(self._lib.mimo_eval_select_by(keys, 2, self._used, self._pct_dev.data_ptr(), p, self._ws.data_ptr(), s),
+                            "mimo_eval_select_by")
+                    L.check(self._lib.mimo_eval_interval_sums_by(
+                        keys, 2, errors, 2, self._used, p, 0, self._ws.data_ptr(),
+                        self._out.data_ptr() + 8 * (3 * p * (j + 1) + k + 6), s), "mimo_eval_interval_sums_by")
                 o = self._out.cpu().numpy()  # the one transfer (and the one synchronisation)
         n, n_masked, n_nonfinite = (int(v) for v in o[3 * p + k: 3 * p + k + 3])
         if n_nonfinite:
             warnings.warn(f"UncertaintyEvaluator: {n_nonfinite} pixels with a non-finite value or a negative variance were "
                           "skipped (the reference's tables would be NaN in every row)", RuntimeWarning, stacklevel=2)
-        return {
+        tables = {
             "precision_recall": {"percentile": self.percentiles.copy(), "mae": o[:p].copy(), "rmse": o[p: 2 * p].copy()},
             "calibration": {"expected": self.expected_p.copy(), "observed": o[3 * p: 3 * p + k].copy()},
             "cutoff_keys": o[2 * p: 3 * p].copy(),
             "n": n, "n_masked": n_masked, "n_nonfinite": n_nonfinite,
             "mae": float(o[3 * p + k + 3]), "mse": float(o[3 * p + k + 4]), "rmse": float(o[3 * p + k + 5]),
         }
+        if self._reported:
+            base = {name: 0 if j == 0 else 3 * p * j + k + 6 for j, name in enumerate(self._orderings)}
+            sp = {name: {"mae": o[base[name]: base[name] + p].copy(), "rmse": o[base[name] + p: base[name] + 2 * p].copy(),
+                         "cutoff_keys": o[base[name] + 2 * p: base[name] + 3 * p].copy()} for name in self._reported}
+            areas = {name: {m: sparsification_areas(self.percentiles, sp[name][m], sp["oracle"][m]) for m in ("mae", "rmse")}
+                     for name in self._reported}
+            tables["sparsification"] = sp
+            tables["ause"] = {name: {m: areas[name][m][0] for m in ("mae", "rmse")} for name in self._reported}
+            tables["aurg"] = {name: {m: areas[name][m][1] for m in ("mae", "rmse")} for name in self._reported}
+        return tables
 
-    def write_csv(self, directory: str, tables: Optional[dict] = None) -> Tuple[str, str]:
-        return write_tables_csv(self.compute() if tables is None else tables, directory)
+    def write_csv(self, directory: str, tables: Optional[dict] = None) -> Tuple[str, ...]:
+        """The reference's two files; with extra sources also `sparsification.csv` and `ause.csv`."""
+        tables = self.compute() if tables is None else tables
+        paths = write_tables_csv(tables, directory)
+        return paths + write_sparsification_csv(tables, directory) if "sparsification" in tables else paths

@@ -7,6 +7,9 @@ of the host route (the same tables from `.cpu()` copies: numpy argsort + 41 quan
     python scripts/evaluate_uncertainty.py --model_checkpoint_paths a.ckpt b.ckpt --batch_dir batches/ --result_dir out
     python scripts/evaluate_uncertainty.py --evidential --synthetic 2 --result_dir out   # a seeded EvidentialUnetModel
     python scripts/evaluate_uncertainty.py --evidential --model_checkpoint_paths ev.ckpt --batch_dir batches/ --result_dir out
+    python scripts/evaluate_uncertainty.py --synthetic 8 --sources combined aleatoric epistemic --result_dir out
+
+--sources: the sparsification curve per uncertainty source and the oracle curve (sparsification.csv), AUSE / AURG (ause.csv).
 
 --evidential: ONE `EvidentialUnetModel` (one checkpoint, or a seeded network) fed through `predict_uncertainties`, as the
 reference's scripts/test/test_nyuv2_depth_evidential.py / test_ndvi_evidential.py drive the model itself.
@@ -68,6 +71,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--distribution", default="norm", choices=["norm", "laplace"])
+    ap.add_argument("--sources", nargs="+", default=["combined"], choices=["combined", "aleatoric", "epistemic", "oracle"],
+                    help="orderings of the sparsification curve; any beyond 'combined' adds the oracle, AUSE and AURG")
     ap.add_argument("--result_dir", required=True)
     ap.add_argument("--no_host_route", action="store_true")
     args = ap.parse_args()
@@ -100,7 +105,7 @@ def main():
         ensemble = EnsembleModule(args.model_checkpoint_paths, monte_carlo_steps=args.monte_carlo_steps, models=models,
                                   keep_on_device=True).to(dev)
 
-    ev = UncertaintyEvaluator(distribution=args.distribution)
+    ev = UncertaintyEvaluator(distribution=args.distribution, sources=args.sources)
     kept, update_ms, masked = [], [], False
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -153,10 +158,13 @@ def main():
            "rmse": tables["rmse"]}
     if update_ms:
         # HIP events around one update(): the accumulate pass AND its 70-workgroup fold launch.  Bytes of the pass: four
-        # fp32 maps in (five with a mask), one 8-byte record out.
+        # fp32 maps in (five with a mask), one 8-byte record out (two with aleatoric / epistemic among the sources).
+        records = 16 if {"aleatoric", "epistemic"} & set(args.sources) else 8
         res.update(update_ms_median=float(np.median(update_ms)), update_ms_min=float(np.min(update_ms)),
-                   bytes_per_pixel=28 if masked else 24)
+                   bytes_per_pixel=(20 if masked else 16) + records)
         res["update_GBps_at_min"] = res["bytes_per_pixel"] * pixels / (res["update_ms_min"] * 1e-3) / 1e9
+    if "ause" in tables:
+        res.update(ause=tables["ause"], aurg=tables["aurg"])
     if kept:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
