@@ -283,6 +283,28 @@ int mimo_input_gradient_mc(mimo_plan* plan, const float* dout, const float* dlos
 int mimo_fgsm_perturb(const float* image, const float* dimage, int64_t elems, const float* eps, int K, float lo, float hi,
                       float* out, mimo_stream stream);
 
+/* ---- PGD (BIM without the random start): the iterated, projected form of the attack above; no reference counterpart.
+ * One step for all K perturbation sizes of a sweep in one launch.  x0 [elems] is the clean image; grad and x_adv are
+ * [K][elems], the gradient taken at each size's current iterate.  x_adv is updated in place:
+ *   v = x_adv[k][i] + alpha[k] * sign(grad[k][i])           (sign as above: sign(0) = 0, a NaN gradient gives NaN)
+ *   v = clamp(v, x0[i] - eps[k], x0[i] + eps[k])            (the eps-ball first; each bound is one fp32 rounding)
+ *   x_adv[k][i] = clamp(v, lo, hi)                          (then the value range; both clamps pass a NaN)
+ * eps[k] = 0 gives clamp(x0, lo, hi) for every non-NaN gradient.  eps, alpha: HOST arrays [K], by value into the launch in
+ * slices of 16.  4 + 8 K B read and 4 K B written per element.  MIMO_ERR_INVALID: a null pointer, elems < 1, K < 1, lo > hi,
+ * a negative or NaN eps or alpha.  Asynchronous on the stream; no atomics. */
+int mimo_pgd_step(const float* x0, const float* grad, float* x_adv, int64_t elems, const float* eps, const float* alpha, int K,
+                  float lo, float hi, mimo_stream stream);
+
+/* ---- the random start of PGD for all K sizes from ONE draw: x_adv[k][i] = clamp(x0[i] + eps[k] * r[i], lo, hi), sum and
+ * product rounded separately (never fused), r[i] the same for every k.  Quad q = elements 4 q .. 4 q + 3 takes the four
+ * words of philox4x32_10(ctr = (lo32(q), hi32(q), lo32(offset) ^ 0xFF000000, hi32(offset)), key = seed), element 4 q + j
+ * word j, and r = (2 (w >> 8) + 1 - 2^24) * 2^-24: exact in fp32, symmetric in (-1, 1).  Counter word 2 carries the site
+ * number 255 in the dropout draws' layout (rng_offset above; sites are < 56) and differs from the permutation draw's
+ * (offset_lo as it is): the three never share a counter within one (seed, offset) block.  (seed, offset): the caller's
+ * generator, which it advances by one counter block (4).  eps: HOST array [K]; MIMO_ERR_INVALID as for the step. */
+int mimo_pgd_init(const float* x0, int64_t elems, const float* eps, int K, float lo, float hi, uint64_t seed, uint64_t offset,
+                  float* x_adv, mimo_stream stream);
+
 /* ---- measurement (no reference counterpart): per-kernel-class device time from HIP events
  * recorded on the launch stream around every 3x3 convolution launch, with the ALGORITHMIC
  * flops (2*9*Cin*Cout*N*H*W, logical channels) and bytes ((Cin+Cout)*N*H*W*4) of those

@@ -164,6 +164,8 @@ _SIGNATURES = {
     "mimo_input_gradient": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "mimo_input_gradient_mc": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "mimo_fgsm_perturb": (C.c_int, [_P, _P, _L, C.POINTER(_F), C.c_int, _F, _F, _P, _P]),
+    "mimo_pgd_step": (C.c_int, [_P, _P, _P, _L, C.POINTER(_F), C.POINTER(_F), C.c_int, _F, _F, _P]),
+    "mimo_pgd_init": (C.c_int, [_P, _L, C.POINTER(_F), C.c_int, _F, _F, C.c_uint64, C.c_uint64, _P, _P]),
     "mimo_plan_num_backward_stages": (C.c_int, [_P]),
     "mimo_plan_backward_stage_range": (C.c_int, [_P, C.c_int, C.POINTER(_L), C.POINTER(_L)]),
     "mimo_plan_profile": (C.c_int, [_P, C.c_int]),

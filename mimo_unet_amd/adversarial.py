@@ -46,6 +46,11 @@ no bit parity to be held to.  The gradient GIVEN the masks is deterministic, and
 
 Still refused: an `EvidentialUnetModel` with active dropout (the reference's evidential scripts have no MC mode), and the
 precisions other than fp32 / split16.
+
+`pgd_sweep` is the iterated, projected form of the same attack (PGD; BIM without its random start), which the reference does
+not have: per step one `image_gradient` call on the perturbation levels stacked on the batch axis and one `mimo_pgd_step`
+launch for all of them (csrc/pgd.hip), an optional random start from the engine's generator (`mimo_pgd_init`), then the same
+predictions.  `RobustnessEvaluator(attack="pgd")` routes through it; the defaults run `fgsm_sweep` as before.
 """
 from __future__ import annotations
 
@@ -171,36 +176,149 @@ def fgsm_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Seq
     dimage = image_gradient(ensemble, image, label, mask, mc_dropout=mc_dropout)
     lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
     perturbed = fgsm_perturb(image.detach(), dimage, eps, lo, hi)
+    return _predict_levels(ensemble, [(e, perturbed[k]) for k, e in enumerate(eps)], return_perturbed)
+
+
+def _predict_levels(ensemble, levels, return_perturbed: bool) -> Dict[float, tuple]:
+    """The tail of a sweep: levels = [(eps, perturbed image)] -> {eps: (mean, aleatoric_var, epistemic_var[, perturbed])}"""
     if _is_evidential(ensemble):
         out = {}
-        for k, e in enumerate(eps):
-            res = ensemble.predict_uncertainties(perturbed[k])
-            out[e] = res + (perturbed[k],) if return_perturbed else res
+        for e, x in levels:
+            res = ensemble.predict_uncertainties(x)
+            out[e] = res + (x,) if return_perturbed else res
         return out
     keep, raw = ensemble.keep_on_device, ensemble.return_raw_predictions
     ensemble.keep_on_device, ensemble.return_raw_predictions = True, False
     out = {}
     try:
-        for k, e in enumerate(eps):
-            res = tuple(ensemble(perturbed[k]))
-            out[e] = res + (perturbed[k],) if return_perturbed else res
+        for e, x in levels:
+            res = tuple(ensemble(x))
+            out[e] = res + (x,) if return_perturbed else res
     finally:
         ensemble.keep_on_device, ensemble.return_raw_predictions = keep, raw
     return out
 
 
+def _validate_pgd(steps, step_size, rel_step_size) -> Tuple[int, Optional[float], float]:
+    if isinstance(steps, bool) or int(steps) != steps or steps < 1:
+        raise ValueError(f"pgd_sweep: steps must be an integer >= 1, got {steps!r}")
+    if step_size is not None and not float(step_size) >= 0.0:
+        raise ValueError(f"pgd_sweep: step_size must be None or a non-negative number, got {step_size!r}")
+    if not float(rel_step_size) > 0.0:
+        raise ValueError(f"pgd_sweep: rel_step_size must be positive, got {rel_step_size!r}")
+    return int(steps), None if step_size is None else float(step_size), float(rel_step_size)
+
+
+def pgd_step_sizes(eps: Sequence[float], steps: int, step_size: Optional[float], rel_step_size: float) -> Tuple[float, ...]:
+    """alpha_k: `step_size` for every level if it is given, else rel_step_size * eps_k / steps in Python floats (cast to fp32
+    once, where the launch takes them)."""
+    return tuple(float(step_size) if step_size is not None else rel_step_size * e / steps for e in eps)
+
+
+def pgd_level_chunks(levels: int, batch: int, limit: int, mc_dropout: bool = False):
+    """[(k0, k1)]: the eps > 0 levels [k0, k1) of each gradient launch — max(1, limit // batch) levels stacked on the batch
+    axis, one level with mc_dropout=True (the passes already fill the launch)."""
+    chunk = 1 if mc_dropout else max(1, int(limit) // max(int(batch), 1))
+    return [(k0, min(levels, k0 + chunk)) for k0 in range(0, levels, chunk)]
+
+
+def _samples_per_launch(ensemble) -> int:
+    if _is_evidential(ensemble):  # the bare model has no such attribute: EnsembleModule's default
+        return max(1, int(os.environ.get("MIMO_MC_CHUNK_SAMPLES", "64")))
+    return int(ensemble.max_samples_per_launch)
+
+
+def _clamp_compare(x: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+    """clamp in the kernels' compare form (a NaN and the sign of a zero pass), once per sweep"""
+    if lo == float("-inf") and hi == float("inf"):
+        return x
+    return torch.where(x < lo, torch.full_like(x, lo), torch.where(x > hi, torch.full_like(x, hi), x))
+
+
+def pgd_sweep(ensemble, image: torch.Tensor, label: torch.Tensor, epsilons: Sequence[float] = DEFAULT_EPSILONS, steps: int = 10,
+              step_size: Optional[float] = None, rel_step_size: float = 2.5, random_start: bool = False,
+              mask: Optional[torch.Tensor] = None, clip: Optional[Tuple[float, float]] = (0.0, 1.0),
+              return_perturbed: bool = False, mc_dropout: bool = False) -> Dict[float, tuple]:
+    """`fgsm_sweep`'s dict for the iterated, projected sign-gradient attack (PGD; BIM with random_start=False): per level
+    eps_k, `steps` times
+
+        x_adv_k = clamp(clamp(x_adv_k + alpha_k * sign(d loss / d image at x_adv_k), image - eps_k, image + eps_k), *clip)
+
+    Same model kinds, refusals and untouched members as `fgsm_sweep`; no reference counterpart (its only attack is FGSM).
+    alpha_k: `step_size`, or rel_step_size * eps_k / steps.  Start: clamp(image, *clip); with random_start=True
+    clamp(image + eps_k * r, *clip), r uniform in (-1, 1) from the engine's generator (`engine.pgd_init`: one draw shared by
+    the levels, keyed by torch's CUDA generator of the image's device, whose offset advances by 4 — `torch.cuda.manual_seed`
+    replays a sweep).
+    Per step the levels with eps > 0 are stacked on the batch axis, in the order given, in chunks of
+    max(1, limit // B) levels (limit = `ensemble.max_samples_per_launch`; for a bare evidential model its default,
+    MIMO_MC_CHUNK_SAMPLES or 64): ONE `image_gradient` call per chunk on [Kc * B, C, H, W] — label and mask are repeated once
+    per sweep — and one `mimo_pgd_step` launch per chunk.  The stacked loss is a mean over the Kc * B samples, so each level's
+    gradient carries a factor 1 / Kc: a positive factor changes no sign, and only the sign is used.  With mc_dropout=True a
+    chunk holds one level (the passes already fill the launch) and every step draws fresh masks from the engine's generator:
+    the attack ascends an expectation over masks.  Levels with eps = 0 take no gradient: they stay at their start.
+    Afterwards every level is predicted exactly as in `fgsm_sweep`."""
+    eps = _validate(ensemble, epsilons, mc_dropout)
+    steps, step_size, rel_step_size = _validate_pgd(steps, step_size, rel_step_size)
+    if not image.is_cuda:
+        from . import _lib as L
+        raise L.MimoHipError("pgd_sweep runs on an AMD GPU through libmimo_hip.so; move the ensemble and its inputs to cuda")
+    from .engine import pgd_init, pgd_step
+    lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
+    x0 = image.detach().contiguous().float()
+    b = x0.shape[0]
+    # attacked levels first, in the order given, so that every chunk is one contiguous [Kc * B, C, H, W] block of x_adv
+    order = [k for k, e in enumerate(eps) if e > 0.0] + [k for k, e in enumerate(eps) if e == 0.0]
+    kp = sum(1 for e in eps if e > 0.0)
+    eps_o = [eps[k] for k in order]
+    alpha_o = pgd_step_sizes(eps_o, steps, step_size, rel_step_size)
+    with torch.no_grad():
+        if random_start:
+            index = x0.device.index if x0.device.index is not None else torch.cuda.current_device()
+            gen = torch.cuda.default_generators[index]
+            seed, offset = gen.initial_seed(), gen.get_offset()
+            x_adv = pgd_init(x0, eps_o, lo, hi, seed, offset)
+            gen.set_offset(offset + 4)  # after the launch, one counter block, as `_engine_permutations` does
+        else:
+            x_adv = _clamp_compare(x0, lo, hi).unsqueeze(0).repeat(len(eps), *([1] * x0.dim()))
+        chunks = pgd_level_chunks(kp, b, _samples_per_launch(ensemble), mc_dropout)
+        if chunks:
+            most = max(k1 - k0 for k0, k1 in chunks)
+            label_r = label.detach().to(x0.device).repeat(most, *([1] * (label.dim() - 1)))
+            mask_r = None if mask is None else mask.detach().to(x0.device).repeat(most, *([1] * (mask.dim() - 1)))
+        for _ in range(steps):
+            for k0, k1 in chunks:
+                n = (k1 - k0) * b
+                stacked = x_adv[k0:k1].view(n, *x0.shape[1:])
+                grad = image_gradient(ensemble, stacked, label_r[:n], None if mask_r is None else mask_r[:n], mc_dropout=mc_dropout)
+                pgd_step(x0, grad.view(k1 - k0, *x0.shape), x_adv[k0:k1], eps_o[k0:k1], alpha_o[k0:k1], lo, hi)
+    perturbed = {eps[k]: x_adv[j] for j, k in enumerate(order)}
+    return _predict_levels(ensemble, [(e, perturbed[e]) for e in eps], return_perturbed)
+
+
+ATTACKS = ("fgsm", "pgd")
+
+
 class RobustnessEvaluator:
     """One `UncertaintyEvaluator` per noise level, fed by `fgsm_sweep`: the sparsification and calibration tables of
     test_nyuv2_depth.py:215-234 for every eps of its sweep (:192).  `evaluator_kwargs` go to every UncertaintyEvaluator.
-    mc_dropout: handed to `fgsm_sweep` (MC-dropout ensembles)."""
+    mc_dropout: handed to `fgsm_sweep` (MC-dropout ensembles).
+    attack="pgd": fed by `pgd_sweep(steps, step_size, rel_step_size, random_start)` instead; the default "fgsm" ignores the four."""
 
-    def __init__(self, epsilons: Sequence[float] = DEFAULT_EPSILONS, mc_dropout: bool = False, **evaluator_kwargs):
+    def __init__(self, epsilons: Sequence[float] = DEFAULT_EPSILONS, mc_dropout: bool = False, attack: str = "fgsm",
+                 steps: int = 10, step_size: Optional[float] = None, rel_step_size: float = 2.5, random_start: bool = False,
+                 **evaluator_kwargs):
         self.epsilons = tuple(float(e) for e in epsilons)
         self.mc_dropout = bool(mc_dropout)
         if not self.epsilons or any(not e >= 0.0 for e in self.epsilons):
             raise NotImplementedError(f"RobustnessEvaluator: epsilons must be non-negative, got {self.epsilons}")
         if len(set(self.epsilons)) != len(self.epsilons):
             raise ValueError(f"RobustnessEvaluator: duplicate epsilons {self.epsilons}")
+        if attack not in ATTACKS:
+            raise ValueError(f"RobustnessEvaluator: unknown attack {attack!r}, one of {ATTACKS}")
+        self.attack = attack
+        self.steps, self.step_size, self.rel_step_size = ((steps, step_size, rel_step_size) if attack == "fgsm" else
+                                                          _validate_pgd(steps, step_size, rel_step_size))
+        self.random_start = bool(random_start)
         self.evaluators = {e: UncertaintyEvaluator(**evaluator_kwargs) for e in self.epsilons}
 
     def reset(self) -> None:
@@ -208,7 +326,12 @@ class RobustnessEvaluator:
             ev.reset()
 
     def update_from(self, ensemble, image, label, mask=None) -> None:
-        sweep = fgsm_sweep(ensemble, image, label, self.epsilons, mask=mask, mc_dropout=self.mc_dropout)
+        if self.attack == "pgd":
+            sweep = pgd_sweep(ensemble, image, label, self.epsilons, steps=self.steps, step_size=self.step_size,
+                              rel_step_size=self.rel_step_size, random_start=self.random_start, mask=mask,
+                              mc_dropout=self.mc_dropout)
+        else:
+            sweep = fgsm_sweep(ensemble, image, label, self.epsilons, mask=mask, mc_dropout=self.mc_dropout)
         for e, (mean, av, ev) in sweep.items():
             self.evaluators[e].update(mean, av, ev, label.to(mean.device), None if mask is None else mask.to(mean.device))
 

@@ -369,6 +369,41 @@ def fgsm_perturb(image: torch.Tensor, dimage: torch.Tensor, epsilons: Sequence[f
     return out
 
 
+def _pgd_sizes(values: Sequence[float]):
+    return (C.c_float * len(values))(*[float(v) for v in values])
+
+
+def pgd_step(x0: torch.Tensor, grad: torch.Tensor, x_adv: torch.Tensor, eps: Sequence[float], alpha: Sequence[float],
+             lo: float = 0.0, hi: float = 1.0) -> torch.Tensor:
+    """One projected sign-gradient step for all K perturbation sizes in one launch (mimo_pgd_step), IN PLACE on `x_adv`:
+    x_adv[k] = clamp(clamp(x_adv[k] + alpha_k * sign(grad[k]), x0 - eps_k, x0 + eps_k), lo, hi).  x0 [*shape]; grad and x_adv
+    [K, *shape], fp32 and contiguous (nothing is copied: the update has to land in the caller's tensor).  Returns `x_adv`."""
+    lib = L.load()
+    k = len(eps)
+    assert len(alpha) == k and k >= 1
+    for t in (x0, grad, x_adv):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert grad.shape == x_adv.shape == (k,) + tuple(x0.shape)
+    with torch.cuda.device(x0.device):
+        L.check(lib.mimo_pgd_step(x0.data_ptr(), grad.data_ptr(), x_adv.data_ptr(), x0.numel(), _pgd_sizes(eps), _pgd_sizes(alpha),
+                                  k, float(lo), float(hi), L.current_stream()), "mimo_pgd_step")
+    return x_adv
+
+
+def pgd_init(x0: torch.Tensor, eps: Sequence[float], lo: float, hi: float, seed: int, offset: int) -> torch.Tensor:
+    """[K, *x0.shape] = clamp(x0 + eps_k * r, lo, hi): the random start of PGD for all K sizes from one Philox draw keyed by
+    (seed, offset), r uniform on a symmetric grid in (-1, 1) and shared by the sizes (mimo_pgd_init, include/mimo_hip.h)."""
+    lib = L.load()
+    assert x0.is_cuda
+    x0 = x0.contiguous().float()
+    k = len(eps)
+    out = torch.empty((k,) + tuple(x0.shape), device=x0.device, dtype=torch.float32)
+    with torch.cuda.device(x0.device):
+        L.check(lib.mimo_pgd_init(x0.data_ptr(), x0.numel(), _pgd_sizes(eps), k, float(lo), float(hi), int(seed) & (2 ** 64 - 1),
+                                  int(offset) & (2 ** 64 - 1), out.data_ptr(), L.current_stream()), "mimo_pgd_init")
+    return out
+
+
 def draw_permutations(batch: int, reps: int, k: int, s: int, seed: int, offset: int, device, want_main: bool = False):
     """[s, batch * reps] int64 gather indices of apply_input_transform (the reference's mimo/models/utils.py:27-36) drawn by
     one launch from the Philox stream keyed by (seed, offset) — mimo_draw_permutations, include/mimo_hip.h: a main

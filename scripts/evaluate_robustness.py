@@ -9,6 +9,11 @@ loss, `x.grad`, the torch expression of the attack, then the ensemble forward.
     python scripts/evaluate_robustness.py --evidential --synthetic 4 --compare --result_dir out   # a bare EvidentialUnetModel
     python scripts/evaluate_robustness.py --evidential --model_checkpoint_paths ev.ckpt --batch_dir batches/ --result_dir out
     python scripts/evaluate_robustness.py --synthetic 8 --monte_carlo_steps 8 --compare --result_dir out   # MC-dropout ensemble
+    python scripts/evaluate_robustness.py --synthetic 4 --attack pgd --pgd_steps 10 --result_dir out       # PGD instead of FGSM
+
+--attack pgd: the iterated, projected attack (`pgd_sweep`) with --pgd_steps steps of --pgd_step_size (default 2.5 * eps / steps)
+and, with --pgd_random_start, a random start from the engine's generator; the tables and their file names are the same.  The
+older route is the FGSM one, so --compare is not offered with it (scripts/measure_pgd.py times PGD against its torch form).
 
 --monte_carlo_steps N (the reference's flag): an MC-dropout ensemble of N passes per member, attacked through
 `fgsm_sweep(..., mc_dropout=True)` — one gradient over the N masked passes, then the MC forward per eps.  The synthetic member
@@ -35,7 +40,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mimo.adversarial import RobustnessEvaluator, fgsm_sweep  # noqa: E402
+from mimo.adversarial import RobustnessEvaluator, fgsm_sweep, pgd_sweep  # noqa: E402
 
 
 def older_route(ensemble, image, label, epsilons, mask=None):
@@ -115,12 +120,18 @@ def main():
     ap.add_argument("--monte_carlo_steps", type=int, default=0, metavar="N",
                     help="MC-dropout ensemble of N passes per member (fgsm_sweep(mc_dropout=True))")
     ap.add_argument("--compare", action="store_true", help="also time the autograd route, in alternating pairs")
+    ap.add_argument("--attack", choices=("fgsm", "pgd"), default="fgsm")
+    ap.add_argument("--pgd_steps", type=int, default=10)
+    ap.add_argument("--pgd_step_size", type=float, default=None, help="default: 2.5 * eps / pgd_steps per level")
+    ap.add_argument("--pgd_random_start", action="store_true")
     ap.add_argument("--result_dir", required=True)
     args = ap.parse_args()
     mc = args.monte_carlo_steps
     if mc < 0 or (mc > 0 and args.evidential):
         ap.error("--monte_carlo_steps: a positive number of passes, and not with --evidential (the reference's evidential "
                  "scripts have no MC mode)")
+    if args.attack == "pgd" and args.compare:
+        ap.error("--compare times the FGSM autograd route: not with --attack pgd")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     from mimo.models.ensemble import EnsembleModule
@@ -176,6 +187,10 @@ def main():
 
     first = {k: torch.as_tensor(batches[0][k]).to(dev) for k in ("image", "label")}
     sweep = fgsm_sweep if mc == 0 else (lambda *a, **k: fgsm_sweep(*a, mc_dropout=True, **k))
+    if args.attack == "pgd":
+        def sweep(*a, **k):
+            return pgd_sweep(*a, steps=args.pgd_steps, step_size=args.pgd_step_size, random_start=args.pgd_random_start,
+                             mc_dropout=mc > 0, **k)
     sweep(ensemble, first["image"], first["label"], eps)  # first calls: plans, code load
     if args.compare:
         older(ensemble, first["image"], first["label"], eps)
@@ -209,6 +224,8 @@ def main():
     out = {"model": "evidential" if args.evidential else "ensemble", "epsilons": list(eps), "batches": len(batches), "pixels_per_batch": int(batches[0]["image"].shape[0]) * args.size * args.size
            if not args.batch_dir else None, "sweep_ms_median": float(np.median(new_ms)), "sweep_ms_min": float(np.min(new_ms)),
            "mae_per_eps": {str(e): tables[e]["mae"] for e in eps}}
+    if args.attack == "pgd":
+        out.update(attack="pgd", pgd_steps=args.pgd_steps, pgd_step_size=args.pgd_step_size, pgd_random_start=args.pgd_random_start)
     if mc > 0:
         # what one launch of fold_image_grad_mc_kernel moves: R * 4 * Ci_p read, 4 * Ci written (+ 4 * Ci read when accumulating)
         # per pixel of the B images, at the chunk the gradient runs in
