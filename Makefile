@@ -3,7 +3,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := mimo_unet_amd/csrc
-SRCS := $(CSRC)/conv3x3.hip $(CSRC)/conv_thin.hip $(CSRC)/conv_bf16x3.hip $(CSRC)/conv_wide.hip $(CSRC)/wgrad_split.hip $(CSRC)/ew_reduce.hip $(CSRC)/ew_layout.hip $(CSRC)/ew_bn_fwd.hip $(CSRC)/ew_resample.hip $(CSRC)/ew_dropout.hip $(CSRC)/ew_bn_bwd.hip $(CSRC)/ew_head_loss.hip $(CSRC)/perm_draw.hip $(CSRC)/fgsm.hip $(CSRC)/pgd.hip $(CSRC)/monitor.hip $(CSRC)/evidential_eval.hip $(CSRC)/optim.hip $(CSRC)/plan.hip $(CSRC)/ops_api.hip $(CSRC)/eval/eval_stats.hip $(CSRC)/optim_clip/grad_clip.hip $(CSRC)/data/dataset_gather.hip $(CSRC)/scene/scene_tiles.hip
+SRCS := $(CSRC)/conv3x3.hip $(CSRC)/conv_thin.hip $(CSRC)/conv_bf16x3.hip $(CSRC)/conv_wide.hip $(CSRC)/wgrad_split.hip $(CSRC)/ew_reduce.hip $(CSRC)/ew_layout.hip $(CSRC)/ew_bn_fwd.hip $(CSRC)/ew_resample.hip $(CSRC)/ew_dropout.hip $(CSRC)/ew_bn_bwd.hip $(CSRC)/ew_head_loss.hip $(CSRC)/perm_draw.hip $(CSRC)/fgsm.hip $(CSRC)/pgd.hip $(CSRC)/monitor.hip $(CSRC)/evidential_eval.hip $(CSRC)/optim.hip $(CSRC)/plan.hip $(CSRC)/ops_api.hip $(CSRC)/eval/eval_stats.hip $(CSRC)/eval/score_rules.hip $(CSRC)/optim_clip/grad_clip.hip $(CSRC)/data/dataset_gather.hip $(CSRC)/scene/scene_tiles.hip
 OBJS := $(SRCS:.hip=.o)
 LIB := mimo_unet_amd/libmimo_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function

@@ -522,6 +522,31 @@ int mimo_eval_interval_sums_by(const uint32_t* keys, int32_t key_stride_words, c
                                int32_t error_stride_words, int64_t num_records, int32_t num_percentiles,
                                int32_t num_thresholds, void* workspace, double* out, mimo_stream stream);
 
+/* ---- proper scoring rules of the ensemble's mixture predictive: per pixel the equal-weight mixture of the `members`
+ * densities an EnsembleModule leaves in HBM (return_raw_predictions) is scored at the label by its probability integral
+ * transform (PIT), its negative log-likelihood (natural log, the full density) and its CRPS, in one pass.  Member scale
+ * as the loss trains it: theta = clamp(exp(p2), eps_min, eps_max), Laplace b = theta, Gaussian sigma^2 = theta; means and
+ * labels are not clipped.  Asynchronous on the stream; no allocation, no synchronisation.
+ * workspace: device memory of mimo_score_workspace_bytes() bytes, 16-byte aligned, zeroed by the caller to reset; the
+ * calls that share it must be issued on one stream. */
+size_t mimo_score_workspace_bytes(void);
+/* p1 / p2 [batch,members,channels,hw] fp32 contiguous and label [batch,channels,hw], of which plane `channel` is used;
+ * mask [batch,mask_channels,hw] (mask_channels 1 or channels) or NULL.  A pixel with mask == 0 is skipped and counted in
+ * n_masked; otherwise one whose label or any member's p1 / p2 is not finite is skipped and counted in n_nonfinite.
+ * expected_p: device [num_thresholds <= 64] ascending fp32 thresholds of the PIT histogram: a pixel goes to the first bin k
+ * with PIT < expected_p[k], to bin num_thresholds when there is none.  pit_map / nll_map / crps_map: [batch,hw] each or
+ * NULL; a skipped pixel gets NaN.  The counters do not depend on which maps are requested; the same sequence of calls gives
+ * the same bits (double sums in a fixed order, integer counts).  MIMO_ERR_INVALID with nothing launched: members outside
+ * 1 ... 64, num_thresholds outside 1 ... 64, an unknown loss_kind, eps_min <= 0 or eps_max < eps_min or not finite, a
+ * null p1 / p2 / label / expected_p / workspace, a pointer that is not 4-byte aligned. */
+int mimo_score_accumulate(const float* p1, const float* p2, const float* label, const float* mask, int32_t batch,
+                          int32_t members, int32_t channels, int32_t channel, int32_t mask_channels, int64_t hw,
+                          int32_t loss_kind, float eps_min, float eps_max, const float* expected_p, int32_t num_thresholds,
+                          float* pit_map, float* nll_map, float* crps_map, void* workspace, mimo_stream stream);
+/* out: device doubles [num_thresholds + 6] = the share of scored pixels with PIT < expected_p[k] per threshold, then n,
+ * n_masked, n_nonfinite, mean NLL, mean CRPS, mean PIT (the shares and the means are NaN at n == 0). */
+int mimo_score_finalize(const void* workspace, int32_t num_thresholds, double* out, mimo_stream stream);
+
 /* ---- single-operator entry points (NHWC, channel-padded) used by the parity tests -------
  * They run the same kernels the plan runs.  x [N,H,W,cin_p], w OIHW [cout][cin][3][3]. */
 int mimo_op_conv3x3_forward(const float* x, const float* w, const float* bias, float* z, double* stats,

@@ -311,3 +311,183 @@ class UncertaintyEvaluator:
         tables = self.compute() if tables is None else tables
         paths = write_tables_csv(tables, directory)
         return paths + write_sparsification_csv(tables, directory) if "sparsification" in tables else paths
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Proper scoring rules of the mixture predictive (score_rules.hip)
+
+MAX_MEMBERS = 64            # score_rules.hip: kMaxS
+REGISTER_MEMBERS = 4        # score_rules.hip: kRegS — up to here the pair loop runs from registers, beyond from an LDS tile
+SCORE_MAX_WORKGROUPS = 1024  # score_rules.hip: kBlocks — a launch's grid; each workgroup strides over the rest
+SCORES_HEADER = ("n", "n_masked", "n_nonfinite", "nll", "crps", "pit_mean", "calibration_error")
+
+
+def check_expected_p(expected_p) -> np.ndarray:
+    """The thresholds of a calibration table as float64: 1..64 values, ascending, within [0, 1] (the rule of
+    `UncertaintyEvaluator`); the default is `arange(41) / 40`."""
+    p = np.arange(41) / 40.0 if expected_p is None else np.asarray(expected_p, dtype=np.float64).reshape(-1)
+    if not 1 <= p.size <= MAX_THRESHOLDS:
+        raise ValueError(f"1..{MAX_THRESHOLDS} expected confidences")
+    if np.any(np.diff(p) < 0) or not (p.min() >= 0 and p.max() <= 1):
+        raise ValueError("expected_p must be ascending within [0, 1]")
+    return p
+
+
+def check_score_shapes(p1, p2, label, mask, channel: int) -> Tuple[int, int, int, int, int, int]:
+    """(B, S, C, H, W, mask_channels) of one `PredictiveScorer.update`, or ValueError: p1 / p2 [B,S,C,H,W], label
+    [B,C,H,W], mask None, [B,1,H,W] or [B,C,H,W], 1 <= S <= 64, 0 <= channel < C."""
+    if p1.dim() != 5:
+        raise ValueError("update expects p1 and p2 of shape [B,S,C,H,W]")
+    b, s, c, h, w = p1.shape
+    if tuple(p2.shape) != (b, s, c, h, w):
+        raise ValueError(f"p2 has shape {tuple(p2.shape)}, expected {(b, s, c, h, w)}")
+    if tuple(label.shape) != (b, c, h, w):
+        raise ValueError(f"label has shape {tuple(label.shape)}, expected {(b, c, h, w)}")
+    if not 1 <= s <= MAX_MEMBERS:
+        raise ValueError(f"{s} members: the mixture is scored for 1..{MAX_MEMBERS}")
+    if not 0 <= channel < c:
+        raise ValueError(f"channel {channel} of {c}")
+    mc = 1
+    if mask is not None:
+        if mask.dim() != 4 or mask.shape[0] != b or mask.shape[1] not in (1, c) or tuple(mask.shape[2:]) != (h, w):
+            raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(b, 1, h, w)} or {(b, c, h, w)}")
+        mc = int(mask.shape[1])
+    return b, s, c, h, w, mc
+
+
+def mixture_of(ensemble) -> Tuple[str, float, float, int]:
+    """(loss, eps_min, eps_max, S_total) of the mixture an `EnsembleModule` predicts: S_total = passes x the subnetworks of
+    every checkpoint.  A bare `EvidentialUnetModel` raises NotImplementedError (its Student-t predictive needs an
+    incomplete-beta CDF); S_total > 64 raises ValueError."""
+    from .models.evidential_unet import EvidentialUnetModel
+    if isinstance(ensemble, EvidentialUnetModel):
+        raise NotImplementedError("PredictiveScorer: the evidential model's Student-t predictive is not scored "
+                                  "(its CDF is an incomplete beta function)")
+    loss_fn = ensemble.loss_fn
+    loss = getattr(loss_fn, "name", "")
+    if loss not in L.LOSS_KINDS:
+        raise NotImplementedError(f"PredictiveScorer: no mixture density for the loss {type(loss_fn).__name__}")
+    s_total = max(1, int(ensemble.monte_carlo_steps)) * int(ensemble.num_subnetworks)
+    if s_total > MAX_MEMBERS:
+        raise ValueError(f"S_total = {s_total} members: the mixture is scored for at most {MAX_MEMBERS}")
+    return loss, float(loss_fn.eps_min), float(loss_fn.eps_max), s_total
+
+
+def coverage_table(expected_p, observed) -> dict:
+    """{level: share} of the central intervals a threshold table holds: every index pair (k, K-1-k) with k < K-1-k and
+    |p_k + p_{K-1-k} - 1| <= 1e-12; level = p_{K-1-k} - p_k, share = observed_{K-1-k} - observed_k."""
+    p, o = np.asarray(expected_p, dtype=np.float64), np.asarray(observed, dtype=np.float64)
+    k_all = p.size
+    return {float(p[k_all - 1 - k] - p[k]): float(o[k_all - 1 - k] - o[k]) for k in range(k_all // 2)
+            if abs(p[k] + p[k_all - 1 - k] - 1.0) <= 1e-12}
+
+
+def write_scores_csv(scores: dict, directory: str) -> Tuple[str, str]:
+    """`scores.csv` (one row: SCORES_HEADER) and `calibration_mixture.csv` (the reference's calibration header)."""
+    os.makedirs(directory, exist_ok=True)
+    paths = (os.path.join(directory, "scores.csv"), os.path.join(directory, "calibration_mixture.csv"))
+    with open(paths[0], "w") as f:
+        f.write(",".join(SCORES_HEADER) + "\n")
+        f.write(",".join(repr(int(scores[k])) if k in SCORES_HEADER[:3] else repr(float(scores[k])) for k in SCORES_HEADER) + "\n")
+    cal = scores["calibration"]
+    with open(paths[1], "w") as f:
+        f.write(",".join(CALIBRATION_HEADER) + "\n")
+        for row in zip(cal["expected"], cal["observed"]):
+            f.write(",".join(repr(float(v)) for v in row) + "\n")
+    return paths
+
+
+class PredictiveScorer:
+    """Streaming proper scoring rules of what an ensemble predicts at a pixel: the equal-weight mixture of its S member
+    densities (`mimo_score_accumulate`), scored at the label by
+
+        nll        -log of the mixture density, natural log, the FULL density (Laplace -|d|/b - log 2b, Gaussian
+                   -d^2/(2 sigma^2) - log sigma - log(2 pi)/2 per member).  This is not the training loss, which drops the
+                   constants and, for the Gaussian, a factor 1/2.
+        crps       the continuous ranked probability score, closed form for mixtures of Laplace / of Gaussian members
+        pit        the probability integral transform u = F(y); its histogram over `expected_p` gives the calibration
+                   curve (`observed_k` = share of pixels with u < p_k), its error and the coverage of central intervals
+
+    Member scale as the loss trains it: clamp(exp(p2), eps_min, eps_max) is the Laplace b, or the Gaussian variance.
+    Means and labels are NOT clipped — the rules score the distribution as predicted (the tables of `UncertaintyEvaluator`
+    clip both to [0, 1] as the reference's scripts do).  A pixel is skipped when mask == 0 (`n_masked`) or when its label or
+    any member's p1 / p2 is not finite (`n_nonfinite`).
+
+    `update` is asynchronous on the current stream; `compute` is the one host copy.  Single stream, single device, as
+    `UncertaintyEvaluator`."""
+
+    def __init__(self, expected_p: Optional[Sequence[float]] = None, channel: int = 0, device=None):
+        self.expected_p = check_expected_p(expected_p)
+        self.channel = int(channel)
+        if not torch.cuda.is_available():
+            raise L.MimoHipError("PredictiveScorer runs on an AMD GPU (mimo_score_*); no GPU is visible")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._lib = L.load()
+        k = self.expected_p.size
+        with torch.cuda.device(self.device):
+            self._p_dev = torch.from_numpy(self.expected_p.astype(np.float32)).to(self.device)
+            self._ws = torch.zeros(int(self._lib.mimo_score_workspace_bytes()) // 8 + 1, dtype=torch.int64, device=self.device)
+            self._out = torch.empty(k + 6, dtype=torch.float64, device=self.device)
+
+    def reset(self) -> None:
+        self._ws.zero_()
+
+    def _accumulate(self, p1, p2, label, mask, loss, eps_min, eps_max, maps):
+        if loss not in L.LOSS_KINDS:
+            raise ValueError(f"loss must be one of {tuple(L.LOSS_KINDS)}, not {loss!r}")
+        b, s, c, h, w, mc = check_score_shapes(p1, p2, label, mask, self.channel)
+        ts = []
+        for name, t in (("p1", p1), ("p2", p2), ("label", label)) + ((("mask", mask),) if mask is not None else ()):
+            if not t.is_cuda:
+                raise L.MimoHipError(f"PredictiveScorer: {name} is not on the GPU (there is no CPU path)")
+            ts.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        with torch.cuda.device(self.device):
+            out = [torch.empty(b, h, w, dtype=torch.float32, device=self.device) for _ in range(3)] if maps else [None] * 3
+            L.check(self._lib.mimo_score_accumulate(
+                ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr() if mask is not None else None, b, s, c,
+                self.channel, mc, h * w, L.LOSS_KINDS[loss], float(eps_min), float(eps_max), self._p_dev.data_ptr(),
+                self.expected_p.size, L.ptr(out[0]) or None, L.ptr(out[1]) or None, L.ptr(out[2]) or None,
+                self._ws.data_ptr(), L.current_stream()), "mimo_score_accumulate")
+        return tuple(out)
+
+    def update(self, p1, p2, label, mask=None, loss: str = "laplace_nll", eps_min: float = 1e-5, eps_max: float = 1e3) -> None:
+        """p1 / p2 [B,S,C,H,W] (the raw member outputs: mean and log-scale), label [B,C,H,W], mask [B,1,H,W] or [B,C,H,W],
+        all on the device.  Enqueues one pass; returns without synchronising."""
+        self._accumulate(p1, p2, label, mask, loss, eps_min, eps_max, False)
+
+    def score_maps(self, p1, p2, label, mask=None, loss: str = "laplace_nll", eps_min: float = 1e-5, eps_max: float = 1e3):
+        """`update`, which also returns the per-pixel (pit, nll, crps) as [B,H,W] device tensors (NaN where skipped)."""
+        return self._accumulate(p1, p2, label, mask, loss, eps_min, eps_max, True)
+
+    def update_from(self, ensemble, image, label, mask=None) -> None:
+        """Run an `EnsembleModule` on `image` and score the mixture of its raw member outputs without leaving the device;
+        the loss kind and its clamps come from `ensemble.loss_fn`."""
+        loss, eps_min, eps_max, _ = mixture_of(ensemble)
+        keep, raw = ensemble.keep_on_device, ensemble.return_raw_predictions
+        ensemble.keep_on_device, ensemble.return_raw_predictions = True, True
+        try:
+            p1, p2 = ensemble.forward_on_device(image)
+        finally:
+            ensemble.keep_on_device, ensemble.return_raw_predictions = keep, raw
+        self.update(p1, p2, label.to(p1.device), None if mask is None else mask.to(p1.device), loss, eps_min, eps_max)
+
+    def compute(self) -> dict:
+        k = self.expected_p.size
+        with torch.cuda.device(self.device):
+            L.check(self._lib.mimo_score_finalize(self._ws.data_ptr(), k, self._out.data_ptr(), L.current_stream()),
+                    "mimo_score_finalize")
+            o = self._out.cpu().numpy()  # the one transfer (and the one synchronisation)
+        n, n_masked, n_nonfinite = (int(v) for v in o[k: k + 3])
+        if n_nonfinite:
+            warnings.warn(f"PredictiveScorer: {n_nonfinite} pixels with a non-finite label or member output were skipped",
+                          RuntimeWarning, stacklevel=2)
+        observed = o[:k].copy()
+        return {"n": n, "n_masked": n_masked, "n_nonfinite": n_nonfinite,
+                "nll": float(o[k + 3]), "crps": float(o[k + 4]), "pit_mean": float(o[k + 5]),
+                "calibration": {"expected": self.expected_p.copy(), "observed": observed},
+                "calibration_error": float(np.mean(np.abs(observed - self.expected_p))),
+                "coverage": coverage_table(self.expected_p, observed)}
+
+    def write_csv(self, directory: str, scores: Optional[dict] = None) -> Tuple[str, str]:
+        """`scores.csv` and `calibration_mixture.csv`."""
+        return write_scores_csv(self.compute() if scores is None else scores, directory)

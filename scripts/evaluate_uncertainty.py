@@ -8,6 +8,11 @@ of the host route (the same tables from `.cpu()` copies: numpy argsort + 41 quan
     python scripts/evaluate_uncertainty.py --evidential --synthetic 2 --result_dir out   # a seeded EvidentialUnetModel
     python scripts/evaluate_uncertainty.py --evidential --model_checkpoint_paths ev.ckpt --batch_dir batches/ --result_dir out
     python scripts/evaluate_uncertainty.py --synthetic 8 --sources combined aleatoric epistemic --result_dir out
+    python scripts/evaluate_uncertainty.py --synthetic_model --synthetic 2 --monte_carlo_steps 4 --scores --result_dir out
+
+--scores: the proper scoring rules of the mixture predictive too (NLL, CRPS, PIT calibration of the equal-weight mixture of every
+member density: `PredictiveScorer`), written to scores.csv and calibration_mixture.csv.  With a model the members are the
+ensemble's raw outputs; with --synthetic alone three seeded Laplace members per pixel.
 
 --sources: the sparsification curve per uncertainty source and the oracle curve (sparsification.csv), AUSE / AURG (ause.csv).
 
@@ -29,7 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mimo.evaluation import UncertaintyEvaluator  # noqa: E402
+from mimo.evaluation import PredictiveScorer, UncertaintyEvaluator  # noqa: E402
 
 
 def seeded_maps(seed, b, size, device):
@@ -40,6 +45,17 @@ def seeded_maps(seed, b, size, device):
     mean = label + a_std * torch.randn(shape, generator=g, device=device)
     e_var = (0.3 * a_std * torch.randn(shape, generator=g, device=device)) ** 2
     return mean, a_std ** 2, e_var, label
+
+
+def seeded_members(seed, b, size, device, members=3):
+    """raw member outputs (p1, p2) [b, members, 1, size, size] around seeded_maps' mean and scale, and its label"""
+    mean, a_var, _, label = seeded_maps(seed, b, size, device)
+    g = torch.Generator(device=device).manual_seed(10_000 + seed)
+    shape = (b, members, 1, size, size)
+    scale = a_var.sqrt()[:, None] / 2 ** 0.5
+    p1 = mean[:, None] + 0.3 * scale * torch.randn(shape, generator=g, device=device)
+    p2 = torch.log(scale) + 0.2 * torch.randn(shape, generator=g, device=device)
+    return p1, p2, label
 
 
 def host_tables(batches, z, percentiles, clip=(0.0, 1.0)):
@@ -73,6 +89,7 @@ def main():
     ap.add_argument("--distribution", default="norm", choices=["norm", "laplace"])
     ap.add_argument("--sources", nargs="+", default=["combined"], choices=["combined", "aleatoric", "epistemic", "oracle"],
                     help="orderings of the sparsification curve; any beyond 'combined' adds the oracle, AUSE and AURG")
+    ap.add_argument("--scores", action="store_true", help="NLL, CRPS and PIT calibration of the mixture predictive")
     ap.add_argument("--result_dir", required=True)
     ap.add_argument("--no_host_route", action="store_true")
     args = ap.parse_args()
@@ -84,6 +101,8 @@ def main():
         from mimo.models.evidential_unet import EvidentialUnetModel
         if len(args.model_checkpoint_paths) > 1 or args.monte_carlo_steps:
             ap.error("--evidential takes one checkpoint and no --monte_carlo_steps")
+        if args.scores:
+            ap.error("--scores: the evidential model's Student-t predictive is not scored")
         if args.model_checkpoint_paths:
             ensemble = EvidentialUnetModel.load_from_checkpoint(args.model_checkpoint_paths[0])
         else:
@@ -106,6 +125,7 @@ def main():
                                   keep_on_device=True).to(dev)
 
     ev = UncertaintyEvaluator(distribution=args.distribution, sources=args.sources)
+    scorer = PredictiveScorer() if args.scores else None
     kept, update_ms, masked = [], [], False
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -129,6 +149,8 @@ def main():
             image, label = (torch.as_tensor(b[k]).to(dev) for k in ("image", "label"))
             mask = torch.as_tensor(b["mask"]).to(dev) if b.get("mask") is not None else None
             masked = masked or mask is not None
+            if scorer is not None:  # a second forward: the evaluator's maps and the raw members are two return modes
+                scorer.update_from(ensemble, image, label, mask)
             if args.no_host_route:
                 ev.update_from(ensemble, image, label, mask)  # the three-line form of INTEGRATION.md
             else:  # the same two steps apart, to time the update alone and to keep the maps for the host route
@@ -141,6 +163,8 @@ def main():
         ev.reset()
         for i in range(args.synthetic):
             timed_update(seeded_maps(i, args.batch, args.size, dev))
+            if scorer is not None:
+                scorer.update(*seeded_members(i, args.batch, args.size, dev))
 
     ev.compute()  # first call
     compute_ms = []
@@ -163,6 +187,12 @@ def main():
         res.update(update_ms_median=float(np.median(update_ms)), update_ms_min=float(np.min(update_ms)),
                    bytes_per_pixel=(20 if masked else 16) + records)
         res["update_GBps_at_min"] = res["bytes_per_pixel"] * pixels / (res["update_ms_min"] * 1e-3) / 1e9
+    if scorer is not None:
+        scores = scorer.compute()
+        scorer.write_csv(args.result_dir, scores)
+        members = 3 if ensemble is None else max(1, args.monte_carlo_steps) * ensemble.num_subnetworks
+        res["scores"] = {k: scores[k] for k in ("n", "nll", "crps", "pit_mean", "calibration_error")}
+        res["scores"].update(members=members, coverage_90=min(scores["coverage"].items(), key=lambda kv: abs(kv[0] - 0.9))[1])
     if "ause" in tables:
         res.update(ause=tables["ause"], aurg=tables["aurg"])
     if kept:
