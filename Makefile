@@ -9,7 +9,8 @@ LIB := mimo_unet_amd/libmimo_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 
 # test-only twin of the library: plan.hip compiled together with tests/host/plan_probe.hip, which copies a layer's input and
-# pre-activation tensor out of a plan (tests/test_plan_entry_gpu.py); same objects otherwise, same version script
+# pre-activation tensor out of a plan (tests/test_plan_entry_gpu.py) and tells which weight-gradient launch the recipe makes
+# (tests/test_wgrad_splits_gpu.py); same objects otherwise, same version script
 PROBE := mimo_unet_amd/libmimo_plan_probe.so
 
 all: $(LIB) $(PROBE)

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/mimo_hip.h"
 #include "conv_launch.h"
@@ -110,6 +111,14 @@ bool wgrad_np2_enabled();
 // (conv3x3_thin_ok queries the device once per process for the plain-FMA kernels' occupancy, whether or not a thin layer follows)
 static inline ConvEnv conv_env(int wg_cus) {
   return ConvEnv{conv3x3_thin_ok(1, 8) != 0, conv_ws_enabled(), conv_wide_force(), conv_ksplit_force(), wgrad_ws_enabled(), wgrad_np2_enabled(), wg_cus};
+}
+// The CUs the weight-gradient launches are sized for (ConvEnv::wg_cus): MIMO_WGRAD_CUS where it holds a value of 8..256, else
+// `sized_for` — the plan's sched::wg_side_cus, the whole chip (256) for a per-operator entry point.  Read per plan / call, as
+// MIMO_WGRAD_NP is, so that the entry points can run the split counts a plan of any size runs.
+static inline int wgrad_cus(int sized_for) {
+  const char* e = getenv("MIMO_WGRAD_CUS");
+  const int v = e ? atoi(e) : 0;
+  return (v >= 8 && v <= 256) ? v : sized_for;
 }
 // 1 when wgrad_split_launch runs this geometry on a kernel that can apply WgradLaunch::in_scale / in_shift in its loader
 int wgrad_split_fuses_input(int cin_p, int cout_p, int store, int np);

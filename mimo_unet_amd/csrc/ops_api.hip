@@ -160,9 +160,10 @@ int pack_image(Temp& t, int dir, int precision, const ConvDir& d, const float* w
 }
 
 // The recipe the plan makes for a layer of this geometry whose input channels lie in order (conv_recipe.h).  An entry point
-// has no network to derive sched::wg_side_cus from: its weight gradient is sized for the whole chip (256 CUs).
+// has no network to derive sched::wg_side_cus from: its weight gradient is sized for the whole chip (256 CUs), or for the
+// MIMO_WGRAD_CUS a plan would honour (wgrad_cus, common.h: the tests run the split counts of the plans' 128 and 192 CUs).
 ConvRecipe op_recipe(int precision, int n, int h, int w, int cin, int cin_p, int cout, int cout_p) {
-  return conv_recipe(precision, 0, n, h, w, cin, cout, cin_p, cout_p, true, conv_env(256));
+  return conv_recipe(precision, 0, n, h, w, cin, cout, cin_p, cout_p, true, conv_env(wgrad_cus(256)));
 }
 // tensors are 16-bit where the plan's are: the operands and results of the 16-bit storage kernels
 int stored_as(int precision, bool on_16bit_kernels) { return on_16bit_kernels ? precision : (int)MIMO_PREC_FP32; }

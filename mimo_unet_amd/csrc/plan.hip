@@ -794,9 +794,7 @@ struct mimo_plan {
     {
       // (a property of the plan, not of the stream mode: MIMO_WGRAD_STREAM=0 and the profiler's serialised pass run the same
       // launches, so the two modes stay bit-identical)
-      const char* e = getenv("MIMO_WGRAD_CUS");
-      const int v = e ? atoi(e) : 0;
-      env = conv_env((v >= 8 && v <= 256) ? v : sched::wg_side_cus((long)N * H * W, S * f));
+      env = conv_env(wgrad_cus(sched::wg_side_cus((long)N * H * W, S * f)));
       const char* d = getenv("MIMO_DEBUG_WGRAD_DELAY_US");
       wg_delay_us = d ? std::max(0, std::min(atoi(d), 5000)) : 0;
     }

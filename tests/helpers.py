@@ -197,6 +197,51 @@ def benchmark_conv_layers():
     return out
 
 
+_WGRAD_PROBE = None
+WGRAD_RECIPE_FIELDS = ("splits", "ci", "co", "ws", "np2", "tiles", "reduce_blocks", "store", "thin")
+
+
+def wgrad_probe():
+    """libmimo_plan_probe.so (the library's test-only twin, tests/host/plan_probe.hip) with its two host-only entry points
+    mimo_test_wgrad_recipe and mimo_test_wg_side_cus"""
+    global _WGRAD_PROBE
+    if _WGRAD_PROBE is None:
+        import ctypes as C
+        from mimo_unet_amd import _lib as L
+        lib = C.CDLL(os.path.join(os.path.dirname(L.LIB_PATH), "libmimo_plan_probe.so"))
+        lib.mimo_test_wgrad_recipe.restype = C.c_int
+        lib.mimo_test_wgrad_recipe.argtypes = [C.c_int32] * 9 + [C.POINTER(C.c_int32)]
+        lib.mimo_test_wg_side_cus.restype = C.c_int
+        lib.mimo_test_wg_side_cus.argtypes = [C.c_int64, C.c_int32]
+        _WGRAD_PROBE = lib
+    return _WGRAD_PROBE
+
+
+def wgrad_recipe(precision, layer, wg_cus=0):
+    """The weight-gradient launch the library's own conv_recipe makes for layer (N, H, W, Cin, Cout) in `precision` (a key
+    of _lib.PRECISIONS; not fp32) at `wg_cus` CUs — 0: at what mimo_op_conv3x3_wgrad runs right now (MIMO_WGRAD_CUS, else
+    256) — as a dict of WGRAD_RECIPE_FIELDS; MIMO_WGRAD_NP and the other switches are read as the library reads them."""
+    import ctypes as C
+    from mimo_unet_amd import _lib as L
+    N, H, W, Ci, Co = layer
+    out = (C.c_int32 * len(WGRAD_RECIPE_FIELDS))()
+    rc = wgrad_probe().mimo_test_wgrad_recipe(L.PRECISIONS[precision], N, H, W, Ci, conv_cin_pad(Ci), Co, pad8(Co), wg_cus, out)
+    assert rc == 0, (precision, layer, wg_cus, rc)
+    return dict(zip(WGRAD_RECIPE_FIELDS, out))
+
+
+def plan_wgrad_cus(layer):
+    """The distinct CU counts (sched::wg_side_cus) the benchmark's plans size their weight-gradient launches for, over every
+    (config, per-GPU batch) of bench.CONFIGS / benchmark_shards whose plan contains `layer`, ascending"""
+    import bench
+    cus = set()
+    for c in bench.CONFIGS.values():
+        for n in benchmark_shards(c):
+            if layer in config_conv_layers(c, n):
+                cus.add(int(wgrad_probe().mimo_test_wg_side_cus(n * c["H"] * c["W"], c["S"] * c["f"])))
+    return sorted(cus)
+
+
 def conv3x3_reference_f64(x, w, b, dz, chunk_elems=1 << 26):
     """Reference of one 3 x 3 reflect-padded convolution (components.py:23,26) in float64, on the inputs' device.
 
@@ -323,9 +368,12 @@ def check_bf16_rounded(got, ref, label, acc_k=None, fp32_ref=None):
     tensor's scale (derived on reduction lengths <= 4096); with `acc_k` ({quantity: reduction length}) within
     fp32_acc_bound(k, 2e-6).  With `fp32_ref` (the reference on the unrounded operands), a forward or weight gradient that
     ran on the plain-FMA fp32 kernels instead (the image layer, conv_thin.hip, taken by the plan in this mode too) passes
-    at the fp32 bound 2e-5 against it.  Reports (after `label`) and returns {quantity: error}, {quantity: worst index}."""
+    at the fp32 bound 2e-5 against it.  Operators that were not run (conv_outputs) are left out.  Reports (after `label`)
+    and returns {quantity: error}, {quantity: worst index}."""
     errs, where, bad = {}, {}, {}
     for q, rk in (("fwd", "z"), ("dgrad", "dx"), ("wgrad", "dw")):
+        if rk not in got:
+            continue
         r = ref[rk].to(got[rk].device)
         errs[q], where[q] = err_where(got[rk], r)
         if errs[q] < (fp32_acc_bound(acc_k[q], 2e-6) if acc_k else 2e-6):
@@ -353,9 +401,14 @@ def check_storage_rounded(got, ref, mode, label, acc_k=None):
     floor is max(1e-3, fp32_acc_bound(K, 0) * max|z| / ulp) — the element-wise error stays within the fp32 accumulation
     bound of the tensor's scale there (observed in 16-mixed on the benchmark's layers: up to 1.95 units at the 1e-3 floor
     for K = 2160 ... 8640, all within one unit of the K floor; bf16-mixed, whose unit is 8 x wider, stays within one unit
-    at 1e-3).  Reports (after `label`) and returns the errors (z and dx in units in the last place) and the worst
-    indices."""
+    at 1e-3).  Outputs of the weight gradient alone (conv_outputs without z and dx): the dW criterion alone.  Reports
+    (after `label`) and returns the errors (z and dx in units in the last place) and the worst indices."""
     dt, ulp = STORAGE_TYPES[mode]
+    if "z" not in got and "dx" not in got:
+        e, at = err_where(got["dw"], ref["dw"].to(got["dw"].device))
+        report(*label, f"dW {e:.1e}", "worst at", at)
+        assert e < 5e-6, ({"wgrad": e}, at)
+        return {"wgrad": e}, {"wgrad": at}
     dev = got["z"].device
     r = lambda t: t.to(dt).double()
     z, dx = got["z"].double(), got["dx"].double()

@@ -15,7 +15,13 @@
 //     nothing else, and the pack job built from the same recipe (pack::make_job, as build() and the entry points call it)
 //     carries the pair tail, the wide rows, the rows and the columns of that launch: what the weight image is laid out for is
 //     what the kernel is told
+//   * the weight gradient's split count (sched::wg_pick_splits through conv_recipe) at the 128, 192 and 256 CUs the plans
+//     size it for, on every table geometry at every per-GPU batch of the benchmark's shards and on the cases of
+//     tests/test_wgrad_splits_gpu.py: 1 <= splits <= min(tiles, 1024), no split of the strided tile walk without a tile, and
+//     the slabs the reduction writes behind them fit the splits + splits / 8 + 2 slabs the plan and the entry points
+//     allocate — the last also for every split count 1..1024 with both final fans, whatever the picker picks
 #include <cstdio>
+#include <initializer_list>
 
 #include "../../mimo_unet_amd/csrc/conv_launch.h"
 
@@ -74,7 +80,83 @@ static void check_dir(const Row& t, int row, int dir, const ConvRecipe& r, const
         "row %d %s: launch geometry", row, name);
 }
 
+// slabs wgrad_reduce_launch (conv3x3.hip) writes behind the `splits` slabs of the weight-gradient kernel: stage A sums groups
+// of 16 into the slabs behind its inputs until <= final_fan slabs are left (16 with >= 512 blocks in the last kernel, else 1)
+static int reduce_extra_slabs(int splits, int final_fan) {
+  int extra = 0;
+  for (int n = splits; n > final_fan;) {
+    n = sched::cdiv(n, 16);
+    extra += n;
+  }
+  return extra;
+}
+
+static void check_wg_splits(int precision, int N, int H, int W, int Cin, int Cout, int cin_p, long* checked, long* below_256_differs) {
+  const int cout_p = sched::rup(Cout, 8);
+  int at256 = 0;
+  for (const int cus : {256, 192, 128})
+    for (const bool ws : {true, false}) {
+      ConvEnv e;
+      e.wgrad_ws = ws;
+      e.wg_cus = cus;
+      const ConvRecipe r = conv_recipe(precision, 0, N, H, W, Cin, Cout, cin_p, cout_p, true, e);
+      if (!r.wg_split) return;
+      int CI, CO;
+      sched::wg_tiles(cin_p, cout_p, ws, &CI, &CO);
+      const bool s16 = r.wg_store == 1 || r.wg_store == 2;
+      const int tiles = sched::wg_num_tiles(N, H, W, sched::wg_use_ws(CI, CO, ws) ? sched::wg_ws_tr(CI, s16) : 4);
+      const int s = r.wg_splits;
+      CHECK(s >= 1 && s <= tiles && s <= 1024, "prec %d %dx%dx%d %d->%d at %d CUs ws %d: %d splits of %d tiles", precision, N, H, W, Cin, Cout,
+            cus, (int)ws, s, tiles);
+      if (s < 1) continue;
+      // wgrad_split_ws_kernel: split b owns tiles b, b + s, ...: (tiles - 1 - b) / s + 1 of them; the last split the fewest
+      CHECK(s - 1 < tiles && (tiles - 1 - (s - 1)) / s + 1 >= 1, "prec %d %dx%dx%d %d->%d at %d CUs: the last of %d splits owns no tile of %d",
+            precision, N, H, W, Cin, Cout, cus, s, tiles);
+      const int blocks = sched::cdiv(r.wg_cin_pad, 32) * sched::cdiv(r.wg_cout_pad, 8);
+      const int extra = reduce_extra_slabs(s, blocks >= 512 ? 16 : 1);
+      CHECK(extra <= s / 8 + 2, "prec %d %dx%dx%d %d->%d at %d CUs: %d splits, %d reduction blocks: %d stage-A slabs > %d", precision, N, H, W,
+            Cin, Cout, cus, s, blocks, extra, s / 8 + 2);
+      ++*checked;
+      if (ws && cus == 256) at256 = s;
+      if (ws && cus != 256 && s != at256) ++*below_256_differs;
+    }
+}
+
+static void test_wg_splits() {
+  // the sizing rule itself, independent of the picker: every stage-A output of any split count fits splits / 8 + 2 slabs
+  for (int s = 1; s <= 1024; ++s) {
+    int all_stages = 0;  // ceil(s / 16) + ceil(s / 256) + ... down to one slab
+    for (int n = s; n > 1;) {
+      n = sched::cdiv(n, 16);
+      all_stages += n;
+    }
+    CHECK(all_stages <= s / 8 + 2 && reduce_extra_slabs(s, 1) == all_stages && reduce_extra_slabs(s, 16) <= all_stages,
+          "%d splits: %d / %d stage-A slabs (final fan 1 / 16), %d allocated", s, reduce_extra_slabs(s, 1), reduce_extra_slabs(s, 16), s / 8 + 2);
+  }
+  long checked = 0, differs = 0;
+  const int precisions[] = {MIMO_PREC_SPLIT16, MIMO_PREC_BF16, MIMO_PREC_BF16_MIXED, MIMO_PREC_FP16_MIXED};
+  // every geometry of the table (the benchmark's layers and the CONV_CASES) at the table's batch and at every per-GPU batch
+  // of the benchmark's shards
+  const int rows = (int)(sizeof(kTable) / sizeof(kTable[0]));
+  for (int i = 0; i < rows; ++i) {
+    const Row& t = kTable[i];
+    if (t.precision != MIMO_PREC_SPLIT16 || t.inference_only != 0 || !(t.envs & 8)) continue;  // one row per geometry
+    for (const int N : {t.N, 2, 4, 8, 16, 32, 64})
+      for (const int p : precisions) check_wg_splits(p, N, t.H, t.W, t.Cin, t.Cout, t.cin_p, &checked, &differs);
+  }
+  // the cases of tests/test_wgrad_splits_gpu.py
+  static const int kCases[][5] = {{4, 64, 96, 30, 30},    {3, 40, 72, 90, 45},   {3, 68, 96, 30, 30},      {1, 16, 16, 480, 480},
+                                  {2, 16, 16, 240, 240},  {2, 32, 16, 240, 240}, {2, 50, 70, 84, 42},      {1, 8, 8, 960, 480},
+                                  {7, 20, 33, 60, 60},    {2, 86, 512, 264, 520}, {5, 28, 544, 264, 520},  {3, 40, 72, 60, 45},
+                                  {3, 40, 72, 60, 30},    {3, 40, 72, 90, 60}};
+  for (const auto& c : kCases)
+    for (const int p : precisions) check_wg_splits(p, c[0], c[1], c[2], c[3], c[4], sched::rup(c[3], 8), &checked, &differs);
+  CHECK(checked > 1000 && differs > 100, "%ld split counts checked, %ld of them other than at 256 CUs", checked, differs);
+  std::printf("%ld weight-gradient split counts, %ld of them other than the one at 256 CUs\n", checked, differs);
+}
+
 int main() {
+  test_wg_splits();
   const int rows = (int)(sizeof(kTable) / sizeof(kTable[0]));
   int thin_rows = 0, wide_rows = 0, pair_rows = 0, ksplit_rows = 0, np2_rows = 0;
   int covered = 0;

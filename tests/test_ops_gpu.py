@@ -8,7 +8,8 @@ import torch.nn.functional as F
 
 from oracle import mimo_oracle as O
 from tests.helpers import (STORAGE_TYPES, benchmark_conv_layers, check_bf16_rounded, check_conv_results, check_storage_rounded,
-                           config_conv_layers, conv3x3_reference_f64, conv_cin_pad, conv_outputs, pad8, rel_err, report)
+                           config_conv_layers, conv3x3_reference_f64, conv_cin_pad, conv_outputs, pad8, plan_wgrad_cus, rel_err, report,
+                           wgrad_recipe)
 
 pytestmark = pytest.mark.gpu
 
@@ -401,13 +402,35 @@ def production_modes(layer):
     return modes
 
 
+def plan_split_counts(layer, mode):
+    """The MIMO_WGRAD_CUS values under which test_conv3x3_at_benchmark_batches_vs_fp64 runs the weight gradient of `layer`
+    once more in `mode` (of production_modes): every CU count a benchmark plan that contains the layer sizes its weight
+    gradient for (helpers.plan_wgrad_cus) at which the library's recipe (helpers.wgrad_recipe) splits the pixels otherwise
+    than at the entry points' 256.  None in fp32 (sched::wg32_pick_splits does not take the CU count) and where the
+    plain-FMA image kernel runs (no splits)."""
+    if mode == "fp32":
+        return []
+    prec = "split16" if mode == "split16-np3" else mode
+    at256 = wgrad_recipe(prec, layer, 256)
+    if at256["thin"]:
+        return []
+    return [c for c in plan_wgrad_cus(layer) if c != 256 and wgrad_recipe(prec, layer, c)["splits"] != at256["splits"]]
+
+
 @pytest.mark.parametrize("layer", BENCH_LAYERS, ids=lambda c: "x".join(map(str, c)))
 def test_conv3x3_at_benchmark_batches_vs_fp64(layer, monkeypatch):
     """Forward, data gradient and weight gradient of every 3 x 3 convolution the benchmark runs (benchmark_conv_layers:
     cfg3, cfg2 and cfg4 at their batches and their 2 / 4 / 8-GPU shards), through mimo_op_conv3x3_*, which take the
-    plan's per-geometry choices (wide or bf16x3 decomposition, K split, pair tail, weight-gradient split counts, the
-    plain-FMA image-layer weight gradient from 4 x (resident workgroups) tiles on), against conv3x3_reference_f64 on the
-    same device-generated operands.  Those choices depend on N: the small CONV_CASES never reach several of them.
+    plan's per-geometry choices (wide or bf16x3 decomposition, K split, pair tail, the plain-FMA image-layer weight
+    gradient from 4 x (resident workgroups) tiles on), against conv3x3_reference_f64 on the same device-generated operands.
+    Those choices depend on N: the small CONV_CASES never reach several of them.
+
+    The weight gradient's split count is the one choice the entry points do not share with the plans: it follows from the
+    CUs the launch is sized for, 256 at an entry point, sched::wg_side_cus — 128 or 192 for every strong-scaling shard and
+    for cfg2 at 32 — in a plan, and most layers split otherwise there.  So after the pass at 256 CUs, every mode but fp32
+    runs the weight gradient alone once more under MIMO_WGRAD_CUS for each CU count of a plan that contains the layer at
+    which the library's own recipe gives another split count (plan_split_counts), against the same reference under the same
+    bounds: the split counts run are the entry points' and those of the benchmark's plans.
 
     Operands as in training: the image layer reads U[0, 1) pixels, every other layer post-ReLU activations (about half
     zeros); init-scale weights; dz of the size a mean loss over N x S x H x W outputs leaves (1 / (2 N H W): the two-MFMA
@@ -447,6 +470,16 @@ def test_conv3x3_at_benchmark_batches_vs_fp64(layer, monkeypatch):
     ref = conv3x3_reference_f64(x, w, b, dz)
     acc_k = {"fwd": 9 * Ci, "dgrad": 9 * Co, "wgrad": N * H * W}  # reduction lengths (fp32_acc_bound)
     rounded = {}  # storage type -> (x, w, dz) rounded to it and their reference (bf16 and bf16-mixed share one)
+    def at_plan_split_counts(mode, check, xs, dzs):  # the weight gradient alone at the plans' split counts, same bounds
+        for cus in plan_split_counts(layer, mode):
+            with monkeypatch.context() as m:
+                m.setenv("MIMO_WGRAD_CUS", str(cus))
+                prec = "split16" if mode == "split16-np3" else mode
+                splits = wgrad_recipe(prec, layer, 0)["splits"]
+                assert splits == wgrad_recipe(prec, layer, cus)["splits"] != wgrad_recipe(prec, layer, 256)["splits"]
+                check(run_conv(lib, xs, w, b, dzs, Ci, Co, L.PRECISIONS[prec], fwd=False, dgrad=False),
+                      ("conv at benchmark batch", mode, layer, "sized for", cus, "CUs:", splits, "splits"))
+
     for mode in modes:
         label = ("conv at benchmark batch", mode, layer)
         if mode == "split16-np3":
@@ -454,6 +487,7 @@ def test_conv3x3_at_benchmark_batches_vs_fp64(layer, monkeypatch):
                 m.setenv("MIMO_WGRAD_NP", "3")
                 got = run_conv(lib, x, w, b, dz, Ci, Co, L.PRECISIONS["split16"], fwd=False, dgrad=False)
                 check_conv_results(got, ref, "split16", label)
+                at_plan_split_counts(mode, lambda o, lb: check_conv_results(o, ref, "split16", lb), x, dz)
             continue
         dt = torch.float16 if mode == "16-mixed" else torch.bfloat16
         if mode != "split16" and mode != "fp32" and dt not in rounded:
@@ -466,10 +500,17 @@ def test_conv3x3_at_benchmark_batches_vs_fp64(layer, monkeypatch):
             if mode == "bf16":
                 check_bf16_rounded(got, rounded[dt][3], label + ("rounded operands",), acc_k,
                                    fp32_ref=ref if Ci <= 4 else None)
+
+            def check(o, lb, mode=mode, dt=dt):
+                check_conv_results(o, ref, mode, lb)
+                if mode == "bf16":
+                    check_bf16_rounded(o, rounded[dt][3], lb + ("rounded operands",), acc_k, fp32_ref=ref if Ci <= 4 else None)
+            at_plan_split_counts(mode, check, x, dz)
         else:
             xr, _, dzr, rref = rounded[dt]
             got = run_conv(lib, xr, w, b, dzr, Ci, Co, L.PRECISIONS[mode])
             check_storage_rounded(got, rref, mode, label, acc_k)
+            at_plan_split_counts(mode, lambda o, lb, mode=mode, rref=rref: check_storage_rounded(o, rref, mode, lb, acc_k), xr, dzr)
         del got
     del x, w, b, dz, ref, rounded
     torch.cuda.empty_cache()

@@ -49,8 +49,9 @@ def test_pack_layout_under_asan_ubsan(tmp_path):
 def test_conv_recipe_under_asan_ubsan(tmp_path):
     """mimo_unet_amd/csrc/conv_recipe.h: the launch decisions of every convolution of cfg2, cfg3 and cfg4 at the benchmark's
     batches and of the per-operator test geometries, in the five precisions and with the image kernels and the
-    wave-specialised kernels on and off, against a table of what the code it replaced decided; and the pack job of every
-    row carries the pair tail and wide rows its launch gets (tests/host/conv_recipe_test.cpp)."""
+    wave-specialised kernels on and off, against a table of what the code it replaced decided; the pack job of every
+    row carries the pair tail and wide rows its launch gets; and the weight gradient's split count at 128, 192 and 256 CUs
+    leaves no split without a tile and its reduction inside the slabs allocated (tests/host/conv_recipe_test.cpp)."""
     _run_host_test(tmp_path, "conv_recipe_test")
 
 
