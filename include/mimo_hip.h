@@ -670,7 +670,7 @@ int mimo_op_head_backward(const mimo_op_head_backward_args* args, mimo_stream st
  *   shift = beta - mean scale;  running_mean / running_var (in place) move by `momentum` towards mean and the unbiased
  *   variance var count / (count - 1) (var itself when count == 1);  channels [c, c_p) of the four vectors are zeros.
  * route: 1 = the one-launch column sum + finalize (rows <= 2048); 2 = the chunked row sum (at most 64 fp64 chunk rows)
- * followed by the finalize launch, which has no status word; 0 = the plan's rule: "rows <= kColsumMaxRows (2048): the one
+ * followed by the finalize launch (the same status word); 0 = the plan's rule: "rows <= kColsumMaxRows (2048): the one
  * launch; otherwise row sum + finalize".  training = 0: mean / invstd / scale / shift from the running statistics instead
  * (partial, rows, count, route and momentum unused).  status (host, or NULL): bit 1 when a channel sum (eval: a running
  * statistic or its scale) is not finite.

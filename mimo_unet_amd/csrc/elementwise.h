@@ -54,10 +54,11 @@ int fold_image_grad_mc_launch(const float* dxpad, int ldp, int B, int R, int C, 
 
 // ---- BatchNorm + ReLU (+ Dropout2d) forward ---------------------------------------------
 // training, more than kColsumMaxRows partial rows: sums = rowsum of the conv epilogue partials ([chunks][2*cout_pad]).
+// status: as bn_fwd_stats_launch (a chunk sum that is not finite)
 int bn_fwd_finalize_launch(const double* sums, int chunks, int cout_pad, int C, int Cp, int64_t count,
                            const float* gamma, const float* beta, float* running_mean, float* running_var,
                            float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
-                           hipStream_t st);
+                           int* status, hipStream_t st);
 int bn_eval_prepare_launch(int C, int Cp, const float* gamma, const float* beta, const float* running_mean,
                            const float* running_var, float eps, float* mean, float* invstd, float* scale,
                            float* shift, hipStream_t st, int* status = nullptr);

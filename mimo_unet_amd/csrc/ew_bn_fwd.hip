@@ -58,12 +58,13 @@ __device__ __forceinline__ void bn_fwd_finalize_channel(
   running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
 }
 
-// second step of the rowsum route (more than kColsumMaxRows partial rows, ops_api.hip): no status word
+// second step of the rowsum route (more than kColsumMaxRows partial rows: plan.hip convbn_forward, ops_api.hip); the chunk
+// sums carry a partial that is not finite, so the status word is raised here as in bn_fwd_stats_kernel
 __global__ void bn_fwd_finalize_kernel(const double* __restrict__ sums, int chunks, int cout_pad, int C, int Cp,
                                        double count, const float* __restrict__ gamma, const float* __restrict__ beta,
                                        float* __restrict__ running_mean, float* __restrict__ running_var,
                                        float momentum, float eps, float* __restrict__ mean, float* __restrict__ invstd,
-                                       float* __restrict__ scale, float* __restrict__ shift) {
+                                       float* __restrict__ scale, float* __restrict__ shift, int* __restrict__ status) {
   __shared__ double red[512];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int cols = 2 * cout_pad;
@@ -71,7 +72,7 @@ __global__ void bn_fwd_finalize_kernel(const double* __restrict__ sums, int chun
   chunk_total2(sums + c, sums + cout_pad + c, cols, chunks, c < C, red, &s1, &s2);
   if (c >= Cp || threadIdx.x >= 64) return;
   bn_fwd_finalize_channel(c, C, s1, s2, count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift,
-                          nullptr);
+                          status);
 }
 
 // rowsum + bn_fwd_finalize in one launch: partial rows [rows][2][cout_pad] straight from the convolution epilogue
@@ -101,9 +102,9 @@ int bn_fwd_stats_launch(const float* partial, int rows, int cout_pad, int C, int
 int bn_fwd_finalize_launch(const double* sums, int chunks, int cout_pad, int C, int Cp, int64_t count,
                            const float* gamma, const float* beta, float* running_mean, float* running_var,
                            float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
-                           hipStream_t st) {
+                           int* status, hipStream_t st) {
   hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(256), 0, st, sums, chunks, cout_pad, C, Cp,
-                     (double)count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift);
+                     (double)count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift, status);
   MIMO_KERNEL_CHECK();
   return MIMO_OK;
 }

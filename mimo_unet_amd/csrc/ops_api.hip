@@ -611,7 +611,7 @@ int mimo_op_bn_stats(const mimo_op_bn_stats_args* p, mimo_stream stream) {
     int chunks = 0;
     MIMO_TRY(rowsum_launch(a.partial, a.rows, 2 * a.cout_pad, sums, &chunks, st));
     MIMO_TRY(bn_fwd_finalize_launch(sums, chunks, a.cout_pad, a.c, a.c_p, a.count, a.gamma, a.beta, a.running_mean, a.running_var,
-                                    a.momentum, a.eps, a.mean, a.invstd, a.scale, a.shift, st));
+                                    a.momentum, a.eps, a.mean, a.invstd, a.scale, a.shift, status, st));
   }
   MIMO_HIP_CHECK(hipStreamSynchronize(st));
   return read_status(status, a.status);

@@ -1093,7 +1093,7 @@ struct mimo_plan {
         MIMO_TRY(rowsum_launch(s_partial, rows, 2 * L.r.fwd.rows, s_sums, &chunks, st));
         MIMO_TRY(bn_fwd_finalize_launch(s_sums, chunks, L.r.fwd.rows, L.Cout, L.cout_p, P, params + L.off_gamma,
                                         params + L.off_beta, bnbuf + L.off_rm, bnbuf + L.off_rv, cfg.bn_momentum,
-                                        cfg.bn_eps, L.mean, L.invstd, L.scale, L.shift, st));
+                                        cfg.bn_eps, L.mean, L.invstd, L.scale, L.shift, d_status, st));
       }
     }
     if (!fused && !elide) {
