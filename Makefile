@@ -3,7 +3,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := mimo_unet_amd/csrc
-SRCS := $(CSRC)/conv3x3.hip $(CSRC)/conv_thin.hip $(CSRC)/conv_bf16x3.hip $(CSRC)/conv_wide.hip $(CSRC)/wgrad_split.hip $(CSRC)/ew_reduce.hip $(CSRC)/ew_layout.hip $(CSRC)/ew_bn_fwd.hip $(CSRC)/ew_resample.hip $(CSRC)/ew_dropout.hip $(CSRC)/ew_bn_bwd.hip $(CSRC)/ew_head_loss.hip $(CSRC)/perm_draw.hip $(CSRC)/fgsm.hip $(CSRC)/pgd.hip $(CSRC)/monitor.hip $(CSRC)/evidential_eval.hip $(CSRC)/optim.hip $(CSRC)/plan.hip $(CSRC)/ops_api.hip $(CSRC)/eval/eval_stats.hip $(CSRC)/eval/score_rules.hip $(CSRC)/optim_clip/grad_clip.hip $(CSRC)/data/dataset_gather.hip $(CSRC)/scene/scene_tiles.hip
+SRCS := $(CSRC)/conv3x3.hip $(CSRC)/conv_thin.hip $(CSRC)/conv_bf16x3.hip $(CSRC)/conv_wide.hip $(CSRC)/wgrad_split.hip $(CSRC)/ew_reduce.hip $(CSRC)/ew_layout.hip $(CSRC)/ew_bn_fwd.hip $(CSRC)/ew_resample.hip $(CSRC)/ew_dropout.hip $(CSRC)/ew_bn_bwd.hip $(CSRC)/ew_head_loss.hip $(CSRC)/perm_draw.hip $(CSRC)/fgsm.hip $(CSRC)/pgd.hip $(CSRC)/monitor.hip $(CSRC)/evidential_eval.hip $(CSRC)/optim.hip $(CSRC)/plan.hip $(CSRC)/ops_api.hip $(CSRC)/eval/eval_stats.hip $(CSRC)/eval/score_rules.hip $(CSRC)/eval/score_evidential.hip $(CSRC)/optim_clip/grad_clip.hip $(CSRC)/data/dataset_gather.hip $(CSRC)/scene/scene_tiles.hip
 OBJS := $(SRCS:.hip=.o)
 LIB := mimo_unet_amd/libmimo_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
@@ -17,7 +17,7 @@ all: $(LIB) $(PROBE)
 
 # every compile leaves hipcc's per-kernel resource remarks next to the object (csrc/*.res): scripts/check_resources.py
 # fails the build when a kernel that counts its vector-memory operations by hand (LDS-DMA) touches scratch
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/pack_layout.h $(CSRC)/conv_recipe.h $(CSRC)/conv_launch.h $(CSRC)/tile_sched.h $(CSRC)/dz_ring.h $(CSRC)/graph_replay.h $(CSRC)/elementwise.h $(CSRC)/ew_device.h $(CSRC)/adam_update.h $(CSRC)/block_reduce.h $(CSRC)/evidential.h $(CSRC)/philox.h include/mimo_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/pack_layout.h $(CSRC)/conv_recipe.h $(CSRC)/conv_launch.h $(CSRC)/tile_sched.h $(CSRC)/dz_ring.h $(CSRC)/graph_replay.h $(CSRC)/elementwise.h $(CSRC)/ew_device.h $(CSRC)/adam_update.h $(CSRC)/block_reduce.h $(CSRC)/evidential.h $(CSRC)/philox.h $(CSRC)/eval/score_common.h $(CSRC)/eval/student_t.h include/mimo_hip.h
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(@:.o=.res) || (grep -v "remark:" $(@:.o=.res) >&2; false)
 	@grep -E "warning:|error:" -A3 $(@:.o=.res) >&2 || true
 

@@ -543,6 +543,29 @@ int mimo_score_accumulate(const float* p1, const float* p2, const float* label, 
                           int32_t members, int32_t channels, int32_t channel, int32_t mask_channels, int64_t hw,
                           int32_t loss_kind, float eps_min, float eps_max, const float* expected_p, int32_t num_thresholds,
                           float* pit_map, float* nll_map, float* crps_map, void* workspace, mimo_stream stream);
+/* The same three rules for the evidential model: the posterior predictive of the Normal-Inverse-Gamma heads at a pixel,
+ * scored into the same workspace (a mixture call and an evidential call on one workspace add up; mimo_score_finalize
+ * serves both).  logits [batch,4,hw] fp32 contiguous; the heads are (mu, v, alpha, beta) = (l0, softplus(l1),
+ * softplus(l2) + 1, softplus(l3)) (softplus with threshold 20), v, alpha and beta fp32 values.  The predictive is
+ * Student-t with nu = 2 alpha degrees of freedom, location mu and scale sigma = sqrt(beta (1 + v) / (v alpha)).  With
+ * z = (y - mu) / sigma and x = nu / (nu + z^2):
+ *   PIT   u = F_nu(z) = I_x(nu/2, 1/2) / 2 for z <= 0, 1 - I_x(nu/2, 1/2) / 2 for z > 0 (I the regularised incomplete beta
+ *         function; u == 0.5 exactly at z == 0)
+ *   NLL   -lgamma(alpha + 1/2) + lgamma(alpha) + ln(nu pi) / 2 + ln sigma + (alpha + 1/2) log1p(z^2 / nu)
+ *   CRPS  sigma [ z (2 F_nu(z) - 1) + 2 f_nu(z) (nu + z^2) / (nu - 1)
+ *                 - 2 sqrt(nu) / (nu - 1) B(1/2, nu - 1/2) / B(1/2, nu/2)^2 ]        (Jordan, Krueger, Lerch 2019)
+ *         f_nu the standard Student-t density; valid for nu > 1, and nu >= 2 here.
+ * Evaluated in double from the fp32 heads and rounded once into the fp32 maps; means and labels are not clipped.
+ * label [batch,1,hw]; mask [batch,hw] or NULL; maps [batch,hw] or NULL; expected_p and workspace as above.  A pixel with
+ * mask == 0 is skipped and counted in n_masked; otherwise one whose label or any of its four logits is not finite, or whose
+ * v or beta is 0 (the fp32 softplus has underflowed: l < -103), is skipped and counted in n_nonfinite; alpha == 1 exactly
+ * is scored.  A skipped pixel gets NaN in every map.  Workspace word 71 keeps the most iterations the incomplete-beta
+ * continued fraction of any pixel took (at most its compile-time cap; a diagnostic, not read by mimo_score_finalize).
+ * MIMO_ERR_INVALID with nothing launched: a null logits / label / expected_p / workspace, batch < 1, hw < 1,
+ * num_thresholds outside 1 ... 64, a pointer that is not 4-byte aligned. */
+int mimo_score_accumulate_evidential(const float* logits, const float* label, const float* mask, int32_t batch, int64_t hw,
+                                     const float* expected_p, int32_t num_thresholds, float* pit_map, float* nll_map,
+                                     float* crps_map, void* workspace, mimo_stream stream);
 /* out: device doubles [num_thresholds + 6] = the share of scored pixels with PIT < expected_p[k] per threshold, then n,
  * n_masked, n_nonfinite, mean NLL, mean CRPS, mean PIT (the shares and the means are NaN at n == 0). */
 int mimo_score_finalize(const void* workspace, int32_t num_thresholds, double* out, mimo_stream stream);

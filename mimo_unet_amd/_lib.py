@@ -196,6 +196,7 @@ _SIGNATURES = {
     "mimo_eval_interval_sums_by": (C.c_int, [_P, _I, _P, _I, _L, _I, _I, _P, _P, _P]),
     "mimo_score_workspace_bytes": (C.c_size_t, []),
     "mimo_score_accumulate": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P]),
+    "mimo_score_accumulate_evidential": (C.c_int, [_P, _P, _P, _I, _L, _P, _I, _P, _P, _P, _P, _P]),
     "mimo_score_finalize": (C.c_int, [_P, _I, _P, _P]),
     "mimo_op_conv3x3_forward": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mimo_op_conv3x3_dgrad": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

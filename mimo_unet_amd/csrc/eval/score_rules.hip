@@ -29,7 +29,10 @@
 //
 // Sums are doubles in a FIXED order (thread -> workgroup tree -> partial row -> fold over the rows), counts are integer
 // atomics in LDS: the same sequence of calls gives the same bits.
-#include "../common.h"
+//
+// The workspace, the tally of a scored pixel, the workgroup prologue / epilogue and the fold are score_common.h's, shared
+// with the evidential model's Student-t scorer (score_evidential.hip).
+#include "score_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -37,23 +40,9 @@
 namespace mimo {
 namespace score {
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 constexpr int kMaxS = 64;        // members
 constexpr int kRegS = 4;         // ... up to which the pair loop runs from registers
-constexpr int kMaxK = 64;        // PIT thresholds
-constexpr int kBins = kMaxK + 1; // bin j = first k with u < p_k; bin K = never below (eval_stats.hip: eval_pixel)
-constexpr int kAccWords = 72;    // [0,65) bins, 65 n, 66 n_masked, 67 n_nonfinite, 68 sum NLL, 69 sum CRPS, 70 sum PIT (doubles)
-constexpr int kFolded = 71;
-constexpr int kBlocks = 1024;    // partial rows = the most workgroups of one launch
 constexpr int kTile = 256;       // pixels of an LDS tile = threads of a workgroup
-
-// The torch-owned workspace (mimo_score_workspace_bytes; zeroed by the caller at reset).
-struct Workspace {
-  u64 acc[kAccWords];
-  u64 part[kBlocks][kAccWords];
-};
 
 struct Args {
   const float *p1, *p2, *label, *mask, *pk;
@@ -64,10 +53,7 @@ struct Args {
   u64* part;
 };
 
-__device__ __forceinline__ double as_double(u64 v) { return __longlong_as_double((long long)v); }
-__device__ __forceinline__ u64 as_u64(double v) { return (u64)__double_as_longlong(v); }
-
-constexpr float kRsqrt2 = 0.70710678118654752f;     // 1 / sqrt 2
+constexpr float kRsqrt2 =0.70710678118654752f;     // 1 / sqrt 2
 constexpr float kRsqrt2Pi = 0.39894228040143268f;   // 1 / sqrt(2 pi)
 constexpr float kRsqrtPi = 0.56418958354775629f;    // 1 / sqrt pi
 constexpr double kHalfLog2Pi = 0.91893853320467274178;  // log(2 pi) / 2
@@ -168,68 +154,6 @@ __device__ __forceinline__ void score_pixel(Mem& mem, int S_rt, float y, double 
   pit = (float)(sF * inv);
   nll = (float)-(mx + log(sE * inv));
   crps = (float)(sA * inv - (2.0 * sC + sD) * (0.5 * inv * inv));
-}
-
-struct Tally {
-  u32 n = 0, nm = 0, nf = 0;
-  double nll = 0.0, crps = 0.0, pit = 0.0;
-};
-
-// bin and sums of one scored pixel, from the fp32 values its maps get
-__device__ __forceinline__ void tally_pixel(float pit, float nll, float crps, const float* __restrict__ zt, int K,
-                                            u32* __restrict__ bins, Tally& t) {
-  int j = 0;  // first threshold with pit < p_j: lower bound over the table padded to 64 with +inf
-#pragma unroll
-  for (int step = 32; step > 0; step >>= 1) j += (pit < zt[j + step - 1]) ? 0 : step;
-  j += (pit < zt[j]) ? 0 : 1;
-  j = j > K ? K : j;
-  atomicAdd(&bins[j], 1u);
-  ++t.n;
-  t.nll += (double)nll;
-  t.crps += (double)crps;
-  t.pit += (double)pit;
-}
-
-__device__ __forceinline__ float pick(const float4& v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
-__device__ __forceinline__ void put(float4& v, int k, float x) {
-  v.x = k == 0 ? x : v.x;
-  v.y = k == 1 ? x : v.y;
-  v.z = k == 2 ? x : v.z;
-  v.w = k == 3 ? x : v.w;
-}
-
-// thresholds and per-wave bins in; one partial row per workgroup out (red / redn: 256 entries per quantity)
-__device__ __forceinline__ void block_prologue(const Args& a, float* zt, u32* bins) {
-  const int tid = threadIdx.x;
-  if (tid <= kMaxK) zt[tid] = tid < a.K ? a.pk[tid] : INFINITY;
-  for (int i = tid; i < 4 * (kBins + 3); i += 256) bins[i] = 0u;
-  __syncthreads();
-}
-
-__device__ __forceinline__ void block_epilogue(const Args& a, const Tally& t, const u32* bins, double* red, u32* redn) {
-  const int tid = threadIdx.x;
-  red[tid] = t.nll;
-  red[256 + tid] = t.crps;
-  red[512 + tid] = t.pit;
-  redn[tid] = t.n;
-  redn[256 + tid] = t.nm;
-  redn[512 + tid] = t.nf;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        red[256 * k + tid] += red[256 * k + tid + off];
-        redn[256 * k + tid] += redn[256 * k + tid + off];
-      }
-    }
-    __syncthreads();
-  }
-  u64* row = a.part + (size_t)blockIdx.x * kAccWords;
-  constexpr int W = kBins + 3;
-  if (tid < kBins) row[tid] = (u64)bins[tid] + bins[W + tid] + bins[2 * W + tid] + bins[3 * W + tid];
-  if (tid >= 65 && tid < 68) row[tid] = redn[256 * (tid - 65)];
-  if (tid >= 68 && tid < 71) row[tid] = as_u64(red[256 * (tid - 68)]);
 }
 
 // Registers.  VEC: hw % 4 == 0 and every pointer 16-byte aligned -> a float4 of pixels per thread per step (2 S + 1 (+ 1)
@@ -376,11 +300,24 @@ __global__ __launch_bounds__(256) void score_lds_kernel(Args a) {
   block_epilogue(a, t, bins, red, (u32*)(red + 3 * 256));
 }
 
-// acc[j] += sum over the partial rows of column j (one workgroup per column; rows in a fixed order)
+// acc[j] += sum over the partial rows of column j (one workgroup per column; rows in a fixed order).  Column kIterWord,
+// folded only after the evidential kernel, is a running maximum instead.
 __global__ __launch_bounds__(256) void score_fold_kernel(const u64* __restrict__ part, int rows, u64* __restrict__ acc) {
   __shared__ u64 ri[256];
   __shared__ double rd[256];
   const int j = blockIdx.x, tid = threadIdx.x;
+  if (j == kIterWord) {
+    u64 m = 0;
+    for (int r = tid; r < rows; r += 256) m = max(m, part[(size_t)r * kAccWords + j]);
+    ri[tid] = m;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+      if (tid < off) ri[tid] = max(ri[tid], ri[tid + off]);
+      __syncthreads();
+    }
+    if (tid == 0) acc[j] = max(acc[j], ri[0]);
+    return;
+  }
   const bool dbl = j >= 68;
   u64 s = 0;
   double d = 0.0;
@@ -418,6 +355,12 @@ __global__ void score_finalize_kernel(const u64* __restrict__ acc, int K, double
   out[K + 1] = (double)acc[66];
   out[K + 2] = (double)acc[67];
   for (int k = 0; k < 3; ++k) out[K + 3 + k] = n ? as_double(acc[68 + k]) / (double)n : nan;
+}
+
+int fold_partials(Workspace* ws, int rows, int columns, hipStream_t stream) {
+  hipLaunchKernelGGL(score_fold_kernel, dim3(columns), dim3(256), 0, stream, &ws->part[0][0], rows, ws->acc);
+  MIMO_KERNEL_CHECK();
+  return MIMO_OK;
 }
 
 typedef void (*Kernel)(Args);
@@ -472,9 +415,7 @@ extern "C" int mimo_score_accumulate(const float* p1, const float* p2, const flo
                                                      : (vec ? pick_kernel<1, true>(members) : pick_kernel<1, false>(members));
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   MIMO_KERNEL_CHECK();
-  hipLaunchKernelGGL(score_fold_kernel, dim3(kFolded), dim3(256), 0, (hipStream_t)stream, &ws->part[0][0], blocks, ws->acc);
-  MIMO_KERNEL_CHECK();
-  return MIMO_OK;
+  return fold_partials(ws, blocks, kFolded, (hipStream_t)stream);
 }
 
 extern "C" int mimo_score_finalize(const void* workspace, int32_t num_thresholds, double* out, mimo_stream stream) {

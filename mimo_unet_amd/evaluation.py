@@ -355,6 +355,19 @@ def check_score_shapes(p1, p2, label, mask, channel: int) -> Tuple[int, int, int
     return b, s, c, h, w, mc
 
 
+def check_evidential_score_shapes(logits, label, mask) -> Tuple[int, int, int]:
+    """(B, H, W) of one `PredictiveScorer.update_evidential`, or ValueError: logits [B,4,H,W], label [B,1,H,W], mask None,
+    [B,H,W] or [B,1,H,W]."""
+    if logits.dim() != 4 or logits.shape[1] != 4:
+        raise ValueError(f"update_evidential expects logits of shape [B,4,H,W], got {tuple(logits.shape)}")
+    b, _, h, w = logits.shape
+    if tuple(label.shape) != (b, 1, h, w):
+        raise ValueError(f"label has shape {tuple(label.shape)}, expected {(b, 1, h, w)}")
+    if mask is not None and tuple(mask.shape) not in ((b, h, w), (b, 1, h, w)):
+        raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(b, h, w)} or {(b, 1, h, w)}")
+    return int(b), int(h), int(w)
+
+
 def mixture_of(ensemble) -> Tuple[str, float, float, int]:
     """(loss, eps_min, eps_max, S_total) of the mixture an `EnsembleModule` predicts: S_total = passes x the subnetworks of
     every checkpoint.  A bare `EvidentialUnetModel` raises NotImplementedError (its Student-t predictive needs an
@@ -413,6 +426,9 @@ class PredictiveScorer:
     clip both to [0, 1] as the reference's scripts do).  A pixel is skipped when mask == 0 (`n_masked`) or when its label or
     any member's p1 / p2 is not finite (`n_nonfinite`).
 
+    The evidential baseline goes through `update_evidential` / `update_from_evidential`: the same three rules of the
+    Student-t posterior predictive of its Normal-Inverse-Gamma heads, into the same accumulators (one network: S = 1).
+
     `update` is asynchronous on the current stream; `compute` is the one host copy.  Single stream, single device, as
     `UncertaintyEvaluator`."""
 
@@ -470,6 +486,54 @@ class PredictiveScorer:
         finally:
             ensemble.keep_on_device, ensemble.return_raw_predictions = keep, raw
         self.update(p1, p2, label.to(p1.device), None if mask is None else mask.to(p1.device), loss, eps_min, eps_max)
+
+    # ------------------------------------------------------------------ the evidential model's Student-t predictive
+    def _accumulate_evidential(self, logits, label, mask, maps):
+        b, h, w = check_evidential_score_shapes(logits, label, mask)
+        ts = []
+        for name, t in (("logits", logits), ("label", label)) + ((("mask", mask),) if mask is not None else ()):
+            if not t.is_cuda:
+                raise L.MimoHipError(f"PredictiveScorer: {name} is not on the GPU (there is no CPU path)")
+            ts.append(t.detach().to(device=self.device, dtype=torch.float32).contiguous())
+        with torch.cuda.device(self.device):
+            out = [torch.empty(b, h, w, dtype=torch.float32, device=self.device) for _ in range(3)] if maps else [None] * 3
+            L.check(self._lib.mimo_score_accumulate_evidential(
+                ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr() if mask is not None else None, b, h * w,
+                self._p_dev.data_ptr(), self.expected_p.size, L.ptr(out[0]) or None, L.ptr(out[1]) or None,
+                L.ptr(out[2]) or None, self._ws.data_ptr(), L.current_stream()), "mimo_score_accumulate_evidential")
+        return tuple(out)
+
+    def update_evidential(self, logits, label, mask=None) -> None:
+        """logits [B,4,H,W] (the raw outputs of an `EvidentialUnetModel`: `model._logits(image)`), label [B,1,H,W], mask
+        [B,H,W] or [B,1,H,W], all on the device.  Scores the Student-t posterior predictive of the Normal-Inverse-Gamma heads
+        (nu = 2 alpha, location mu, scale sqrt(beta (1 + v) / (v alpha)); `mimo_score_accumulate_evidential`) into the same
+        accumulators as `update`.  A pixel whose v or beta has underflowed to 0 counts as `n_nonfinite`.  Enqueues one pass;
+        returns without synchronising.  (The model has one target: `channel` plays no part.)"""
+        self._accumulate_evidential(logits, label, mask, False)
+
+    def score_maps_evidential(self, logits, label, mask=None):
+        """`update_evidential`, which also returns the per-pixel (pit, nll, crps) as [B,H,W] device tensors (NaN where
+        skipped)."""
+        return self._accumulate_evidential(logits, label, mask, True)
+
+    def update_from_evidential(self, model, image, label, mask=None) -> None:
+        """Run an `EvidentialUnetModel` (in eval mode) on `image` — the no-grad forward on its inference plan — and score
+        its logits with one `update_evidential`, without leaving the device.  Anything else is refused with TypeError before
+        a kernel is launched (an `EnsembleModule` goes through `update_from`)."""
+        from .models.evidential_unet import EvidentialUnetModel
+        if not isinstance(model, EvidentialUnetModel):
+            raise TypeError(f"PredictiveScorer.update_from_evidential scores an EvidentialUnetModel, not a {type(model).__name__}")
+        model.require_eval("PredictiveScorer.update_from_evidential")
+        if image.dim() != 4 or image.shape[1] != model.in_channels:
+            raise ValueError("channel dimension must match in_channels")
+        b, _, h, w = image.shape
+        if tuple(label.shape) != (b, 1, h, w):
+            raise ValueError(f"label has shape {tuple(label.shape)}, expected {(b, 1, h, w)}")
+        if mask is not None and tuple(mask.shape) not in ((b, h, w), (b, 1, h, w)):
+            raise ValueError(f"mask has shape {tuple(mask.shape)}, expected {(b, h, w)} or {(b, 1, h, w)}")
+        with torch.no_grad():
+            logits = model._logits(image.detach())
+        self.update_evidential(logits, label.to(logits.device), None if mask is None else mask.to(logits.device))
 
     def compute(self) -> dict:
         k = self.expected_p.size

@@ -9,10 +9,12 @@ of the host route (the same tables from `.cpu()` copies: numpy argsort + 41 quan
     python scripts/evaluate_uncertainty.py --evidential --model_checkpoint_paths ev.ckpt --batch_dir batches/ --result_dir out
     python scripts/evaluate_uncertainty.py --synthetic 8 --sources combined aleatoric epistemic --result_dir out
     python scripts/evaluate_uncertainty.py --synthetic_model --synthetic 2 --monte_carlo_steps 4 --scores --result_dir out
+    python scripts/evaluate_uncertainty.py --evidential --synthetic 2 --scores --result_dir out
 
 --scores: the proper scoring rules of the mixture predictive too (NLL, CRPS, PIT calibration of the equal-weight mixture of every
 member density: `PredictiveScorer`), written to scores.csv and calibration_mixture.csv.  With a model the members are the
-ensemble's raw outputs; with --synthetic alone three seeded Laplace members per pixel.
+ensemble's raw outputs; with --synthetic alone three seeded Laplace members per pixel; with --evidential the one network's
+Student-t posterior predictive (`PredictiveScorer.update_from_evidential`, reported with members = 1) under the same rules.
 
 --sources: the sparsification curve per uncertainty source and the oracle curve (sparsification.csv), AUSE / AURG (ause.csv).
 
@@ -101,8 +103,6 @@ def main():
         from mimo.models.evidential_unet import EvidentialUnetModel
         if len(args.model_checkpoint_paths) > 1 or args.monte_carlo_steps:
             ap.error("--evidential takes one checkpoint and no --monte_carlo_steps")
-        if args.scores:
-            ap.error("--scores: the evidential model's Student-t predictive is not scored")
         if args.model_checkpoint_paths:
             ensemble = EvidentialUnetModel.load_from_checkpoint(args.model_checkpoint_paths[0])
         else:
@@ -149,7 +149,9 @@ def main():
             image, label = (torch.as_tensor(b[k]).to(dev) for k in ("image", "label"))
             mask = torch.as_tensor(b["mask"]).to(dev) if b.get("mask") is not None else None
             masked = masked or mask is not None
-            if scorer is not None:  # a second forward: the evaluator's maps and the raw members are two return modes
+            if scorer is not None and args.evidential:  # a second forward; the Student-t predictive of the one network
+                scorer.update_from_evidential(ensemble, image, label, mask)
+            elif scorer is not None:  # a second forward: the evaluator's maps and the raw members are two return modes
                 scorer.update_from(ensemble, image, label, mask)
             if args.no_host_route:
                 ev.update_from(ensemble, image, label, mask)  # the three-line form of INTEGRATION.md
@@ -190,7 +192,7 @@ def main():
     if scorer is not None:
         scores = scorer.compute()
         scorer.write_csv(args.result_dir, scores)
-        members = 3 if ensemble is None else max(1, args.monte_carlo_steps) * ensemble.num_subnetworks
+        members = 3 if ensemble is None else 1 if args.evidential else max(1, args.monte_carlo_steps) * ensemble.num_subnetworks
         res["scores"] = {k: scores[k] for k in ("n", "nll", "crps", "pit_mean", "calibration_error")}
         res["scores"].update(members=members, coverage_90=min(scores["coverage"].items(), key=lambda kv: abs(kv[0] - 0.9))[1])
     if "ause" in tables:

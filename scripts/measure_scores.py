@@ -1,6 +1,7 @@
 """Timings of `PredictiveScorer` on the GPU, next to a torch restatement of the same formulas on the same device:
 
     python scripts/measure_scores.py            # writes profiles/scores/summary.txt
+    python scripts/measure_scores.py --evidential   # adds the evidential model's section to it
 
 `update` and `compute` at 5 x 256^2 and 32 x 256^2 pixels, both losses, S_total = 3 (one MIMO model), 12 (four checkpoints)
 and 24 (8 MC passes x 3).  Each figure is the median (and the minimum) of --reps calls between HIP events after --warmup
@@ -78,8 +79,75 @@ def timed(fn, warmup, reps):
     return float(np.median(ms)), float(np.min(ms))
 
 
+EVIDENTIAL_MARK = "PredictiveScorer.update_evidential"
+
+
+def evidential_leg(args, dev):
+    """`update_evidential` at --evidential_batch x size^2 next to `update` at S = 1 (the same 1-member traffic: the
+    bandwidth yardstick) and next to the route a user had before: the logits copied to the host and the three quantities
+    from scipy.stats.t.  Replaces the section of --out that starts at EVIDENTIAL_MARK (or appends one)."""
+    import time
+    B, size = args.evidential_batch, args.size
+    g = torch.Generator(device=dev).manual_seed(77)
+    logits = torch.randn((B, 4, size, size), generator=g, device=dev) * 1.5
+    logits[:, 2] = torch.rand((B, size, size), generator=g, device=dev) * 12.0 - 3.0  # alpha from 1.05 to 10
+    label = logits[:, :1] + torch.randn((B, 1, size, size), generator=g, device=dev) * 1.5
+    pixels = B * size * size
+    sc = PredictiveScorer()
+    upd = timed(lambda: sc.update_evidential(logits, label), args.warmup, args.reps)
+    sc.reset()
+    sc.update_evidential(logits, label)
+    res = sc.compute()
+    worst_iterations = int(sc._ws[71])
+    mix = PredictiveScorer()
+    p1, p2 = logits[:, None, :1].contiguous(), logits[:, None, 1:2].contiguous()
+    one = timed(lambda: mix.update(p1, p2, label, None, "laplace_nll"), args.warmup, args.reps)
+    lines = [f"{EVIDENTIAL_MARK} on {torch.cuda.get_device_name(0)}: the Student-t predictive of the evidential model, {B} x {size} x "
+             f"{size} pixels, no mask, no maps; HIP-event times in ms, median (min) of {args.reps} calls after {args.warmup} warm-up calls",
+             f"update_evidential (20 B/pixel)         {upd[0]:8.3f} ({upd[1]:6.3f})  = {20 * pixels / (upd[1] * 1e-3) / 1e9:6.0f} GB/s at the min",
+             f"update, Laplace, S = 1 (12 B/pixel)    {one[0]:8.3f} ({one[1]:6.3f})  = {12 * pixels / (one[1] * 1e-3) / 1e9:6.0f} GB/s at the min",
+             f"update_evidential / update at S = 1: {upd[0] / one[0]:.1f} x (double-precision arithmetic, not traffic: at the "
+             f"S = 1 kernel's bytes per second its 20 B/pixel would take {20 * pixels / (12 * pixels / one[1]):.3f} ms)",
+             f"most continued-fraction iterations of any pixel: {worst_iterations} (cap 160); n = {res['n']}, mean nll {res['nll']:.6f}, "
+             f"mean crps {res['crps']:.6f}, mean pit {res['pit_mean']:.6f}"]
+    try:
+        from scipy import stats
+    except ImportError:
+        lines.append("host route (scipy.stats.t): scipy is not importable here: not measured")
+    else:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        l, y = logits.cpu().numpy().astype(np.float64), label.cpu().numpy()[:, 0].astype(np.float64)
+        sp = lambda x: np.where(x > 20, x, np.log1p(np.exp(np.minimum(x, 20))))
+        mu, v, alpha, beta = l[:, 0], sp(l[:, 1]), sp(l[:, 2]) + 1, sp(l[:, 3])
+        nu, sigma = 2 * alpha, np.sqrt(beta * (1 + v) / (v * alpha))
+        z = (y - mu) / sigma
+        F, f = stats.t.cdf(z, nu), stats.t.pdf(z, nu)
+        from scipy.special import gammaln
+        lb1 = np.log(np.pi) / 2 + gammaln(alpha) - gammaln(alpha + 0.5)
+        lb2 = np.log(np.pi) / 2 + gammaln(nu - 0.5) - gammaln(nu)
+        nll = -(stats.t.logpdf(z, nu) - np.log(sigma))
+        crps = sigma * (z * (2 * F - 1) + 2 * f * (nu + z * z) / (nu - 1) - 2 * np.sqrt(nu) / (nu - 1) * np.exp(lb2 - 2 * lb1))
+        host_s = time.perf_counter() - t0
+        diff = max(abs(nll.mean() - res["nll"]) / abs(res["nll"]), abs(crps.mean() - res["crps"]) / abs(res["crps"]),
+                   abs(F.mean() - res["pit_mean"]) / abs(res["pit_mean"]))
+        lines.append(f"host route (logits to the host, scipy.stats.t cdf / pdf / logpdf in float64, one call each): {host_s * 1e3:.0f} ms "
+                     f"= {host_s * 1e3 / upd[0]:.0f} x update_evidential; max rel diff of the three means {diff:.2e}")
+    print("\n".join(lines), flush=True)
+    old = open(args.out).read().splitlines() if os.path.exists(args.out) else []
+    keep = next((i for i, line in enumerate(old) if line.startswith(EVIDENTIAL_MARK)), len(old))
+    old = old[:keep]
+    while old and not old[-1].strip():
+        old.pop()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(old + ([""] if old else []) + lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--evidential", action="store_true", help="only the evidential leg: appended to --out")
+    ap.add_argument("--evidential_batch", type=int, default=32)
     ap.add_argument("--out", default=os.path.join("profiles", "scores", "summary.txt"))
     ap.add_argument("--batches", type=int, nargs="+", default=[5, 32])
     ap.add_argument("--members", type=int, nargs="+", default=[3, 12, 24])
@@ -92,6 +160,9 @@ def main():
         raise SystemExit("measure_scores.py needs a GPU: nothing is measured without one")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if args.evidential:
+        evidential_leg(args, dev)
+        return
     lines = [f"PredictiveScorer on {torch.cuda.get_device_name(0)}: HIP-event times in ms, median (min) of {args.reps} calls after "
              f"{args.warmup} warm-up calls; {args.size} x {args.size} images, one channel, no mask",
              "torch: the same formulas in fp32 torch on the same GPU ([B,S,S,H,W] broadcast in image chunks); "
